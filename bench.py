@@ -23,7 +23,8 @@ solve; the timed region ends when every gather has landed.
 
 Prints ONE JSON line on rank 0 with `roofline` (algorithmic HBM bytes of one launch / its HIP-event
 duration), `cpu_baseline` (oracle/admm_port.c on the host cores, bounded sample, N = 1 only) and the
-kernel-only rate of the same step (`kernel_only`).
+kernel-only rate of the same step (`kernel_only`).  `--dump-outputs DIR` also writes what the last timed step returned
+(`dump_outputs`): the inputs depend on the arguments only, so two builds can be compared array by array.
 """
 from __future__ import annotations
 
@@ -62,7 +63,40 @@ def parse(argv=None):
     ap.add_argument("--one-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--rehearse-collective", action="store_true",
                     help="rehearsal only: run the per-step all-gather (and its process group) even with one rank")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to rank 0 as DIR/<name>.npy (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_X_BYTES = 48 << 20   # cap of the schedules in a --dump-outputs directory (the whole directory stays under 64 MB)
+
+
+def dump_outputs(out_dir, results):
+    """What the timed path hands its caller, from the last timed step: the per-problem scalars of every problem
+    (status, iterations, residuals, objective) and the schedules x, of a fixed seeded sample of the problems when all
+    of them would exceed DUMP_X_BYTES (`x_index` says which).  Everything float64, so that two builds compare
+    file by file."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    x = np.concatenate([r.x for r in results])
+    per_problem = x[0].nbytes
+    n = x.shape[0]
+    keep = min(n, DUMP_X_BYTES // per_problem)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    arrays = {"x": x[idx], "x_index": idx}
+    for name in ("status", "iters", "pri_res", "dua_res", "obj"):
+        arrays[name] = np.concatenate([getattr(r, name) for r in results])
+    written = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": os.path.abspath(out_dir), "files": sorted(name + ".npy" for name in arrays), "bytes": written,
+            "problems": int(n), "x_problems": int(keep)}
 
 
 def spawn_ranks(args) -> int:
@@ -551,6 +585,7 @@ def main():
         elapsed = float(tmax.item())
 
     results = runs[(args.steps - 1) % 2 if collective else 0][1]
+    dumped = dump_outputs(args.dump_outputs, results) if args.dump_outputs and rank == 0 else None
     status_all = np.concatenate([r.status for r in results])
     iters_all = np.concatenate([r.iters for r in results])
     solved = int((status_all == 1).sum())
@@ -666,6 +701,8 @@ def main():
                 "anderson_columns": handle.accel_columns(Tm, K, opts),
             },
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             # a CPU sample of >= 32 problems per thread: the first 16 batches (4,096 problems) of the timed workload
             ncb = max(1, min(G, 4096 // B))

@@ -139,3 +139,38 @@ def test_bench_multi_rank_path_runs(flags, n_gpus):
     assert d["solver"]["solved"] == d["solver"]["problems"] == n_gpus * 8 * 256
     assert "all-gather" in d["config"]["parallelism"] or n_gpus == 1
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
+
+
+def test_dump_outputs_writes_float64_under_the_cap_and_the_same_sample_every_time(tmp_path):
+    """`--dump-outputs DIR`: what the last timed step returned, every array float64, the directory under 64 MB; the
+    schedules of the headline step (16,384 x 54 x 12 doubles) do not fit and are sampled, the same problems each run."""
+    from adacharge_amd.backend import BatchResult
+
+    G, B, N, Tm = 64, 256, 54, 12
+    rng = np.random.default_rng(3)
+    results = [BatchResult(x=rng.random((B, N, Tm)), status=np.ones(B, np.int32), iters=rng.integers(1, 900, B).astype(np.int32),
+                           pri_res=rng.random(B), dua_res=rng.random(B), obj=rng.random(B)) for _ in range(G)]
+    info = [bench.dump_outputs(str(tmp_path / d), results) for d in ("a", "b")]
+    assert info[0]["problems"] == G * B and 0 < info[0]["x_problems"] < G * B and info[0]["bytes"] <= 64e6
+    names = ("x", "x_index", "status", "iters", "pri_res", "dua_res", "obj")
+    assert sorted(info[0]["files"]) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in info[0]["files"]) <= 64e6
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    idx = got["x_index"].astype(np.int64)
+    assert np.array_equal(got["x_index"], idx) and (np.diff(idx) > 0).all()
+    assert np.array_equal(got["x"], np.concatenate([r.x for r in results])[idx])
+    assert np.array_equal(got["iters"], np.concatenate([r.iters for r in results]))
+    for n in names:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    # a step that fits is written whole
+    small = bench.dump_outputs(str(tmp_path / "c"), results[:2])
+    assert small["x_problems"] == small["problems"] == 2 * B
+    assert np.array_equal(np.load(tmp_path / "c" / "x.npy"), np.concatenate([r.x for r in results[:2]]))
+
+
+def test_steps_sets_the_timed_steps_and_must_be_positive():
+    assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
