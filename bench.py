@@ -21,10 +21,15 @@ For N > 1 each step leaves the rank's schedules in HBM as well (acnqp_results.x_
 job's single collective, one RCCL all-gather of the schedules over xGMI, overlapped with the next step's
 solve; the timed region ends when every gather has landed.
 
-Prints ONE JSON line on rank 0 with `roofline` (algorithmic HBM bytes of one launch / its HIP-event
-duration), `cpu_baseline` (oracle/admm_port.c on the host cores, bounded sample, N = 1 only) and the
-kernel-only rate of the same step (`kernel_only`).  `--dump-outputs DIR` also writes what the last timed step returned
-(`dump_outputs`): the inputs depend on the arguments only, so two builds can be compared array by array.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline (`value`,
+`ms_per_step`, the step's `config`, `pcie` and `solver` counts); nothing else runs on the GPU or the host cores.
+`--full` adds, after the timed steps, everything else the bench measures and checks: the kernel-only rate of the same
+step (`kernel_only`, one lone launch), `roofline` on that launch (algorithmic flops and HBM bytes / its HIP-event
+duration), for N > 1 the check that the gather carries the schedules, and for N = 1 `cpu_baseline` and `parity`
+(oracle/admm_port.c on the host cores, bounded sample; `--no-cpu-baseline` skips them) and the other BASELINE.json
+configurations (`host_inclusive`, `polish`, `strict_batch256`, `other_configs`; `--no-other-configs` skips them).
+`--dump-outputs DIR` also writes what the last timed step returned (`dump_outputs`): the inputs depend on the
+arguments only, so two builds can be compared array by array.
 """
 from __future__ import annotations
 
@@ -54,9 +59,12 @@ def parse(argv=None):
     ap.add_argument("--constraint-type", default="SOC", choices=["SOC", "LINEAR"])
     ap.add_argument("--precision", type=int, default=64, choices=[64])
     ap.add_argument("--pageable", action="store_true", help="problem / result arrays in pageable host memory")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the lone launch (kernel_only, roofline), the gather check (N > 1), "
+                         "the CPU baseline and the other BASELINE.json configurations (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the legs that time the other BASELINE.json configurations after the headline (N = 1 only)")
+                    help="with --full: skip the legs that time the other BASELINE.json configurations after the headline (N = 1 only)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + --one-device rehearses the N > 1 path on a single-GPU box")
@@ -216,13 +224,13 @@ def other_workloads():
         "cfg3_site0_T12_b1024": lambda: cfg3_site(0),
         "cfg4_synth512_T48_b2048": cfg4,
         "stress_caltech54_T144_b256": stress144,
-        # eight workgroups' worth of problems per CU: the long-horizon kernel's bandwidth-bound regime (in the default
+        # eight workgroups' worth of problems per CU: the long-horizon kernel's bandwidth-bound regime (in the --full
         # run since round 4, so that its HBM fraction is driver-timed)
         "stress_caltech54_T144_b2048": lambda: stress144(2048),
     }
 
 
-# legs of `other_workloads` the default `python bench.py` run leaves out (profiling targets only)
+# legs of `other_workloads` that `python bench.py --full` leaves out (profiling targets only)
 NOT_IN_DEFAULT_RUN = ()
 
 
@@ -587,13 +595,12 @@ def main():
     results = runs[(args.steps - 1) % 2 if collective else 0][1]
     dumped = dump_outputs(args.dump_outputs, results) if args.dump_outputs and rank == 0 else None
     status_all = np.concatenate([r.status for r in results])
-    iters_all = np.concatenate([r.iters for r in results])
     solved = int((status_all == 1).sum())
     if collective:
         cnt = torch.tensor([solved, per_step], dtype=torch.int64, device=gdev)
         dist.all_reduce(cnt)
         solved_all, total_all = int(cnt[0]), int(cnt[1])
-        if rank == 0:   # the gather really carries this rank's schedules, and they are what came back to the host
+        if args.full and rank == 0:   # the gather really carries this rank's schedules, and they are what came back to the host
             k = (args.steps - 1) % 2
             assert torch.equal(gathered[k][:per_step].to(dev), x_dev[k])
             assert np.array_equal(x_dev[k][:B].cpu().numpy(), results[0].x)
@@ -603,7 +610,7 @@ def main():
     # kernel-only rate of the same step, outside the timed region: the step's problems resident in HBM, ONE launch of
     # the device-pointer entry, HIP events around it (what `value` would be with free copies)
     kernel_only = None
-    if rank == 0:
+    if args.full and rank == 0:
         from adacharge_amd.backend import DeviceBatch
 
         dbig = DeviceBatch(ProblemBatch.concatenate(batches), dev)
@@ -622,28 +629,7 @@ def main():
         # launches of one step differ in size (512, 1,024, then 2,048 problems: acn_qp_api.hip, run_pipeline): the
         # roofline is stated per MEAN launch -- mean problems per launch over mean launch duration
         launch_b = per_step * args.steps / max(len(kernel_ms), 1)
-        k_avg_ms = float(np.mean(kernel_ms))
         _, per_qp, _ = algorithmic_bytes(launch_b, N, Tm, K, batch.site)
-        traffic = None
-        tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tfile):   # committed result of the separate rocprofv3 --pmc passes (same command)
-            try:
-                tj = json.load(open(tfile))
-                # launches differ in size: scale the measured bytes per problem to this run's mean launch
-                traffic = tj["hbm_bytes_per_problem"] * launch_b if tj.get("hbm_bytes_per_problem") else tj.get("hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
-        fl_dense = flops_per_iteration(N, Tm, batch.site)
-        whole = ProblemBatch.concatenate(batches)
-        fl_sparse = flops_per_iteration_sparse(whole)
-        it_sum = float(iters_all.sum())
-        # the dominant kernel is timed WITHOUT neighbours: one launch over the step's problems (kernel_only, HIP events on
-        # the launch stream); the pipelined launches of the timed region overlap on four streams, so their durations
-        # include the CUs they cede to each other and are reported beside it (pipelined_*)
-        lone_ms = kernel_only["launch_ms"]
-        abytes1, _, _ = algorithmic_bytes(per_step, N, Tm, K, batch.site)
-        tf_sparse = it_sum * fl_sparse / (lone_ms * 1e-3) / 1e12
-        tf_dense = it_sum * fl_dense / (lone_ms * 1e-3) / 1e12
         host_bytes = per_step * (per_qp - 0)   # H2D of the inputs + D2H of the results = the algorithmic bytes per QP
         out = {
             "metric": "MPC QP solves/sec whole-node, 54 EVSE x horizon 12; max rate residual vs cvxpy",
@@ -668,7 +654,31 @@ def main():
                 "n_evse": N, "horizon": T, "constraint_type": args.constraint_type,
                 "parallelism": f"dp{world} (own snapshots per GPU" + (", one RCCL all-gather of schedules per step)" if world > 1 else ")"),
             },
-            "roofline": {
+        }
+        if args.full:
+            k_avg_ms = float(np.mean(kernel_ms))
+            traffic = None
+            tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            if os.path.exists(tfile):   # committed result of the separate rocprofv3 --pmc passes (same command)
+                try:
+                    tj = json.load(open(tfile))
+                    # launches differ in size: scale the measured bytes per problem to this run's mean launch
+                    traffic = tj["hbm_bytes_per_problem"] * launch_b if tj.get("hbm_bytes_per_problem") else tj.get("hbm_bytes_per_launch")
+                except Exception:
+                    traffic = None
+            fl_dense = flops_per_iteration(N, Tm, batch.site)
+            whole = ProblemBatch.concatenate(batches)
+            fl_sparse = flops_per_iteration_sparse(whole)
+            iters_all = np.concatenate([r.iters for r in results])
+            it_sum = float(iters_all.sum())
+            # the dominant kernel is timed WITHOUT neighbours: one launch over the step's problems (kernel_only, HIP events on
+            # the launch stream); the pipelined launches of the timed region overlap on four streams, so their durations
+            # include the CUs they cede to each other and are reported beside it (pipelined_*)
+            lone_ms = kernel_only["launch_ms"]
+            abytes1, _, _ = algorithmic_bytes(per_step, N, Tm, K, batch.site)
+            tf_sparse = it_sum * fl_sparse / (lone_ms * 1e-3) / 1e12
+            tf_dense = it_sum * fl_dense / (lone_ms * 1e-3) / 1e12
+            out["roofline"] = {
                 # register / LDS-resident iterative solver: HBM is touched once per problem, so the roof that
                 # can bind is the fp64 arithmetic one (vector = matrix peak on MI355X); the HBM view is reported beside it
                 "bound": "mfma", "binding_unit": "valu (fp64: the vector ALU and the matrix cores share the 78.6 TF peak; one wave per "
@@ -692,18 +702,17 @@ def main():
                 "note": "achieved = ALGORITHMIC flops (SURVEY.md 8d: 4 nnz(A) + 12 (n + m) + 4 Mg^2 T per iteration, sparse G) x "
                         "iterations run / the duration of ONE non-overlapped launch over the step's problems; the dense count "
                         "is what the MFMA chains execute (G and Q dense)",
-            },
-            "kernel_only": kernel_only,
-            "pcie": {"host_bytes_per_step_per_gpu": int(host_bytes), "achieved_GBs_per_gpu": host_bytes * args.steps / elapsed / 1e9},
-            "solver": {
-                "solved": solved_all, "problems": total_all,
-                "eps_abs": opts.eps_abs, "eps_rel": opts.eps_rel, "reg_rel": opts.reg_rel,
-                "anderson_columns": handle.accel_columns(Tm, K, opts),
-            },
+            }
+            out["kernel_only"] = kernel_only
+        out["pcie"] = {"host_bytes_per_step_per_gpu": int(host_bytes), "achieved_GBs_per_gpu": host_bytes * args.steps / elapsed / 1e9}
+        out["solver"] = {
+            "solved": solved_all, "problems": total_all,
+            "eps_abs": opts.eps_abs, "eps_rel": opts.eps_rel, "reg_rel": opts.reg_rel,
+            "anderson_columns": handle.accel_columns(Tm, K, opts),
         }
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # a CPU sample of >= 32 problems per thread: the first 16 batches (4,096 problems) of the timed workload
             ncb = max(1, min(G, 4096 // B))
             cb, parity = cpu_baseline_leg(ProblemBatch.concatenate(batches[:ncb]), np.concatenate([r.x for r in results[:ncb]]),
@@ -711,7 +720,7 @@ def main():
                                           accel_mem=handle.accel_columns(Tm, K, opts), first=B)
             out["cpu_baseline"] = cb
             out["parity"] = parity
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             out["host_inclusive"] = host_inclusive_leg(infra, iface, objective, site, handle, opts, horizon=T)
             out["polish"] = handle.polish_stats()
             out["strict_batch256"] = strict_batch256_leg(handle, batches[0], opts)

@@ -1,5 +1,6 @@
 """The JSON line bench.py prints is a contract with the driver: check the committed record of the last GPU run
-(profiles/r04_bench.json, written by `python bench.py` on an MI355X) and the bookkeeping helpers, on the CPU."""
+(profiles/r04_bench.json, written on an MI355X by `python bench.py`, which then ran every leg `--full` runs today) and
+the bookkeeping helpers, on the CPU."""
 import json
 import os
 
@@ -119,8 +120,8 @@ def test_algorithmic_bytes_and_flops_bookkeeping():
 ])
 def test_bench_multi_rank_path_runs(flags, n_gpus):
     """the N > 1 code of bench.py (process group, x_dev, the per-step all-gather overlapped with the
-    next solve, the max-over-ranks clock, the gather assert) is run on every GPU test pass, so it cannot rot unseen
-    until an 8-GPU node appears.  bench.py is started as a CHILD process (for --gpus 2 it spawns its ranks itself,
+    next solve, the max-over-ranks clock, the gather assert of `--full`) is run on every GPU test pass, so it cannot rot
+    unseen until an 8-GPU node appears.  bench.py is started as a CHILD process (for --gpus 2 it spawns its ranks itself,
     before anything in it touches HIP).  No scaling number comes out of this: both ranks share one GPU."""
     import subprocess
     import sys
@@ -129,7 +130,7 @@ def test_bench_multi_rank_path_runs(flags, n_gpus):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batches", "8",
-           "--no-cpu-baseline", "--no-other-configs", *flags]
+           "--full", "--no-cpu-baseline", "--no-other-configs", *flags]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -139,6 +140,37 @@ def test_bench_multi_rank_path_runs(flags, n_gpus):
     assert d["solver"]["solved"] == d["solver"]["problems"] == n_gpus * 8 * 256
     assert "all-gather" in d["config"]["parallelism"] or n_gpus == 1
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
+
+
+FULL_ONLY = ("roofline", "kernel_only", "cpu_baseline", "parity", "host_inclusive", "polish", "strict_batch256", "other_configs")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_and_nothing_else(tmp_path):
+    """A run without `--full` times the steps and prints the headline: the contract fields, `value` from the timed
+    steps alone, and none of the legs that take runs of their own.  `--dump-outputs` still writes the last step."""
+    import subprocess
+    import sys
+
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batches", "8",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "pcie", "solver", "dump_outputs"):
+        assert k in d, k
+    assert d["unit"] == "QP solves/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - 8 * 256 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["solver"]["solved"] == d["solver"]["problems"] == 8 * 256
+    assert d["dump_outputs"]["problems"] == 8 * 256 and os.path.exists(tmp_path / "out" / "x.npy")
+    assert not any(k in d for k in FULL_ONLY), [k for k in FULL_ONLY if k in d]
 
 
 def test_dump_outputs_writes_float64_under_the_cap_and_the_same_sample_every_time(tmp_path):
@@ -167,6 +199,12 @@ def test_dump_outputs_writes_float64_under_the_cap_and_the_same_sample_every_tim
     small = bench.dump_outputs(str(tmp_path / "c"), results[:2])
     assert small["x_problems"] == small["problems"] == 2 * B
     assert np.array_equal(np.load(tmp_path / "c" / "x.npy"), np.concatenate([r.x for r in results[:2]]))
+
+
+def test_full_is_off_by_default():
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full"]).full is True
+    assert bench.parse(["--full", "--no-cpu-baseline", "--no-other-configs"]).no_other_configs is True
 
 
 def test_steps_sets_the_timed_steps_and_must_be_positive():

@@ -4,7 +4,7 @@ set -o pipefail
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-.}"
 OUT=gpurun_out/prof_${1:-traffic}
-ARGS="--steps 16 --warmup 8 --no-cpu-baseline"
+ARGS="--full --steps 16 --warmup 8 --no-cpu-baseline"
 rm -rf $OUT; mkdir -p $OUT
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py $ARGS > $OUT/bench_fetch.json 2> $OUT/fetch.err
 echo "fetch rc=$?"
