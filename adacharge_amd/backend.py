@@ -143,7 +143,12 @@ EXPORTED_SYMBOLS = (
     "acnqp_host_alloc",
     "acnqp_host_free",
     "acnqp_launch_count",
+    "acnqp_route",
 )
+
+# kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
+ROUTE_NAMES = {1: "wave1", 2: "wave2", 3: "wave3", 4: "wave4", 5: "wave5", 6: "tiled_ct1", 7: "tiled_ct2",
+               8: "long_lds", 9: "long_ws", 10: "stream", 11: "general"}
 
 _lib = None
 
@@ -210,6 +215,8 @@ def load_library():
     lib.acnqp_ordered_launch_count.restype = C.c_int64
     lib.acnqp_polish_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
     lib.acnqp_polish_stats.restype = C.c_int
+    lib.acnqp_route.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.acnqp_route.restype = C.c_int32
     _lib = lib
     return lib
 
@@ -516,6 +523,15 @@ class SiteHandle:
         buf = (C.c_float * int(capacity))()
         n = int(self._lib.acnqp_kernel_times(self._h, buf, int(capacity)))
         return [float(buf[k]) for k in range(n)]
+
+    def route(self, t_max: int, k_sessions: int, batch: int = 1):
+        """(family, polish): the kernel family (ROUTE_NAMES) a launch of ``batch`` problems of this padded shape runs,
+        and whether it runs the polish phase under default options (acnqp_route; no device work)."""
+        pol = C.c_int32(0)
+        fam = int(self._lib.acnqp_route(self._h, int(t_max), int(k_sessions), int(batch), C.byref(pol)))
+        if fam == 0:
+            raise ValueError(f"acnqp_route: no route for t_max={t_max}, k_sessions={k_sessions}, batch={batch}")
+        return ROUTE_NAMES[fam], bool(pol.value)
 
     def accel_columns(self, t_max: int, k_sessions: int, options: Options) -> int:
         """Anderson columns the kernels use for this problem shape under ``options`` (shape-only rule)."""

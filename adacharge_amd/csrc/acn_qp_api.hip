@@ -433,11 +433,64 @@ static bool long_shape(const acnqp_handle* h, int t_max, int k_sessions) {
   return !tiled_shape(h, t_max, k_sessions) && !stream_shape(h, t_max) && t_max <= 288 && h->dev64.MR <= 32;
 }
 
+// The kernel family a launch of this shape runs, and whether the shape may run the polish phase: the ONE place the choice
+// is made (launch() and acnqp_route both call it, so that what the tests query is what runs).  The launch size enters
+// only through the diagnostic ACNQP_WAVE_MIN_BATCH (wave_shape).
+struct Route {
+  int family = 0;     // ACNQP_ROUTE_*
+  int wv = 0;         // wave-per-problem variant (0: another family)
+  bool tiled = false, stream = false, lng = false, lds = false, on_chip = false;
+  int pol_blk = -1;   // LDS doubles for the blocks of the polish's system; -1: no polish for this shape
+};
+
+static Route route_for(const acnqp_handle* h, int t_max, int k_sessions, int batch) {
+  Route r;
+  const SiteDev* d = &h->dev64;
+  r.wv = acnqp::wave_shape(h->N, t_max, k_sessions, d->MR, h->has_max, batch);
+  r.tiled = r.wv > 0 || tiled_shape(h, t_max, k_sessions);   // (no workspace: state on chip)
+  r.stream = !r.tiled && stream_shape(h, t_max);
+  r.lng = !r.tiled && long_shape(h, t_max, k_sessions);
+  r.lds = r.lng && lds_long_shape(h, t_max);
+  r.on_chip = r.tiled || r.lds;
+  if (r.wv > 0) r.family = r.wv;   // ACNQP_ROUTE_WAVE1 ... ACNQP_ROUTE_WAVE5
+  else if (r.tiled) r.family = t_max <= 16 ? ACNQP_ROUTE_TILED_CT1 : ACNQP_ROUTE_TILED_CT2;
+  else if (r.stream) r.family = ACNQP_ROUTE_STREAM;
+  else if (r.lng) r.family = r.lds ? ACNQP_ROUTE_LONG_LDS : ACNQP_ROUTE_LONG_WS;
+  else r.family = ACNQP_ROUTE_GENERAL;
+  // ---- the polish (acn_qp_polish.hpp): small sites, separable objective, served by an on-chip kernel ------------------
+  static const bool no_polish = std::getenv("ACNQP_NO_POLISH") != nullptr;   // diagnostic
+  const int nrow_site = h->M + h->has_peak;
+  if (!no_polish && r.on_chip && h->N <= 64 && t_max <= 32 && k_sessions <= acnqp::kMaxK && !h->has_flat && !h->has_max &&
+      nrow_site > 0) {
+    // LDS of a polish workgroup: where the solver kernel runs two workgroups per CU (the headline shape: one column tile,
+    // one row tile, one session slot: 77 KB each) the polish takes no more than one of those slots, so that it starts as
+    // soon as ANY solver workgroup of a neighbouring stream's launch ends; elsewhere the whole CU
+    const bool two_per_cu = r.tiled && t_max <= 16 && d->MR == 16 && k_sessions == 1;
+    r.pol_blk = acnqp::polish_blocks_that_fit(h->N, t_max, h->Mg, nrow_site, acnqp::polish_max_sess(h->N, k_sessions),
+                                              two_per_cu ? 76 * 1024 : 160 * 1024);
+    if (r.pol_blk < 2 * nrow_site * (2 * nrow_site + 1) / 2) r.pol_blk = -1;   // not even one full block
+    // (never a function of the launch size: a problem's result must not depend on what it is batched with, DESIGN.md
+    //  2.3 -- tests/test_batch_invariance.py.  The polish phase runs behind the solver launch; on throughput-bound
+    //  launches it adds its rounds to the launch's end, DESIGN.md 2.3 has the price)
+  }
+  return r;
+}
+
 }  // namespace
 
 extern "C" {
 
 int32_t acnqp_abi_version(void) { return ACNQP_ABI_VERSION; }
+
+int32_t acnqp_route(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t batch, int32_t* polish) {
+  if (polish) *polish = 0;
+  if (!h || t_max < 1 || t_max > 4096 || k_sessions < 1 || k_sessions > 4096 || batch < 1) return 0;
+  const Route r = route_for(h, t_max, k_sessions, batch);
+  acnqp_options o;
+  acnqp_default_options(&o);
+  if (polish) *polish = (r.pol_blk >= 0 && o.polish_iters > 0 && o.polish_iters < o.max_iter) ? 1 : 0;
+  return r.family;
+}
 
 const char* acnqp_last_error(void) { return g_last_error.c_str(); }
 
@@ -475,6 +528,11 @@ int acnqp_create(const acnqp_site* site, int32_t device_id, acnqp_handle** out) 
   const int expect = (site->cone == ACNQP_CONE_SOC ? 2 * M : M) + (site->has_peak ? 1 : 0) + (site->has_flat ? 1 : 0) + (site->has_max ? 1 : 0);
   if (M < 0 || Mg != expect || Mg > 48)
     return fail(ACNQP_ERR_INVALID, "acnqp_create: n_rows inconsistent with n_infra/cone/has_peak/has_flat/has_max or > 48");
+  // the kernels' row tiles: SOC pads its 2M rows to 8*ceil(M/4) (build_site_dev), and the padded count must fit 48
+  const int padded = (site->cone == ACNQP_CONE_SOC ? 8 * ((M + 3) / 4) : M) + (Mg - (site->cone == ACNQP_CONE_SOC ? 2 * M : M));
+  if (padded > 48)
+    return fail(ACNQP_ERR_INVALID, "acnqp_create: " + std::to_string(padded) + " site rows after padding (SOC: 8*ceil(n_infra/4) "
+                                   "+ peak/flat/max rows) > 48, the padded limit");
   if (Mg > 0 && !site->G) return fail(ACNQP_ERR_INVALID, "acnqp_create: G is null");
   if (M > 0 && !site->limits) return fail(ACNQP_ERR_INVALID, "acnqp_create: limits is null");
   for (int j = 0; j < M; ++j)
@@ -631,8 +689,9 @@ int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acn
   // the same or better (configs[4] leg 432 vs 434-438 ms, 54 x 144 x 2,048 237-243 vs 247-248 ms; gpurun_out/r4c):
   // they keep one workgroup per problem.
   // the wave-per-problem kernel's variant for this shape (0: another kernel family; acn_qp_wave.hip)
-  const int wv = acnqp::wave_shape(h->N, p->t_max, p->k_sessions, d->MR, h->has_max, p->batch);
-  const bool on_chip = wv > 0 || tiled_shape(h, p->t_max, p->k_sessions) || (long_shape(h, p->t_max, p->k_sessions) && lds_long_shape(h, p->t_max));
+  const Route rt = route_for(h, p->t_max, p->k_sessions, p->batch);
+  const int wv = rt.wv;
+  const bool on_chip = rt.on_chip;
   const bool no_queue = no_queue_env || !(on_chip || queue_all);
   // (the order by sessions only for separable objectives: with a load-flattening or demand-charge row the coupling, not
   //  the number of sessions, sets the iteration count -- on the configs[4] leg it was 10 % SLOWER than the natural one)
@@ -661,9 +720,7 @@ int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acn
   static const bool ws_per_problem = std::getenv("ACNQP_WS_PER_PROBLEM") != nullptr;   // diagnostic
   a.ws_by_slot = a.queue && !ws_per_problem ? 1 : 0;
   a.grid_cap = a.ws_by_slot ? std::min(p->batch, 2 * h->cus) : p->batch;
-  const bool tiled = wv > 0 || tiled_shape(h, p->t_max, p->k_sessions);   // (no workspace: state on chip)
-  const bool stream = !tiled && stream_shape(h, p->t_max);
-  const bool lng = !tiled && long_shape(h, p->t_max, p->k_sessions);
+  const bool tiled = rt.tiled, stream = rt.stream, lng = rt.lng;
   acnqp::GeneralArgs ga;
   acnqp::StreamArgs sa;
   if (stream) {
@@ -703,7 +760,7 @@ int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acn
     if (wv > 0) return acnqp::launch_wave(aa, st);
     if (tiled) return p->t_max <= 16 ? acnqp::launch_tiled_ct1(aa, st) : acnqp::launch_tiled_ct2(aa, st);
     if (stream) { sa.t = aa; return acnqp::launch_stream(sa, st); }
-    if (lng) { sa.t = aa; return acnqp::launch_long(sa, st, lds_long_shape(h, p->t_max)); }
+    if (lng) { sa.t = aa; return acnqp::launch_long(sa, st, rt.lds); }
     // workgroup size by problem size: the plain loops are latency-bound, more threads per problem hide more of it
     const long long nvar = (long long)h->N * p->t_max;
     const int nt = nvar <= 4096 ? 256 : (nvar <= 12288 ? 512 : 1024);
@@ -714,25 +771,9 @@ int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acn
   // solver kernel (pass 0 up to polish_iters iterations; what has not converged by then is listed) -> polish kernel over
   // the list -> solver kernel again over the list for what the polish gave up on (from scratch, with the retry passes:
   // the answer it had before there was a polish).  Three launches on the stream, the last two nearly empty as a rule.
+  // (route_for: the shape's part of the decision; here the options' part)
   const int nrow_site = h->M + h->has_peak;
-  int pol_blk = -1;   // LDS doubles for the blocks of the polish's system; -1: no polish for this launch
-  static const bool no_polish = std::getenv("ACNQP_NO_POLISH") != nullptr;   // diagnostic
-  if (!no_polish && o->polish_iters > 0 && o->polish_iters < o->max_iter && on_chip && h->N <= 64 && p->t_max <= 32 &&
-      p->k_sessions <= acnqp::kMaxK && !h->has_flat && !h->has_max && !a.warm_x && nrow_site > 0) {
-    // LDS of a polish workgroup: where the solver kernel runs two workgroups per CU (the headline shape: one column tile,
-    // one row tile, one session slot: 77 KB each) the polish takes no more than one of those slots, so that it starts as
-    // soon as ANY solver workgroup of a neighbouring stream's launch ends; elsewhere the whole CU
-    const bool two_per_cu = tiled && p->t_max <= 16 && d->MR == 16 && p->k_sessions == 1;
-    pol_blk = acnqp::polish_blocks_that_fit(h->N, p->t_max, h->Mg, nrow_site, acnqp::polish_max_sess(h->N, p->k_sessions),
-                                            two_per_cu ? 76 * 1024 : 160 * 1024);
-    if (pol_blk < 2 * nrow_site * (2 * nrow_site + 1) / 2) pol_blk = -1;   // not even one full block
-    // The polish is a remedy for a launch's TAIL, and its phase runs behind the solver launch.  A launch of many problems
-    // per resident slot of a one-workgroup-per-CU shape is throughput-bound -- its stragglers overlap the bulk of the work
-    // -- so the polish phase (horizon-24 rounds: 0.1 ms each, up to 30 of them) only adds to it: jpl52 x 24 x 4,096
-    // 61.0 -> 67.8 ms with it.  Such launches keep the ADMM alone (ACNQP_POLISH_ALWAYS=1: diagnostic).
-    static const bool polish_always = std::getenv("ACNQP_POLISH_ALWAYS") != nullptr;
-    if (!two_per_cu && p->batch > 8 * h->cus && !polish_always) pol_blk = -1;
-  }
+  const int pol_blk = (o->polish_iters > 0 && o->polish_iters < o->max_iter && !a.warm_x) ? rt.pol_blk : -1;
   hipError_t e = hipSuccess;
   if (pol_blk >= 0) {
     // [0] queue of the polish kernel, [1] queue of the resume launch, [2] list length; list[B]; multipliers [B][Mg][Tm]

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define ACNQP_ABI_VERSION 9
+#define ACNQP_ABI_VERSION 10
 
 /* cone of the infrastructure rows (constraint_type at aco.py:35, 151, 165) */
 #define ACNQP_CONE_LINEAR 0
@@ -67,6 +67,19 @@ extern "C" {
 #define ACNQP_ERR_HIP (-2)         /* HIP runtime failure              */
 #define ACNQP_ERR_NO_DEVICE (-3)
 
+/* kernel families (acnqp_route): which kernel serves a launch is a function of the site and the padded shape */
+#define ACNQP_ROUTE_WAVE1 1        /* wave per problem: one row tile, horizon <= 12, one wave             */
+#define ACNQP_ROUTE_WAVE2 2        /* ... one row tile, horizon 13-24, two waves                          */
+#define ACNQP_ROUTE_WAVE3 3        /* ... two row tiles, horizon <= 12, two waves of six periods           */
+#define ACNQP_ROUTE_WAVE4 4        /* ... two row tiles, horizon 13-24, four waves of six periods          */
+#define ACNQP_ROUTE_WAVE5 5        /* ... one row tile, horizon 33-48, four waves                          */
+#define ACNQP_ROUTE_TILED_CT1 6    /* register-resident tiled kernel, one column tile (horizon <= 16)      */
+#define ACNQP_ROUTE_TILED_CT2 7    /* ... two column tiles (horizon 17-32)                                 */
+#define ACNQP_ROUTE_LONG_LDS 8     /* long-horizon MFMA kernel, site-row state in LDS                      */
+#define ACNQP_ROUTE_LONG_WS 9      /* long-horizon MFMA kernel, state in a workspace                       */
+#define ACNQP_ROUTE_STREAM 10      /* large-site MFMA kernel (N > 64, horizon <= 48)                       */
+#define ACNQP_ROUTE_GENERAL 11     /* general-shape kernel                                                 */
+
 typedef struct acnqp_handle acnqp_handle; /* opaque; one per (site, GPU) */
 
 /* Site data shared by every problem of a batch: what InfrastructureInfo
@@ -79,7 +92,10 @@ typedef struct acnqp_handle acnqp_handle; /* opaque; one per (site, GPU) */
 typedef struct {
   int32_t n_evse;        /* N                                   */
   int32_t n_infra;       /* M: rows of constraint_matrix         */
-  int32_t n_rows;        /* rows of G = M or 2M, + has_flat + has_max + has_peak */
+  int32_t n_rows;        /* rows of G = M or 2M, + has_flat + has_max + has_peak; at most 48 AFTER the
+                            kernels' padding: SOC pads its 2M rows to 8*ceil(M/4), so a SOC site
+                            needs 8*ceil(M/4) + has_flat + has_max + has_peak <= 48 (M <= 20 with a
+                            peak, flat or max row, M <= 24 without); LINEAR: n_rows <= 48        */
   int32_t cone;          /* ACNQP_CONE_*                         */
   int32_t has_peak;      /* 0 / 1                                */
   int32_t has_flat;      /* 0 / 1: aggregate-power row for load_flattening */
@@ -327,6 +343,12 @@ int acnqp_polish_stats(acnqp_handle* h, int64_t* out, int32_t capacity);
  * test/bench plumbing so that a CPU restatement can run the same algorithm.  */
 int32_t acnqp_accel_columns(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t precision,
                             int32_t requested);
+
+/* ABI v10: the kernel family (ACNQP_ROUTE_*) a launch of `batch` problems of this padded shape (t_max periods,
+ * k_sessions slots) runs on this handle's site, and in *polish (may be NULL) 1 if that launch runs the polish phase
+ * under acnqp_default_options, else 0.  The library's own routing rule, read only: no device work.  Returns 0 for
+ * a null handle or a shape acnqp_solve_batch refuses.  Test plumbing: lets a test assert which kernel it exercises. */
+int32_t acnqp_route(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t batch, int32_t* polish);
 
 #ifdef __cplusplus
 }

@@ -190,3 +190,52 @@ def prox_case(g, name):
         o += L
     exp = dict(rates=g[f"{name}_rates"], obj=float(g[f"{name}_obj"]), binding=int(g[f"{name}_binding"][0]))
     return sessions, infra, iface, obj, spec, meta, exp
+
+
+EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "edges.npz")
+
+
+def load_edges():
+    """tools/make_golden_edges.py: certified optima at the shape edges of every kernel route."""
+    return np.load(EDGES, allow_pickle=False)
+
+
+def edges_case(g, name):
+    """Rebuild fixture ``name`` of edges.npz: (sessions, infrastructure, interface, objective list, meta dict,
+    peak_limit, expected dict).  The site is stored with the case (constraint matrix, limits, phases; 208 V, 32 A)."""
+    from adacharge_amd import ObjectiveComponent, demand_charge, equal_share, load_flattening, quick_charge, total_energy
+    from adacharge_amd.acn import InfrastructureInfo
+
+    cm = g[f"{name}_cm"]
+    n = cm.shape[1]
+    infra = InfrastructureInfo(cm, g[f"{name}_limits"], g[f"{name}_phases"], np.full(n, 208.0),
+                               constraint_ids=[f"c{j}" for j in range(cm.shape[0])], station_ids=[f"E-{i:04d}" for i in range(n)],
+                               max_pilot=np.full(n, 32.0), min_pilot=np.full(n, 8.0),
+                               allowable_pilots=[np.r_[0.0, np.arange(8.0, 33.0)] for _ in range(n)],
+                               is_continuous=np.zeros(n, dtype=bool))
+    kind = str(g[f"{name}_objective"])
+    if kind == "lf":
+        obj = [ObjectiveComponent(load_flattening, 1.0, {"external_signal": g[f"{name}_ext"].copy()}), ObjectiveComponent(equal_share, 1e-3)]
+        iface = Interface({"infrastructure_info": infra, "period": 5})
+    elif kind == "dc":
+        obj = [ObjectiveComponent(total_energy, 20.0), ObjectiveComponent(demand_charge), ObjectiveComponent(equal_share, 1e-3)]
+        iface = Interface({"infrastructure_info": infra, "period": 5, "demand_charge": 15.0, "prev_peak": 50.0})
+    else:
+        obj = [ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-3)]
+        iface = Interface({"infrastructure_info": infra, "period": 5})
+    st, arr, dep = g[f"{name}_station"], g[f"{name}_arrival"], g[f"{name}_departure"]
+    minr, maxr = g[f"{name}_minr"], g[f"{name}_maxr"]
+    sessions, o = [], 0
+    for k in range(len(st)):
+        L = int(dep[k] - arr[k])
+        sessions.append(SessionInfo(infra.station_ids[int(st[k])], f"s{k}", float(g[f"{name}_demand"][k]), 0.0,
+                                    int(arr[k]), int(dep[k]), current_time=0,
+                                    min_rates=minr[o:o + L].copy(), max_rates=maxr[o:o + L].copy()))
+        o += L
+    m = g[f"{name}_meta"]
+    meta = dict(T=int(m[0]), ct="SOC" if m[1] else "LINEAR", eq=bool(m[2]), seed=int(m[3]), objective=kind,
+                family=str(g[f"{name}_family"]), how=str(g[f"{name}_how"]))
+    pk = g[f"{name}_peak"]
+    peak = None if np.isnan(pk[0]) else (float(pk[0]) if len(pk) == 1 else pk.copy())
+    exp = dict(rates=g[f"{name}_rates"], obj=float(g[f"{name}_obj"]), cert=g[f"{name}_cert"])
+    return sessions, infra, iface, obj, meta, peak, exp

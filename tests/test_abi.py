@@ -25,8 +25,8 @@ def test_header_symbols_all_exported(hip_library):
         assert hasattr(hip_library, s), s
 
 
-def test_abi_version_and_defaults(hip_library):
-    assert hip_library.acnqp_abi_version() == 9
+def test_abi_v10_version_and_defaults(hip_library):
+    assert hip_library.acnqp_abi_version() == 10   # ABI v10: acnqp_route
     o = backend.default_options()
     assert o.precision == 64 and 0 < o.alpha < 2 and o.max_iter > 0 and o.eps_abs > 0
     # ABI v7: stall rule and retry passes are options of the library (every entry point), not of the binding
@@ -63,9 +63,18 @@ def test_create_rejects_bad_arguments(hip_library):
     assert hip_library.acnqp_create(C.byref(desc), 0, C.byref(h)) == -1   # n_rows inconsistent
     desc = backend._Site(4, 1, 1, 7, 0, 0, 0, G.ctypes.data_as(C.c_void_p), lim.ctypes.data_as(C.c_void_p))
     assert hip_library.acnqp_create(C.byref(desc), 0, C.byref(h)) == -1   # bad cone
+    # SOC, 21 infrastructure rows + a peak row: n_rows = 43 <= 48, but the SOC rows pad to 8 * ceil(21 / 4) = 48, + 1
+    G = np.ones((43, 4))
+    lim = np.ones(21)
+    desc = backend._Site(4, 21, 43, 1, 1, 0, 0, G.ctypes.data_as(C.c_void_p), lim.ctypes.data_as(C.c_void_p))
+    assert hip_library.acnqp_create(C.byref(desc), 0, C.byref(h)) == -1
+    assert b"49 site rows after padding" in hip_library.acnqp_last_error() and b"padded limit" in hip_library.acnqp_last_error()
     assert hip_library.acnqp_solve_batch(None, None, None, None) == -1
     assert hip_library.acnqp_last_kernel_ms(None) < 0
     assert hip_library.acnqp_accel_columns(None, 12, 1, 64, 10) == 0
+    pol = C.c_int32(7)
+    assert hip_library.acnqp_route(None, 12, 1, 1, C.byref(pol)) == 0 and pol.value == 0   # ABI v10: no handle, no route
+    assert hip_library.acnqp_route(None, 12, 1, 1, None) == 0
     assert hip_library.acnqp_kernel_times(None, None, 0) == 0
     assert hip_library.acnqp_launch_count(None) == 0
     hip_library.acnqp_destroy(None)   # no-op
@@ -88,3 +97,37 @@ def test_product_never_imports_oracle():
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), f
                 assert "oracle/" not in src or f.endswith((".hpp", ".py")) and "import" not in src.split("oracle/")[0][-20:]
+
+
+@pytest.mark.gpu
+def test_soc_row_limit_is_the_padded_one():
+    """acnqp_create counts SOC rows as the kernels pad them (8 ceil(M / 4)): 21 rows + a peak (n_rows 43, 49 padded) is
+    refused with a message naming the padded limit; 20 rows + a peak (n_rows 41, 41 padded, MR 48) is the largest such
+    site, and it solves a small batch within the site rows."""
+    from adacharge_amd import ObjectiveComponent, equal_share, quick_charge, sites
+    from adacharge_amd.acn import Interface
+    from adacharge_amd.backend import SiteHandle, default_options
+    from adacharge_amd.builder import build_batch, make_site
+
+    for pods, ok in ((15, False), (14, True)):   # M = pods + 6
+        infra = sites.balanced_three_phase(60, pods=pods, load_fraction=0.35)
+        assert infra.constraint_matrix.shape[0] == pods + 6
+        site = make_site(infra, "SOC", with_peak=True)
+        assert site.Mg == 2 * (pods + 6) + 1
+        if not ok:
+            with pytest.raises(ValueError, match="49 site rows after padding.*padded limit"):
+                SiteHandle(site, 0)
+            continue
+        iface = Interface({"infrastructure_info": infra, "period": 5})
+        snaps = sites.snapshot_batch(infra, 12, 8, seed=41)
+        batch = build_batch(snaps, infra, iface, [ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-3)],
+                            "SOC", peak_limits=[300.0] * 8, site=site)
+        h = SiteHandle(site, 0)
+        res = h.solve(batch, default_options())
+        h.close()
+        assert (res.status == 1).all(), res.status
+        ph = np.deg2rad(infra.phases)
+        cm = infra.constraint_matrix
+        mag = np.hypot(np.einsum("mn,bnt->bmt", cm * np.cos(ph), res.x), np.einsum("mn,bnt->bmt", cm * np.sin(ph), res.x))
+        assert (mag <= infra.constraint_limits[None, :, None] + 1e-3).all()
+        assert (res.x.sum(axis=1) <= 300.0 + 1e-3).all()
