@@ -434,16 +434,21 @@ class SiteHandle:
         res.kernel_ms = self._kernel_ms_of_call()
         return self._finish(plan, res)
 
-    def solve_many(self, batches, options: Optional[Options] = None, pinned_results: bool = True):
+    def solve_many(self, batches, options: Optional[Options] = None, pinned_results: bool = True, want_y=None, warm=None):
         """acnqp_solve_batches: several independent batches in ONE pipelined pass (shared launches, overlapped
-        copies).  Returns one BatchResult per batch."""
+        copies).  Returns one BatchResult per batch.  ``want_y[g]`` / ``warm[g]``: optional per-batch multiplier output
+        and warm start, as ``solve`` takes them (None = no batch wants / has one)."""
         o = options if options is not None else default_options()
         n = len(batches)
+        want_y = [False] * n if want_y is None else list(want_y)
+        warm = [None] * n if warm is None else list(warm)
+        if len(want_y) != n or len(warm) != n:
+            raise ValueError("want_y and warm need one entry per batch")
         P, R = (_Problems * n)(), (_Results * n)()
         results, keep = [], []
         for g, batch in enumerate(batches):
             self._check_site(batch)
-            P[g], R[g], res, k = self._marshal(batch, pinned_results)
+            P[g], R[g], res, k = self._marshal(batch, pinned_results, warm=warm[g], want_y=bool(want_y[g]))
             results.append(res)
             keep.append(k)
         _check(self._lib.acnqp_solve_batches(self._h, n, P, C.byref(o), R), "acnqp_solve_batches")
@@ -484,7 +489,8 @@ class SiteHandle:
             None, None,
         )
         r = _Results(dev.x.data_ptr(), dev.status.data_ptr(), dev.iters.data_ptr(),
-                     dev.pri_res.data_ptr(), dev.dua_res.data_ptr(), dev.obj.data_ptr(), None, None)
+                     dev.pri_res.data_ptr(), dev.dua_res.data_ptr(), dev.obj.data_ptr(),
+                     None if dev.y is None else dev.y.data_ptr(), None)
         _check(
             self._lib.acnqp_solve_batch_device(self._h, C.byref(p), C.byref(o), C.byref(r), C.c_void_p(stream)),
             "acnqp_solve_batch_device",
@@ -543,7 +549,7 @@ class DeviceBatch:
     """A ProblemBatch resident in HBM (torch tensors on one GPU) plus result
     tensors; torch is used for device memory only."""
 
-    def __init__(self, batch: ProblemBatch, device):
+    def __init__(self, batch: ProblemBatch, device, want_y: bool = False):
         import torch
 
         dev = torch.device(device)
@@ -568,3 +574,5 @@ class DeviceBatch:
         self.pri_res = torch.zeros(self.B, dtype=torch.float64, device=dev)
         self.dua_res = torch.zeros(self.B, dtype=torch.float64, device=dev)
         self.obj = torch.zeros(self.B, dtype=torch.float64, device=dev)
+        # site-row multipliers (B, Mg, Tm) when wanted (acnqp_results.y), else None
+        self.y = torch.zeros((self.B, batch.site.Mg, self.Tm), dtype=torch.float64, device=dev) if want_y else None

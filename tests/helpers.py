@@ -239,3 +239,66 @@ def edges_case(g, name):
     peak = None if np.isnan(pk[0]) else (float(pk[0]) if len(pk) == 1 else pk.copy())
     exp = dict(rates=g[f"{name}_rates"], obj=float(g[f"{name}_obj"]), cert=g[f"{name}_cert"])
     return sessions, infra, iface, obj, meta, peak, exp
+
+
+# ---- padding and certificate pools (oracle/kkt.py; tests/test_kkt_certificate.py, tests/test_route_certificate.py) ----
+def pad_batch(batch, t_max, k_sessions):
+    """``batch`` padded to ``t_max`` periods and ``k_sessions`` session slots: the same problems (include/acn_qp.h: periods
+    t >= horizon[b] are dead -- lb = ub = q = 0, peak = +inf -- and an empty slot has s_len = 0), another padded shape and
+    so possibly another kernel family (acnqp_route decides on (t_max, k_sessions), never on horizon[b])."""
+    import copy
+
+    assert t_max >= batch.Tm and k_sessions >= batch.K
+    B, N, Tm, K = batch.B, batch.N, batch.Tm, batch.K
+
+    def grow(a, shape, fill=0):
+        out = np.full(shape, fill, dtype=a.dtype)
+        out[tuple(slice(0, s) for s in a.shape)] = a
+        return out
+
+    out = copy.copy(batch)
+    out.Tm, out.K = int(t_max), int(k_sessions)
+    out.lb, out.ub, out.q = (grow(a, (B, N, t_max)) for a in (batch.lb, batch.ub, batch.q))
+    out.s_off, out.s_len, out.s_cap = (grow(a, (B, k_sessions, N)) for a in (batch.s_off, batch.s_len, batch.s_cap))
+    out.peak = None if batch.peak is None else grow(batch.peak, (B, t_max), np.inf)
+    return out
+
+
+def pad_result(a, t_max):
+    """(B, R, Tm) result array padded with zeros to t_max periods (what the library writes at dead periods)"""
+    out = np.zeros(a.shape[:-1] + (t_max,), dtype=a.dtype)
+    out[..., : a.shape[-1]] = a
+    return out
+
+
+def certificate_pool(site_name, cone, T, n, seed, eq=False, two=True, peak=None):
+    """``n`` snapshots of ``site_name`` (sites.random_sessions_general: delayed arrivals, two sessions on 40 % of the
+    EVSEs when ``two``), horizons T, T - 2 and T - 4 mixed in one batch; ``peak``: None (no peak row), "scalar",
+    "vector" or "mixed" (scalar, vector and unlimited snapshots in one batch)."""
+    from adacharge_amd import ObjectiveComponent, equal_share, quick_charge, total_energy
+    from adacharge_amd.builder import build_batch
+
+    infra = getattr(sites, site_name)()
+    iface = Interface({"infrastructure_info": infra, "period": 5})
+    rng = np.random.default_rng(seed)
+    obj = [ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-3), ObjectiveComponent(total_energy, 0.5)]
+    snaps, peaks = [], []
+    for k in range(n):
+        Tb = T - 2 * (k % 3)
+        snaps.append(sites.random_sessions_general(infra, Tb, rng, two_per_evse=two, min_rates=not eq,
+                                                   demand_scale=0.5 if eq else 1.5))
+        kind = peak if peak != "mixed" else ("scalar", "vector", None)[k % 3]
+        Tk = max(s.arrival_offset + s.remaining_time for s in snaps[-1])
+        peaks.append(None if kind is None else float(rng.uniform(250, 600)) if kind == "scalar"
+                     else rng.uniform(250, 600, size=Tk))
+    return build_batch(snaps, infra, iface, obj, cone, eq, peak_limits=peaks if peak else None)
+
+
+def edges_pool(name, n, seed=0):
+    """``n`` demand scenarios (factors U(0.85, 1) per session) of edges.npz case ``name``: its site, horizon and slots."""
+    from adacharge_amd.builder import build_batch, scenario_batch
+
+    sl, infra, iface, obj, meta, peak, exp = edges_case(load_edges(), name)
+    base = build_batch([sl], infra, iface, obj, meta["ct"], meta["eq"], peak_limits=[peak])
+    rng = np.random.default_rng(seed)
+    return scenario_batch(base, rng.uniform(0.85, 1.0, size=(n, base.K, base.N)))
