@@ -241,6 +241,9 @@ class AdaptiveChargingOptimization:
         self.last_result = None
         self._last_plan = None
         self._last_batch = None
+        self._last_handle = None
+        self._last_options = None
+        self._last_duals = None
 
     # the single-problem API asks for tighter residuals than the batch default so that the
     # reference's own test tolerances (1e-7 on the peak row, t_aco.py:257) hold
@@ -389,6 +392,7 @@ class AdaptiveChargingOptimization:
         if not bool(opts.pop("retry_stalled", True)):   # shorthand kept from round 2: the passes live in the library now
             opts["retry_passes"] = 0
         self._last_plan, self._last_batch = plan, None
+        self._last_handle, self._last_options, self._last_duals = handle, backend.default_options(**opts), None
         if warm_start is not None and any(w is not None for w in warm_start):
             # per problem (x0, y0) or None; a problem without one starts from its own cold start's point only if all
             # are None -- mixed batches give the cold problems x0 = y0 = 0 (a valid, if plain, starting point)
@@ -412,6 +416,58 @@ class AdaptiveChargingOptimization:
         if getattr(self, "_last_batch", None) is None and getattr(self, "_last_plan", None) is not None:
             self._last_batch = self._last_plan.expand()
         return getattr(self, "_last_batch", None)
+
+    @property
+    def last_duals(self):
+        """``backend.DualResult`` of the last solve: the multipliers of the energy rows (``mu``) and of the rate bounds
+        (``z``) and the KKT residuals of every problem of ``last_result``, computed on the GPU from ``last_result`` and
+        ``last_batch`` on first access (no solve pays for it), then cached.  Units of the C ABI (include/acn_qp.h); they
+        are the duals of the problem the kernels solve, the Tikhonov floor ``reg_rel`` of LP-like problems included."""
+        if getattr(self, "_last_duals", None) is None and self.last_result is not None and getattr(self, "_last_handle", None) is not None:
+            self._last_duals = self._last_handle.duals(self.last_batch, self.last_result, self._last_options)
+        return getattr(self, "_last_duals", None)
+
+    def dual_values(self, active_sessions, infrastructure, b: int = 0):
+        """Dual values of problem ``b`` of the last solve, keyed exactly like the constraints dict the reference's
+        ``build_problem`` returns (aco.py:245-276), in the reference's units (rates in A, energy in kWh):
+
+          * ``charging_rate_bounds.lb`` / ``.ub``: (N, T) arrays ``max(-z, 0)`` / ``max(z, 0)``;
+          * ``energy_constraints.<session_id>``: ``mu / k_i`` with ``k_i = voltage_i * period / 1e3 / 60`` (per kWh,
+            aco.py:114);
+          * ``infrastructure_constraints.<id>``: (T,) array, ``y_j`` (LINEAR) or ``|(y_j, y_{j+M})|`` (SOC);
+          * ``peak_constraint``: (T,) array, the peak row of ``y`` (only when the solve had a peak limit).
+
+        Sign convention: with ``f`` the MINIMISED objective (the negative of the reference's maximised one), rates ``r``
+        and ``nu`` the value reported for a session, the Lagrangian is ``L = f + nu (k sum r - demand) + ...``.  Every
+        value is non-negative except an equality energy row's, whose sign follows that Lagrangian.  cvxpy is not a
+        dependency of this package, so the sign and scaling conventions of its ``constraint.dual_value`` have not been
+        compared with these; the Lagrangian above is what is guaranteed.  The values are the duals of the problem the
+        kernels solve (for LP-like objectives that includes the Tikhonov floor ``reg_rel``)."""
+        d, res, batch = self.last_duals, self.last_result, self.last_batch
+        if d is None:
+            raise RuntimeError("dual_values: no solve yet")
+        from . import backend
+
+        if int(res.status[b]) not in backend.ACCEPTED_STATUSES:
+            raise InfeasibilityException(f"problem {b} ended with status {backend.STATUS_NAMES.get(int(res.status[b]), res.status[b])}: no dual values")
+        site = batch.site
+        T, M = int(batch.T[b]), site.M
+        z, y = d.z[b][:, :T], res.y[b][:, :T]
+        out = {"charging_rate_bounds.lb": np.maximum(-z, 0.0), "charging_rate_bounds.ub": np.maximum(z, 0.0)}
+        for session in active_sessions:
+            i = infrastructure.get_station_index(session.station_id)
+            slot = np.flatnonzero((batch.s_len[b, :, i] > 0) & (batch.s_off[b, :, i] == session.arrival_offset))
+            if session.remaining_time <= 0 or slot.size == 0:
+                out[f"energy_constraints.{session.session_id}"] = 0.0
+                continue
+            k_i = infrastructure.voltages[i] * self.interface.period / 1e3 / 60
+            out[f"energy_constraints.{session.session_id}"] = float(d.mu[b, slot[0], i]) / k_i
+        for j in range(M):
+            val = np.hypot(y[j], y[j + M]) if site.cone == 1 else y[j].copy()
+            out[f"infrastructure_constraints.{infrastructure.constraint_ids[j]}"] = val
+        if site.has_peak and np.isfinite(batch.peak[b][:T]).any():
+            out["peak_constraint"] = y[site.Mg - 1].copy()
+        return out
 
     @property
     def last_multipliers(self):

@@ -98,6 +98,12 @@ class _Results(C.Structure):
     ]
 
 
+class _Duals(C.Structure):
+    """Mirror of ``acnqp_duals`` (include/acn_qp.h)."""
+
+    _fields_ = [("mu", C.c_void_p), ("z", C.c_void_p), ("res", C.c_void_p)]
+
+
 class Options(C.Structure):
     """Mirror of ``acnqp_options``; construct with ``default_options()``."""
 
@@ -144,6 +150,8 @@ EXPORTED_SYMBOLS = (
     "acnqp_host_free",
     "acnqp_launch_count",
     "acnqp_route",
+    "acnqp_duals_device",
+    "acnqp_duals_host",
 )
 
 # kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
@@ -217,6 +225,12 @@ def load_library():
     lib.acnqp_polish_stats.restype = C.c_int
     lib.acnqp_route.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
     lib.acnqp_route.restype = C.c_int32
+    lib.acnqp_duals_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(_Duals), C.c_void_p]
+    lib.acnqp_duals_device.restype = C.c_int
+    lib.acnqp_duals_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(_Duals)]
+    lib.acnqp_duals_host.restype = C.c_int
     _lib = lib
     return lib
 
@@ -256,6 +270,18 @@ class BatchResult:
     kernel_ms: float = float("nan")   # sum of the HIP-event durations of the call's launches (chunks of the pipelined
                                       # entry overlap on the GPU: an upper bound of the time the GPU was busy)
     y: Optional[np.ndarray] = None   # (B, Mg, Tm) multipliers of the site rows (when asked for): warm_y of a later solve
+
+
+@dataclass
+class DualResult:
+    """The dual report of a batch of answers (acnqp_duals_host / acnqp_duals_device, include/acn_qp.h), in the units of the
+    C ABI (minimisation form, energy rows in A-periods)."""
+    mu: np.ndarray       # (B, K, N) multiplier of each session's energy row (layout of s_cap; 0 for an empty slot)
+    z: Optional[np.ndarray]   # (B, N, Tm) multipliers of the rate bounds: > 0 of ub, < 0 of lb (None: not asked for)
+    stat: np.ndarray     # (B,) natural residual |x - clip(v - mu)|_inf
+    energy: np.ndarray   # (B,) worst energy-row violation / max(1, |cap|)
+    site: np.ndarray     # (B,) worst site-row violation / max(1, limit)
+    comp: np.ndarray     # (B,) worst multiplier x slack over the site rows (oracle-free KKT check, scaled as documented)
 
 
 class _PinnedBlock:
@@ -494,6 +520,54 @@ class SiteHandle:
         _check(
             self._lib.acnqp_solve_batch_device(self._h, C.byref(p), C.byref(o), C.byref(r), C.c_void_p(stream)),
             "acnqp_solve_batch_device",
+        )
+
+    # -- dual report (acn_qp_duals.hpp) -------------------------------------------------------------------------------
+    def duals(self, batch: ProblemBatch, res: "BatchResult", options: Optional[Options] = None, want_z: bool = True) -> DualResult:
+        """acnqp_duals_host: the multipliers of the energy rows and rate bounds of the answers ``res`` (a BatchResult with
+        ``y``, i.e. solved with ``want_y=True``) to ``batch``, and their KKT residuals, computed on the GPU.  ``options``:
+        the options of the solve (``reg_rel`` is read)."""
+        self._check_site(batch)
+        B, N, Tm, K = batch.B, batch.N, batch.Tm, batch.K
+        if self.site.Mg > 0 and res.y is None:
+            raise ValueError("duals need the site-row multipliers: solve with want_y=True")
+        o = options if options is not None else default_options()
+        p, _, _, keep = self._marshal(batch, False)
+        x = np.ascontiguousarray(res.x, np.float64)
+        y = None if res.y is None else np.ascontiguousarray(res.y, np.float64)
+        st = np.ascontiguousarray(res.status, np.int32)
+        if x.shape != (B, N, Tm) or st.shape != (B,) or (y is not None and y.shape != (B, self.site.Mg, Tm)):
+            raise ValueError("result arrays do not match the batch")
+        mu, z, r = np.zeros((B, K, N)), (np.zeros((B, N, Tm)) if want_z else None), np.zeros((B, 4))
+        d = _Duals(_ptr(mu), _ptr(z), _ptr(r))
+        _check(self._lib.acnqp_duals_host(self._h, C.byref(p), C.byref(o), _ptr(x), _ptr(y), _ptr(st), C.byref(d)), "acnqp_duals_host")
+        del keep
+        return DualResult(mu, z, r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy())
+
+    def duals_device(self, dev: "DeviceBatch", mu, res, z=None, options: Optional[Options] = None, stream: int = 0,
+                     use_status: bool = True) -> None:
+        """acnqp_duals_device: the same for a ``DeviceBatch`` after ``solve_device`` (it needs ``want_y=True`` on a site with
+        rows); ``mu`` (B, K, N), ``res`` (B, 4) and the optional ``z`` (B, N, Tm) are float64 device tensors that receive the
+        report.  Asynchronous on ``stream``."""
+        o = options if options is not None else default_options()
+        if self.site.Mg > 0 and dev.y is None:
+            raise ValueError("duals need the site-row multipliers: DeviceBatch(..., want_y=True)")
+        p = _Problems(
+            dev.B, dev.Tm, dev.K,
+            dev.horizon.data_ptr(), dev.lb.data_ptr(), dev.ub.data_ptr(), dev.q.data_ptr(), dev.pdiag.data_ptr(),
+            dev.s_off.data_ptr(), dev.s_len.data_ptr(), dev.s_cap.data_ptr(), dev.s_eq.data_ptr(),
+            None if dev.peak is None else dev.peak.data_ptr(),
+            dev.lf.data_ptr() if self.site.has_flat else None,
+            dev.dc.data_ptr() if self.site.has_max else None,
+            dev.dfloor.data_ptr() if self.site.has_max else None,
+            None, None,
+        )
+        d = _Duals(mu.data_ptr(), None if z is None else z.data_ptr(), res.data_ptr())
+        _check(
+            self._lib.acnqp_duals_device(self._h, C.byref(p), C.byref(o), C.c_void_p(dev.x.data_ptr()),
+                                         None if dev.y is None else C.c_void_p(dev.y.data_ptr()),
+                                         C.c_void_p(dev.status.data_ptr()) if use_status else None, C.byref(d), C.c_void_p(stream)),
+            "acnqp_duals_device",
         )
 
     def _kernel_ms_of_call(self) -> float:

@@ -14,6 +14,7 @@
 
 #include "acn_qp.h"
 #include "acn_qp_launch.hpp"
+#include "acn_qp_duals.hpp"
 
 namespace {
 
@@ -159,7 +160,7 @@ struct acnqp_handle {
   // per launch stream: the kernel workspace (long-horizon, large-site, general-shape kernels) and the launch's small
   // scheduling buffer (queue counter, then sort keys and queue order).  Launches on different streams never share (or
   // regrow) each other's state, and a stream's own launches are ordered by the stream.
-  struct Work { hipStream_t st; DevBuf buf; DevBuf ord; DevBuf pol; long long used; hipEvent_t last; };   // pol: the polish's list and multiplier buffer
+  struct Work { hipStream_t st; DevBuf buf; DevBuf ord; DevBuf pol; long long used; hipEvent_t last; DevBuf dua; };   // pol: the polish's list and multiplier buffer; dua: g of a dual report without z
   std::vector<Work> work;
   long long work_clock = 0;
   // streams of the CALLER (acnqp_solve_batch_device) beyond the handle's own kSlots: a caller that round-robins one
@@ -195,6 +196,7 @@ struct acnqp_handle {
         work[lru].buf.release();
         work[lru].ord.release();
         work[lru].pol.release();
+        work[lru].dua.release();
         work.erase(work.begin() + (long)lru);
       }
     }
@@ -209,11 +211,13 @@ struct acnqp_handle {
       w.buf.release();
       w.ord.release();
       w.pol.release();
+      w.dua.release();
     }
     work.clear();
   }
   int cus = 0;   // compute units of the device (the work-queue launches size their grid from it)
   int32_t* pol_stats = nullptr;   // device counters of the polish kernel, summed over the handle's life (acnqp_polish_stats)
+  DevBuf duals_stage;   // acnqp_duals_host: device staging of one chunk
 };
 
 namespace {
@@ -596,6 +600,7 @@ void acnqp_destroy(acnqp_handle* h) {
   h->small_out.release();
   for (auto& ev : h->h2d_done) if (ev) (void)hipEventDestroy(ev);
   h->release_work();
+  h->duals_stage.release();
   if (h->pol_stats) (void)hipFree(h->pol_stats);
   delete h;
 }
@@ -1425,6 +1430,106 @@ int acnqp_solve_batches(acnqp_handle* h, int32_t n_batches, const acnqp_problems
 
 int acnqp_solve_batch(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r) {
   return acnqp_solve_batches(h, 1, p, o, r);
+}
+
+// ---- dual report (acn_qp_duals.hpp) ---------------------------------------------------------------------------------
+static int check_duals_args(const acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x,
+                            const double* y, const acnqp_duals* out, const char* who) {
+  const std::string w(who);
+  if (!h || !p || !o || !out) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  if (p->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (p->batch == 0) return ACNQP_OK;
+  if (p->t_max < 1 || p->t_max > 4096) return fail(ACNQP_ERR_INVALID, w + ": t_max must be in [1, 4096]");
+  if (p->k_sessions < 1 || p->k_sessions > 4096) return fail(ACNQP_ERR_INVALID, w + ": k_sessions must be in [1, 4096]");
+  if (!p->horizon || !p->lb || !p->ub || !p->q || !p->pdiag || !p->s_off || !p->s_len || !p->s_cap || !p->s_eq)
+    return fail(ACNQP_ERR_INVALID, w + ": null problem array");
+  if (h->has_peak && !p->peak) return fail(ACNQP_ERR_INVALID, w + ": site has a peak row but peak is null");
+  if (h->has_flat && !p->lf) return fail(ACNQP_ERR_INVALID, w + ": site has a flat row but lf is null");
+  if (h->has_max && !p->dc) return fail(ACNQP_ERR_INVALID, w + ": site has a max row but dc is null");
+  if (!x || (h->Mg > 0 && !y)) return fail(ACNQP_ERR_INVALID, w + ": null x or y");
+  if (!out->mu || !out->res) return fail(ACNQP_ERR_INVALID, w + ": null mu or res");
+  if (!(o->reg_rel >= 0)) return fail(ACNQP_ERR_INVALID, w + ": invalid option value (reg_rel)");
+  return ACNQP_OK;
+}
+
+int acnqp_duals_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y,
+                       const int32_t* status, acnqp_duals* out, void* hip_stream) {
+  int rc = check_duals_args(h, p, o, x, y, out, "acnqp_duals_device");
+  if (rc != ACNQP_OK) return rc;
+  if (p->batch == 0) return ACNQP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const SiteDev* d = &h->dev64;
+  acnqp::DualsArgs a;
+  a.B = p->batch; a.N = h->N; a.Tm = p->t_max; a.K = p->k_sessions; a.M = h->M; a.Mg = h->Mg; a.cone = h->cone;
+  a.has_peak = h->has_peak; a.has_flat = h->has_flat; a.has_max = h->has_max;
+  a.G = d->Gabi; a.limits = d->limabi;
+  a.horizon = p->horizon; a.lb = p->lb; a.ub = p->ub; a.q = p->q; a.pdiag = p->pdiag;
+  a.s_off = p->s_off; a.s_len = p->s_len; a.s_cap = p->s_cap; a.s_eq = p->s_eq;
+  a.peak = h->has_peak ? p->peak : nullptr;
+  a.lf = h->has_flat ? p->lf : nullptr;
+  a.dc = h->has_max ? p->dc : nullptr;
+  a.x = x; a.y = y; a.status = status;
+  a.mu = out->mu; a.z = out->z; a.res = out->res; a.gbuf = out->z;
+  a.reg_rel = o->reg_rel;
+  if (!a.gbuf && !acnqp::duals_wave_shape(h->N, p->t_max)) {   // z not wanted: g goes to a scratch of this stream (the wave form keeps g in LDS)
+    acnqp_handle::Work* wk = h->work_for(st);
+    const size_t need = (size_t)p->batch * h->N * p->t_max * sizeof(double);
+    if (need > wk->dua.cap) HIP_TRY(hipStreamSynchronize(st));   // an earlier report on this stream may still use the old one
+    HIP_TRY(wk->dua.reserve(need));
+    a.gbuf = static_cast<double*>(wk->dua.p);
+  }
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_duals(a, st);
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("duals kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_duals_host(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y,
+                     const int32_t* status, acnqp_duals* out) {
+  int rc = check_duals_args(h, p, o, x, y, out, "acnqp_duals_host");
+  if (rc != ACNQP_OK) return rc;
+  if (p->batch == 0) return ACNQP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = h->slot[0].st;
+  const size_t N = (size_t)h->N, Tm = (size_t)p->t_max, K = (size_t)p->k_sessions, Mg = (size_t)h->Mg;
+  // per-problem bytes of every staged array, in staging order (each array of a chunk starts on a 256-byte line)
+  enum { LB, UB, Q, X, Y, SOFF, SLEN, SCAP, PEAK, HOR, PD, SEQ, LF, DC, STAT, MU, Z, RES, NARR };
+  size_t per[NARR] = {N * Tm * 8, N * Tm * 8, N * Tm * 8, N * Tm * 8, Mg * Tm * 8, K * N * 4, K * N * 4, K * N * 8,
+                      h->has_peak ? Tm * 8 : 0, 4, 8, 1, h->has_flat ? 8u : 0u, h->has_max ? 8u : 0u, status ? 4u : 0u,
+                      K * N * 8, out->z ? N * Tm * 8 : 0, 32};
+  const void* src[NARR] = {p->lb, p->ub, p->q, x, y, p->s_off, p->s_len, p->s_cap, p->peak, p->horizon, p->pdiag, p->s_eq,
+                           p->lf, p->dc, status, nullptr, nullptr, nullptr};
+  size_t total = 0;
+  for (size_t b : per) total += b;
+  const size_t budget = (size_t)256 << 20;   // device staging of one chunk
+  const long long chunk = std::max<long long>(1, std::min<long long>(p->batch, (long long)(budget / std::max<size_t>(total, 1))));
+  size_t offs[NARR], need = 0;
+  for (int k = 0; k < NARR; ++k) { offs[k] = need; need += al256(per[k] * (size_t)chunk); }
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(h->duals_stage.reserve(need));
+  char* base = static_cast<char*>(h->duals_stage.p);
+  auto dev = [&](int k) -> void* { return per[k] ? base + offs[k] : nullptr; };
+  for (long long lo = 0; lo < p->batch; lo += chunk) {
+    const long long nb = std::min<long long>(chunk, p->batch - lo);
+    for (int k = 0; k < MU; ++k)
+      if (per[k]) HIP_TRY(hipMemcpyAsync(dev(k), static_cast<const char*>(src[k]) + per[k] * (size_t)lo, per[k] * (size_t)nb, hipMemcpyHostToDevice, st));
+    acnqp_problems pc = *p;
+    pc.batch = (int32_t)nb;
+    pc.lb = (const double*)dev(LB); pc.ub = (const double*)dev(UB); pc.q = (const double*)dev(Q);
+    pc.s_off = (const int32_t*)dev(SOFF); pc.s_len = (const int32_t*)dev(SLEN); pc.s_cap = (const double*)dev(SCAP);
+    pc.peak = (const double*)dev(PEAK); pc.horizon = (const int32_t*)dev(HOR); pc.pdiag = (const double*)dev(PD);
+    pc.s_eq = (const uint8_t*)dev(SEQ); pc.lf = (const double*)dev(LF); pc.dc = (const double*)dev(DC);
+    pc.warm_x = pc.warm_y = nullptr;
+    acnqp_duals oc{(double*)dev(MU), (double*)dev(Z), (double*)dev(RES)};
+    rc = acnqp_duals_device(h, &pc, o, (const double*)dev(X), (const double*)dev(Y), (const int32_t*)dev(STAT), &oc, st);
+    if (rc != ACNQP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out->mu + (size_t)lo * K * N, dev(MU), per[MU] * (size_t)nb, hipMemcpyDeviceToHost, st));
+    if (out->z) HIP_TRY(hipMemcpyAsync(out->z + (size_t)lo * N * Tm, dev(Z), per[Z] * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out->res + (size_t)lo * 4, dev(RES), per[RES] * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return ACNQP_OK;
 }
 
 void* acnqp_host_alloc(size_t bytes) {

@@ -350,6 +350,46 @@ int32_t acnqp_accel_columns(acnqp_handle* h, int32_t t_max, int32_t k_sessions, 
  * a null handle or a shape acnqp_solve_batch refuses.  Test plumbing: lets a test assert which kernel it exercises. */
 int32_t acnqp_route(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t batch, int32_t* polish);
 
+/* ---- dual report (additive to ABI v10: new symbols only, no existing structure changes) -------------------------------
+ * For any answer (x, y) of the library: the multipliers of the energy rows and of the rate bounds, and the KKT
+ * residuals of the full primal-dual point, computed on the GPU by one kernel that is independent of the solver loop.
+ * With pd_eff the diagonal the kernels use (options.reg_rel: the Tikhonov floor of LP-like problems included -- the
+ * duals are those of the problem the kernels solve), in the minimisation form and the units of this header:
+ *
+ *     g    = pd_eff x + q + G'y                                         [N][Tm]
+ *     v    = x - g
+ *     mu_s = the shift for which sum_{t in window s} clip(v - mu_s, lb, ub) = cap_s  (inequality rows: 0 when
+ *            sum clip(v, lb, ub) <= cap_s, else the shift > 0) -- the multiplier of the session's energy row
+ *     z    = -(g + mu_s) inside a window, 0 outside                     (> 0: multiplier of ub, < 0: of lb)
+ *
+ * Where the admissible shifts form an interval (every entry of the window on a bound) the value of least magnitude is
+ * reported.  res holds four doubles per problem:
+ *   [0] stat    |x - clip(v - mu, lb, ub)|_inf, the natural residual (amperes; zero exactly at a KKT point)
+ *   [1] energy  worst energy-row violation / max(1, |cap|)
+ *   [2] site    worst site-row violation / max(1, limit)   (LINEAR rows, SOC pairs, finite peak periods)
+ *   [3] comp    worst multiplier x slack / (max(1, |q|_inf) max(1, limit)) over those rows, and over the demand-charge
+ *               row y_t (max_t v'x_t - v'x_t) / (max(1, |q|_inf) max(1, |max_t v'x_t|))
+ * Periods t >= horizon[b] and entries outside every window get exact zeros in z; an empty slot gets 0 in mu.  A problem
+ * whose status is neither SOLVED nor SOLVED_INACCURATE gets zeros in mu and z and +inf in its four residuals.
+ * No floating-point atomics, fixed summation order: the same problem gives the same bits in any batch, at any position. */
+typedef struct {
+  double* mu;   /* [B*K*N]   layout of s_cap: multiplier of each session's energy row (per A-period) */
+  double* z;    /* [B*N*Tm]  or NULL (not wanted): multipliers of the rate bounds                     */
+  double* res;  /* [B*4]     stat, energy, site, comp                                                */
+} acnqp_duals;
+
+/* acnqp_duals_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns without
+ * synchronising.  p: the problems (warm_x / warm_y ignored); o: read for reg_rel only; x [B*N*Tm], y [B*n_rows*Tm]
+ * (may be NULL for a site without rows) and status [B] (NULL: every problem counts as solved) as a solve wrote them.
+ * Bad arguments, a null handle included, return ACNQP_ERR_INVALID with acnqp_last_error set.                        */
+int acnqp_duals_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x,
+                       const double* y, const int32_t* status, acnqp_duals* out, void* hip_stream);
+
+/* acnqp_duals_host -- the same with host pointers, synchronous; a large batch is processed in chunks.  Same bits as
+ * the device entry.                                                                                                  */
+int acnqp_duals_host(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x,
+                     const double* y, const int32_t* status, acnqp_duals* out);
+
 #ifdef __cplusplus
 }
 #endif
