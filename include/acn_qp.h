@@ -149,6 +149,18 @@ typedef struct {
                         so that a collective (the RCCL all-gather of a multi-GPU job) can start
                         from HBM without re-uploading them.  Ignored by acnqp_solve_batch_device. */
 } acnqp_results;
+/* What the outputs hold for a problem that is not solved -- the same on every kernel family (tests/test_verdicts_gpu.py
+ * pins it on all eleven of acnqp_route).  Every element of every output is written whatever the status.
+ *   PRIMAL_INFEASIBLE, MAX_ITER:  x is the ADMM iterate z at exit: finite, lb <= x <= ub exactly, exact zeros outside
+ *       the session windows and at t >= horizon[b], on the energy rows to the projection's roundoff -- a point of the
+ *       box-and-energy set, NOT of the site rows, and not a schedule to apply.  y (when wanted) is the finite multiplier
+ *       iterate, zero at t >= horizon[b]; obj is the objective of that x; pri_res / dua_res are the finite residuals of
+ *       the last check; iters the iterations made (all passes; < max_iter for a certificate, max_iter per pass else).
+ *   EMPTY_SET:  decided before any iteration, on the raw arrays (sum lb > cap, or sum ub < cap under equality, beyond
+ *       64e-13 max(1, |cap|)): x = 0 and y = 0 everywhere, iters = 0, obj = 0, pri_res = dua_res = 1e300.
+ * The certificate behind PRIMAL_INFEASIBLE is a test on the change v of the multipliers between two residual checks
+ * (|A'v|_inf <= 1e-4 |v|_inf and a support-function bound below -1e-4 |v|_inf), not a proof: what it decides at relative
+ * distances 1e-2 ... 1e-5 either side of the feasibility boundary is pinned by tests/verdict_cases.py.                 */
 
 /* Solver options -- the knobs cvxpy would forward to its solver (the
  * reference sets none, aco.py:318; defaults: acnqp_default_options). */

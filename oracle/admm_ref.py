@@ -187,6 +187,57 @@ def _prox_rows(zh, rho, site, limits, peak_b, T, lf, lf_ext):
     return z
 
 
+def _certifies_infeasibility(v1, v2, G, limits, peak_b, site, lb, ub, s_off, s_len, s_cap, eq, qnorm):
+    """The primal infeasibility certificate of the device kernels and oracle/admm_port.c, on the change v = (v1, v2) of
+    the multipliers (y1 of the box / energy set B, y2 of the site rows C, equilibrated units) between two residual checks:
+    if A'v = v1 + G'v2 ~ 0 and the support function of B x C at v is negative, no point of B x C solves A r = z.
+    Accepted when |A'v|_inf <= 1e-4 |v|_inf and the bound on the support function is below -1e-4 |v|_inf."""
+    Mg, M = G.shape[0], site.M
+    vn = max(np.abs(v1).max(), np.abs(v2).max() if Mg else 0.0)
+    vtol = 1e-4 * vn
+    if not (vn > 1e-12 * max(1.0, qnorm) and np.abs(v1 + G.T @ v2).max() <= vtol):
+        return False
+    ssum = 0.0
+    for r in range(Mg):
+        if site.cone == CONE_SOC and r < M:            # disc: radius * |(v_re, v_im)|
+            ssum += limits[r] * np.hypot(v2[r], v2[r + M]).sum()
+        elif site.cone == CONE_SOC and r < 2 * M:
+            pass
+        elif r < M:                                    # box: z <= limit
+            ssum += limits[r] * np.maximum(v2[r], 0.0).sum()
+            if (v2[r] < -vtol).any():
+                return False
+        elif site.has_peak and r == Mg - 1:
+            pk = np.full(v2.shape[1], np.inf) if peak_b is None else peak_b
+            fin = pk < 1e300
+            ssum += (pk[fin] * np.maximum(v2[r][fin], 0.0)).sum()
+            if (v2[r][~fin] > vtol).any() or (v2[r] < -vtol).any():
+                return False
+        elif (np.abs(v2[r]) > vtol).any():             # prox rows admit no ray
+            return False
+    # sessions: phi(l) = l cap + sum_t [ub (v_t - l)+ + lb (v_t - l)-] bounds the support function for any admissible
+    # l; evaluated at min v, max v, 0.  Periods outside every window are pinned to lb (= ub).
+    covered = np.zeros(v1.shape, bool)
+    K, N = s_len.shape
+    for k in range(K):
+        for i in range(N):
+            L, o = int(s_len[k, i]), int(s_off[k, i])
+            if L <= 0:
+                continue
+            win = slice(o, min(o + L, v1.shape[1]))
+            covered[i, win] = True
+            v = v1[i, win]
+            best = np.inf
+            for l_ in (v.min(), v.max(), 0.0):
+                if not eq:
+                    l_ = max(l_, 0.0)
+                dv = v - l_
+                best = min(best, l_ * s_cap[k, i] + (ub[i, win] * np.maximum(dv, 0.0) + lb[i, win] * np.minimum(dv, 0.0)).sum())
+            ssum += best
+    ssum += (lb[~covered] * v1[~covered]).sum()
+    return bool(ssum < -vtol)
+
+
 def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
     """Run the ADMM on problem ``b`` of a builder.ProblemBatch-like object.
     Returns dict(x (N,Tm), status, iters, pri_res, dua_res, obj, rho)."""
@@ -196,6 +247,17 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
         return dict(x=np.zeros((N, Tm)), status=ST_PRESOLVE_INFEASIBLE, iters=0,
                     pri_res=np.inf, dua_res=np.inf, obj=np.nan, rho=opts.rho)
     lb, ub, q = batch.lb[b], batch.ub[b], batch.q[b]
+    # EMPTY_SET: a session whose own bounds cannot meet its energy row (the kernels' test, before any iteration)
+    for k in range(batch.s_len.shape[1]):
+        for i in range(N):
+            L, o = int(batch.s_len[b, k, i]), int(batch.s_off[b, k, i])
+            if L > 0:
+                cap = float(batch.s_cap[b, k, i])
+                slack = 64 * 1e-13 * max(1.0, abs(cap))
+                lo, hi = lb[i, o:o + L].sum(), np.maximum(ub[i, o:o + L], lb[i, o:o + L]).sum()
+                if lo > cap + slack or (bool(batch.s_eq[b]) and hi < cap - slack):
+                    return dict(x=np.zeros((N, Tm)), status=ST_PRESOLVE_INFEASIBLE, iters=0,   # (include/acn_qp.h)
+                                pri_res=1e300, dua_res=1e300, obj=0.0, rho=opts.rho)
     pdiag = float(batch.pdiag[b])
     # Tikhonov floor: LP-like problems only (kRegResolve / effective_pdiag in acn_qp_tiled.hpp)
     has_prox = float(batch.lf[b]) > 0 or (getattr(batch, "dc", None) is not None and float(batch.dc[b]) > 0)
@@ -226,6 +288,7 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
     it = 0
     n_adapt = 0
     best_score, best_it = np.inf, 0
+    y_prev = None   # (y1, y2) at the previous check: the infeasibility certificate tests their difference
     aa = _Anderson(opts.accel_mem, N * Tm + Mg * Tm) if opts.accel_mem > 0 else None
     if aa is not None:
         aa.uprev = np.concatenate([(z1 + y1 / rho).ravel(), z2.ravel()])
@@ -263,6 +326,13 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
             if pri <= opts.eps_abs + opts.eps_rel * npri and dua <= opts.eps_abs + opts.eps_rel * ndua:
                 status = ST_SOLVED
                 break
+            if y_prev is not None and _certifies_infeasibility(
+                    y1 - y_prev[0], y2 - y_prev[1], G, limits, peak_b, site, lb, ub, batch.s_off[b], batch.s_len[b],
+                    batch.s_cap[b], eq, np.abs(q).max()):
+                status = ST_PRIMAL_INFEASIBLE
+                break
+            # the device keeps this snapshot in single precision (registers): same rounding here
+            y_prev = (y1.astype(np.float32).astype(np.float64), y2.astype(np.float32).astype(np.float64))
             score = max(pri / max(opts.eps_abs + opts.eps_rel * npri, 1e-300), dua / max(opts.eps_abs + opts.eps_rel * ndua, 1e-300))
             if score < STALL_GAIN * best_score:
                 best_score, best_it = score, it

@@ -302,3 +302,31 @@ def edges_pool(name, n, seed=0):
     base = build_batch([sl], infra, iface, obj, meta["ct"], meta["eq"], peak_limits=[peak])
     rng = np.random.default_rng(seed)
     return scenario_batch(base, rng.uniform(0.85, 1.0, size=(n, base.K, base.N)))
+
+
+# ---- one launch per kernel family (tests/test_route_certificate.py, tests/test_verdicts_gpu.py) -----------------------
+T_PADS = (12, 13, 17, 20, 25, 28, 33, 40, 49, 60, 289)
+
+
+def route_shapes(h, batch):
+    """{family: (t_max, k_sessions)}: the smallest padded shape of each family this pool reaches"""
+    out = {}
+    for k in sorted({batch.K, max(batch.K, 2), 5}):
+        for t in sorted({batch.Tm} | {t for t in T_PADS if t >= batch.Tm}):
+            fam, _ = h.route(t, k, batch.B)
+            out.setdefault(fam, (t, k))
+    return out
+
+
+def launch_poisoned(h, batch, options=None):
+    """one launch through the device entry with every output poisoned (NaN, iters -1); returns host arrays"""
+    import torch
+    from adacharge_amd.backend import DeviceBatch
+
+    dev = DeviceBatch(batch, "cuda:0", want_y=True)
+    for a in (dev.x, dev.y, dev.pri_res, dev.dua_res, dev.obj):
+        a.fill_(float("nan"))
+    dev.iters.fill_(-1)
+    h.solve_device(dev, options, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return {k: getattr(dev, k).cpu().numpy() for k in ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")}

@@ -17,6 +17,7 @@ import pytest
 
 from oracle import kkt
 from tests import helpers as H
+from tests.helpers import launch_poisoned as _launch_poisoned, route_shapes as _shapes
 
 RATE_TOL = 1e-4 * 32.0   # north star: 1e-4 relative on rates, 32 A pilots (the hard limit across routes)
 # |x_route - x_route'| of a problem SOLVED on both routes, per pool: 10x the worst difference measured on an MI355X (in
@@ -40,7 +41,6 @@ ROUTE_RATE_TOL = {
 # 3.9e-9; load flattening: 9.3e-9).  Measured elsewhere: <= 7.9e-10.
 ROUTE_OBJ_REL = {"edges_jpl_t13_soc": 3.9e-8, "edges_n100_t24_lf": 9.4e-8}
 FAMILIES = {"wave1", "wave2", "wave3", "wave4", "wave5", "tiled_ct1", "tiled_ct2", "long_lds", "long_ws", "stream", "general"}
-T_PADS = (12, 13, 17, 20, 25, 28, 33, 40, 49, 60, 289)
 
 
 def _stalled_pool(copies=5):
@@ -76,30 +76,6 @@ POOLS = {
     "edges_n100_t24_lf": lambda: H.edges_pool("n100_t24_lf", 64, 44),
     "edges_jpl_t28_dc": lambda: H.edges_pool("jpl_t28_dc", 64, 45),
 }
-
-
-def _shapes(h, batch):
-    """{family: (t_max, k_sessions)}: the smallest padded shape of each family this pool reaches"""
-    out = {}
-    for k in sorted({batch.K, max(batch.K, 2), 5}):
-        for t in sorted({batch.Tm} | {t for t in T_PADS if t >= batch.Tm}):
-            fam, _ = h.route(t, k, batch.B)
-            out.setdefault(fam, (t, k))
-    return out
-
-
-def _launch_poisoned(h, batch):
-    """one launch through the device entry with every output poisoned (NaN, iters -1); returns host arrays"""
-    import torch
-    from adacharge_amd.backend import DeviceBatch
-
-    dev = DeviceBatch(batch, "cuda:0", want_y=True)
-    for a in (dev.x, dev.y, dev.pri_res, dev.dua_res, dev.obj):
-        a.fill_(float("nan"))
-    dev.iters.fill_(-1)
-    h.solve_device(dev, stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return {k: getattr(dev, k).cpu().numpy() for k in ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")}
 
 
 @functools.lru_cache(maxsize=None)
