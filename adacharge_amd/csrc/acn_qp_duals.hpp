@@ -23,7 +23,7 @@
 
 #include <cstdint>
 
-#include "acn_qp_tiled.hpp"
+#include "acn_qp_common.hpp"
 
 namespace acnqp {
 

@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "acn_qp_tiled.hpp"
+#include "acn_qp_common.hpp"
 
 namespace acnqp {
 
@@ -52,11 +52,11 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
   __shared__ real aaH[kGenAccelMax * kGenAccelMax + kGenAccelMax];
   __shared__ real aaG[kGenAccelMax];
   // passes: pass 0 as the options state it, then cold fixed-penalty retries of a stalled problem (retry_wanted,
-  // acn_qp_tiled.hpp).  The WHOLE body is the pass, with the thread / block ids opaque and the argument block read
+  // acn_qp_common.hpp).  The WHOLE body is the pass, with the thread / block ids opaque and the argument block read
   // through a per-pass opaque pointer to the kernarg segment: nothing of a pass is invariant across passes, so no
   // pass-invariant address, predicate or argument is kept alive across the solver loop.
   __shared__ int q_slot;
-  for (int q_round = 0;; ++q_round) {   // work queue: this workgroup's next problem (queue_next, acn_qp_tiled.hpp)
+  for (int q_round = 0;; ++q_round) {   // work queue: this workgroup's next problem (queue_next, acn_qp_common.hpp)
   const int q_pos = queue_next(SA_kernarg.t.queue, queue_length(SA_kernarg.t), q_round, &q_slot);
   if (q_pos < 0) break;
   int it_total = 0, best_status = 0;
@@ -460,9 +460,10 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
       dua = block_reduce_max<real, kGenThreads>(v1, red, tid);
       const real npri = block_reduce_max<real, kGenThreads>(v2, red, tid);
       const real ndua = fmax(fmax(block_reduce_max<real, kGenThreads>(v4, red, tid), block_reduce_max<real, kGenThreads>(v5, red, tid)), qnorm);
-      if (pri <= (real)A.eps_abs + (real)A.eps_rel * npri && dua <= (real)A.eps_abs + (real)A.eps_rel * ndua) { status = 1; done = true; }
+      const CheckTol<real> eps = check_tolerances<real>(A.eps_abs, A.eps_rel, npri, ndua);
+      if (converged(pri, dua, eps)) { status = 1; done = true; }
       if (!done && have_prev) {
-        // ---- primal infeasibility certificate (see acn_qp_tiled.hpp): v = y - y(previous check) ------------
+        // ---- primal infeasibility certificate (acn_qp_check.hpp): v = y - y(previous check) ------------
         real vnl = 0, atl = 0;
         for (int k = tid; k < n; k += kGenThreads) {
           const int i = k / T, t = k - i * T;
@@ -475,23 +476,16 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
         for (int k = tid; k < mt; k += kGenThreads) vnl = fmax(vnl, fabs(y2[k] - y2p[k]));
         const real vn = block_reduce_max<real, kGenThreads>(vnl, red, tid);
         const real atv = block_reduce_max<real, kGenThreads>(atl, red, tid);
-        const real vtol = (real)1e-4 * vn;
-        if (vn > (real)1e-12 * fmax((real)1, qnorm) && atv <= vtol) {   // block-uniform
+        real vtol;
+        if (cert_gate<real>(vn, atv, qnorm, vtol)) {   // block-uniform
           real ssum = 0, bad = 0;
           for (int k = tid; k < mt; k += kGenThreads) {
             const int r = k / T, t = k - r * T;
             const int ty = A.rowtype[r];
-            const real v2 = y2[k] - y2p[k];
-            if (ty == kRowBox) { ssum += RL[r] * fmax(v2, (real)0); if (v2 < -vtol) bad = 1; }
-            else if (ty == kRowPeak) {
-              const double pv = A.peak ? A.peak[(size_t)b * T + t] : 1e300;
-              if (pv < (double)M::big) ssum += (real)(pv * A.peak_scale) * fmax(v2, (real)0); else if (v2 > vtol) bad = 1;
-              if (v2 < -vtol) bad = 1;
-            } else if (ty == kRowSocRe) {
-              const real vi = y2[(r + GA.pair_stride) * T + t] - y2p[(r + GA.pair_stride) * T + t];
-              ssum += RL[r] * sqrt(v2 * v2 + vi * vi);
-            } else if (ty == kRowSocIm) {
-            } else if (fabs(v2) > vtol) bad = 1;   // free / prox rows admit no ray
+            const double pv = A.peak && ty == kRowPeak ? A.peak[(size_t)b * T + t] : 1e300;
+            const int kp = ty == kRowSocRe ? (r + GA.pair_stride) * T + t : k;   // the partner of a SOC pair
+            const real pk = pv < (double)M::big ? (real)(pv * A.peak_scale) : M::big;
+            cert_row_ray<real>(ty, y2[k] - y2p[k], y2[kp] - y2p[kp], cert_row_has_limit(ty) ? RL[r] : (real)0, pk, M::big, vtol, ssum, bad);
           }
           // sessions (zh is free at this point: coverage flags of the periods that lie in some window)
           for (int k = tid; k < n; k += kGenThreads) zh[k] = 0;
@@ -511,13 +505,10 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
             }
             real best = M::big;
             for (int j = 0; j < 3; ++j) {
-              real l_ = j == 0 ? lmin : (j == 1 ? lmax : (real)0);
-              if (!eq) l_ = fmax(l_, (real)0);
+              const real l_ = cert_session_candidate<real>(j == 0 ? lmin : (j == 1 ? lmax : (real)0), eq);
               real ph = l_ * (real)A.s_cap[sidx];
-              for (int t = off; t < off + len; ++t) {
-                const real dv = (y1[i * T + t] - y1p[i * T + t]) - l_;
-                ph += ub[i * T + t] * fmax(dv, (real)0) + (real)lbg[i * T + t] * fmin(dv, (real)0);
-              }
+              for (int t = off; t < off + len; ++t)
+                ph += cert_support_term<real>(ub[i * T + t], (real)lbg[i * T + t], (y1[i * T + t] - y1p[i * T + t]) - l_);
               best = fmin(best, ph);
             }
             ssum += best;
@@ -527,7 +518,7 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
             if (zh[k] == (real)0) ssum += (real)lbg[k] * (y1[k] - y1p[k]);
           const real stot = block_reduce_sum<real, kGenThreads>(ssum, red, tid);
           const real anyb = block_reduce_max<real, kGenThreads>(bad, red, tid);
-          if (anyb == (real)0 && stot < -vtol) { status = 3; done = true; }
+          if (cert_verdict(anyb, stot, vtol)) { status = 3; done = true; }
         }
       }
       if (!done) {   // snapshot for the next certificate test
@@ -536,22 +527,18 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
         for (int k = tid; k < mt; k += kGenThreads) y2p[k] = (real)(float)y2[k];
         have_prev = true;
       }
-      const real score = fmax(pri / fmax((real)A.eps_abs + (real)A.eps_rel * npri, (real)1e-300),
-                              dua / fmax((real)A.eps_abs + (real)A.eps_rel * ndua, (real)1e-300));
-      if (score < (real)kStallGain * best_score) { best_score = score; best_it = it; }
+      const real score = stall_score<real>(pri, dua, eps);
+      if (stall_improved<real>(score, best_score)) { best_score = score; best_it = it; }
       const bool inacc = inaccurate_ok<real>(pri, dua, npri, ndua, A.eps_abs, A.eps_rel, A.inacc_floor);
-      const bool stalled = A.stall_iters > 0 && it - best_it >= A.stall_iters && score <= (real)kStallNear * best_score;   // acn_qp_tiled.hpp
+      const bool stalled = stall_reached<real>(A.stall_iters, it, best_it, score, best_score);
       if (done) {
       } else if (it >= max_iter_p || stalled) {
         done = true;
         if (inacc) status = 5;   // solved, inaccurately
-      }
-      else if (adapt_p > 0 && it % adapt_p == 0) {
-        const real sp = pri / fmax(npri, (real)1e-12), sd = dua / fmax(ndua, (real)1e-12);
-        const real ratio = sqrt(sp / fmax(sd, (real)1e-30));
-        const real tol_eff = (real)A.adapt_tol * ((real)1 + (real)n_adapt * (real)(1.0 / kAdaptWiden));
-        if (ratio > tol_eff || ratio < (real)1 / tol_eff) {
-          rho = fmin(fmax(rho * ratio, (real)1e-6), (real)1e6);
+      } else if (adapt_p > 0 && it % adapt_p == 0) {
+        const real ratio = rho_ratio<real>(pri, dua, npri, ndua);
+        if (rho_outside_band(ratio, A.adapt_tol, n_adapt)) {
+          rho = rho_clamped<real>(rho * ratio);
           ++n_adapt;
           if (aa_m > 0) {   // the fixed-point map changed: restart the ring from the current (z, y)
             aa_cnt = 0; aa_head = 0; aa_valid = 0; aa_have_prev = false; aa_was = false;

@@ -40,7 +40,7 @@ inline int accel_capacity_best(int NW, int MT, int CT, int NP, int K, int* pbuf_
 
 // Grid of a launch.  With the work queue (a.queue set) it is the number of workgroups the chip keeps RESIDENT for this
 // kernel -- occupancy x compute units, never more than the problems or than `a.grid_cap` -- and the workgroups fetch
-// problems until the queue is empty (queue_next, acn_qp_tiled.hpp); without it one workgroup per problem.
+// problems until the queue is empty (queue_next, acn_qp_common.hpp); without it one workgroup per problem.
 // (occupancy and device queries cost tens of microseconds each: with three launches per pipelined chunk they made the
 //  host thread the bottleneck -- 18 chunks per step -- so both are cached per (kernel, block size, LDS) and per device)
 inline int resident_per_cu(const void* kern, int threads, size_t lds) {

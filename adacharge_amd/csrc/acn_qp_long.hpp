@@ -110,10 +110,10 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
   real* HH = EH + MT * CTL * 256;                 // h^ (start: Ghat z1)
 
   // passes: pass 0 as the options state it, then cold fixed-penalty retries of a stalled problem (retry_wanted,
-  // acn_qp_tiled.hpp).  The WHOLE body is the pass, with the argument block read through a per-pass opaque pointer to
+  // acn_qp_common.hpp).  The WHOLE body is the pass, with the argument block read through a per-pass opaque pointer to
   // the kernarg segment: no argument is kept alive across the solver loop for the next pass's sake.
   __shared__ int q_slot;
-  for (int q_round = 0;; ++q_round) {   // work queue: this workgroup's next problem (queue_next, acn_qp_tiled.hpp)
+  for (int q_round = 0;; ++q_round) {   // work queue: this workgroup's next problem (queue_next, acn_qp_common.hpp)
   const int q_pos = queue_next(SA_kernarg.t.queue, queue_length(SA_kernarg.t), q_round, &q_slot);
   if (q_pos < 0) break;
   int it_total = 0, best_status = 0;
@@ -1096,13 +1096,10 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
       stream_block_max<5, NWV>(v, SC, lane, wave);
       pri = v[0]; dua = v[1];
       const real npri = v[2], ndua = fmax(fmax(v[3], v[4]), qnorm);
-      const real eps_p = A.eps_abs + A.eps_rel * npri, eps_d = A.eps_abs + A.eps_rel * ndua;
-      if (pri <= eps_p && dua <= eps_d) { status = 1; done = true; }
+      const CheckTol<real> eps = check_tolerances<real>(A.eps_abs, A.eps_rel, npri, ndua);
+      if (converged(pri, dua, eps)) { status = 1; done = true; }
       if (!done && have_prev) {
-        // ---- primal infeasibility certificate (OSQP's, generalised to the sets B and C; acn_qp_tiled.hpp) ----------
-        // v = y - y(previous check).  If A'v ~ 0 and the support function of B x C at v is negative, no point of
-        // B x C satisfies A r = z.  For B the support function of a session is bounded above by
-        // phi(l) = l cap + sum_t [ub (v_t - l)+ + lb (v_t - l)-] for any admissible l.
+        // ---- primal infeasibility certificate (acn_qp_check.hpp): v = y - y(previous check) ----------
         real w6[2] = {0, 0};   // |v|, |v1 + G'v2|
 #pragma unroll 1
         for (int q = wave; q < n_tile; q += NWV) {
@@ -1133,8 +1130,8 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
         }
         stream_block_max<2, NWV>(w6, SC, lane, wave);
         const real vn = w6[0];
-        const real vtol = 1e-4 * vn;
-        if (vn > 1e-12 * fmax(1.0, qnorm) && w6[1] <= vtol) {   // block-uniform
+        real vtol;
+        if (cert_gate<real>(vn, w6[1], qnorm, vtol)) {   // block-uniform
           real ssum = 0, bad = 0;
 #pragma unroll 1
           for (int q = wave; q < n_site; q += NWV) {   // site rows
@@ -1145,20 +1142,11 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
             if (A.peak && tt < Tm) { const double pv = A.peak[(size_t)b * Tm + tt]; pk = pv < M::big ? pv * A.peak_scale : M::big; }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const unsigned i = sidx2(m, c, r);
+              const unsigned i = sidx2(m, c, r), i2 = sidx2(m, c, (r + 1) & 3);
               const int j = 16 * m + M::rowof(g, r);
-              const real v2_ = at(Y2, i) - (real)at(Y2P, i);
               const int ty = RowTy[j];
-              if (ty == kRowBox) { ssum += RowLim[j] * fmax(v2_, 0.0); if (v2_ < -vtol) bad = 1; }
-              else if (ty == kRowPeak) {
-                if (pk < M::big) ssum += pk * fmax(v2_, 0.0); else if (v2_ > vtol) bad = 1;
-                if (v2_ < -vtol) bad = 1;
-              } else if (ty == kRowSocRe) {
-                const unsigned i2 = sidx2(m, c, (r + 1) & 3);
-                const real vi = at(Y2, i2) - (real)at(Y2P, i2);
-                ssum += RowLim[j] * sqrt(v2_ * v2_ + vi * vi);
-              } else if (ty == kRowSocIm) {
-              } else if (fabs(v2_) > vtol) bad = 1;   // free / quadratic rows admit no ray
+              cert_row_ray<real>(ty, at(Y2, i) - (real)at(Y2P, i), ty == kRowSocRe ? at(Y2, i2) - (real)at(Y2P, i2) : 0.0,
+                                 cert_row_has_limit(ty) ? RowLim[j] : 0.0, pk, M::big, vtol, ssum, bad);
             }
           }
           // sessions (row items): bound each session's support function; periods outside every window are pinned
@@ -1201,16 +1189,12 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
               real best = M::big;
 #pragma unroll
               for (int j = 0; j < 3; ++j) {
-                real l_ = lam3[j];
-                if (!eq) l_ = fmax(l_, 0.0);
+                const real l_ = cert_session_candidate<real>(lam3[j], eq);
                 real ph = 0;
 #pragma unroll
                 for (int c = 0; c < CTL; ++c) {
                   const int tp = 16 * c + t;
-                  if (tp >= off && tp < off + len) {
-                    const real dv = vv[c] - l_;
-                    ph += ubv[c] * fmax(dv, 0.0) + lbv[c] * fmin(dv, 0.0);
-                  }
+                  if (tp >= off && tp < off + len) ph += cert_support_term<real>(ubv[c], lbv[c], vv[c] - l_);
                 }
                 ph = row_sum<real>(ph) + l_ * cap;
                 best = fmin(best, ph);
@@ -1227,7 +1211,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
           real stot = 0, bmax = 0;
           for (int wv = 0; wv < NWV; ++wv) { stot += SC[wv * 8]; bmax = fmax(bmax, SC[wv * 8 + 1]); }
           __syncthreads();
-          if (bmax == 0.0 && stot < -vtol) { status = 3; done = true; }
+          if (cert_verdict(bmax, stot, vtol)) { status = 3; done = true; }
         }
       }
       if (!done) {   // snapshot for the next certificate test
@@ -1247,29 +1231,22 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
         }
         have_prev = true;
       }
-      const real score = fmax(pri / fmax(eps_p, 1e-300), dua / fmax(eps_d, 1e-300));
-      if (score < kStallGain * best_score) { best_score = score; best_it = it; }
+      const real score = stall_score<real>(pri, dua, eps);
+      if (stall_improved<real>(score, best_score)) { best_score = score; best_it = it; }
       const bool inacc = inaccurate_ok<real>(pri, dua, npri, ndua, A.eps_abs, A.eps_rel, A.inacc_floor);
-      const bool stalled = A.stall_iters > 0 && it - best_it >= A.stall_iters && score <= kStallNear * best_score;   // acn_qp_tiled.hpp
+      const bool stalled = stall_reached<real>(A.stall_iters, it, best_it, score, best_score);
       bool hand_over = false;
       if (!done && pass == 0 && A.polish_iters > 0 && it >= A.polish_iters) {   // block-uniform
-        // rows the polish's Schur system would have (acn_qp_tiled.hpp): more than it holds -> the ADMM goes on
-        real cnt = 0;
-        const real ytol = 1e-9 * fmax(1.0, qnorm);
+        real cnt = 0;   // rows the polish's Schur system would have (polish_row_weight): more than it holds -> the ADMM goes on
+        const real ytol = polish_ytol<real>(qnorm);
 #pragma unroll 1
         for (int q = wave; q < n_site; q += NWV) {
           RELANE();
           const int m = __builtin_amdgcn_readfirstlane(q / nct), c = q - m * nct;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int j = 16 * m + M::rowof(g, r);
-            const int ty = RowTy[j];
-            const real yr = at(Y2, sidx2(m, c, r)), yi = at(Y2, sidx2(m, c, (r + 1) & 3));
-            const bool disc = ty == kRowSocRe;
-            const real mag = disc ? sqrt(yr * yr + yi * yi) : yr;
-            const bool counts = (disc || ty == kRowBox || ty == kRowPeak) && 16 * c + t < Tm && mag > ytol;
-            cnt += counts ? (disc ? 2.0 : 1.0) : 0.0;
-          }
+          for (int r = 0; r < 4; ++r)
+            cnt += polish_row_weight<real>(RowTy[16 * m + M::rowof(g, r)], at(Y2, sidx2(m, c, r)), at(Y2, sidx2(m, c, (r + 1) & 3)),
+                                           ytol, 16 * c + t < Tm);
         }
         cnt = wave_sum<real>(cnt);
         __syncthreads();
@@ -1278,7 +1255,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
         real tot = 0;
         for (int wv = 0; wv < NWV; ++wv) tot += SC[wv];
         __syncthreads();
-        hand_over = tot + 8.0 <= (real)A.pol_rows;
+        hand_over = polish_fits(tot, A.pol_rows);
       }
       if (done) {
       } else if (hand_over) {
@@ -1286,14 +1263,12 @@ __global__ __launch_bounds__(NWV * 64, 1) void admm_long_kernel(const StreamArgs
         done = true;
       } else if (it >= max_iter_p || stalled) {
         done = true;
-        if (inacc) status = 5;
+        if (inacc) status = 5;   // solved, inaccurately
       } else if (adapt_p > 0 && it % adapt_p == 0) {
-        const real sp = pri / fmax(npri, 1e-12), sd = dua / fmax(ndua, 1e-12);
-        const real ratio = sqrt(sp / fmax(sd, 1e-30));
-        const real tol_eff = A.adapt_tol * (1.0 + (real)n_adapt * (1.0 / kAdaptWiden));
-        if (ratio > tol_eff || ratio < 1.0 / tol_eff) {
+        const real ratio = rho_ratio<real>(pri, dua, npri, ndua);
+        if (rho_outside_band(ratio, A.adapt_tol, n_adapt)) {
           ++n_adapt;
-          rho = fmin(fmax(rho * ratio, 1e-6), 1e6);
+          rho = rho_clamped<real>(rho * ratio);
           set_dj();
           // r0 and u depend on rho; the fixed-point map changed: restart the ring from the current (z, y)
 #pragma unroll 1

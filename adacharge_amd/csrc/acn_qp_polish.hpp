@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "acn_qp_tiled.hpp"
+#include "acn_qp_common.hpp"
 
 namespace acnqp {
 

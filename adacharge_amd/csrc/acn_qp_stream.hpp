@@ -31,7 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "acn_qp_tiled.hpp"
+#include "acn_qp_common.hpp"
 
 namespace acnqp {
 
@@ -132,12 +132,12 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
   real* SC = sm + L.scal;
 
   // passes: pass 0 as the options state it, then cold fixed-penalty retries of a stalled problem (retry_wanted,
-  // acn_qp_tiled.hpp).  The WHOLE body is the pass, with the thread / block ids opaque and the argument block read
+  // acn_qp_common.hpp).  The WHOLE body is the pass, with the thread / block ids opaque and the argument block read
   // through a per-pass opaque pointer to the kernarg segment: nothing of a pass is invariant across passes, so no
   // pass-invariant address, predicate or argument is kept alive across the solver loop.
   __shared__ int q_slot;
   __shared__ unsigned char TileFlat[kStreamFlatTiles];   // per EVSE tile: its bounds compress (flat tiles, tile_back)
-  for (int q_round = 0;; ++q_round) {   // work queue: this workgroup's next problem (queue_next, acn_qp_tiled.hpp)
+  for (int q_round = 0;; ++q_round) {   // work queue: this workgroup's next problem (queue_next, acn_qp_common.hpp)
   const int q_pos = queue_next(SA_kernarg.t.queue, queue_length(SA_kernarg.t), q_round, &q_slot);
   if (q_pos < 0) break;
   int it_total = 0, best_status = 0;
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
   {
     real f[3] = {qn, um, bad};
     stream_block_max<3, NWV>(f, SC, lane, wave);
-    // block-uniform doubles are forced into scalar registers (uniform_scalar, acn_qp_tiled.hpp): as vector-register
+    // block-uniform doubles are forced into scalar registers (uniform_scalar, acn_qp_common.hpp): as vector-register
     // pairs a dozen of them were spilled around every tile of the fused pass
     qnorm = uniform_scalar(f[0]);
     pd = uniform_scalar(effective_pdiag<real>(pd_user, A.reg_rel, qnorm, f[1], A.horizon[b], lfb > 0.0 || dcb > 0.0));
@@ -1227,13 +1227,10 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
       stream_block_max<5, NWV>(v, SC, lane, wave);
       pri = v[0]; dua = v[1];
       const real npri = v[2], ndua = fmax(fmax(v[3], v[4]), qnorm);
-      const real eps_p = A.eps_abs + A.eps_rel * npri, eps_d = A.eps_abs + A.eps_rel * ndua;
-      if (pri <= eps_p && dua <= eps_d) { status = 1; done = true; }
+      const CheckTol<real> eps = check_tolerances<real>(A.eps_abs, A.eps_rel, npri, ndua);
+      if (converged(pri, dua, eps)) { status = 1; done = true; }
       if (!done && have_prev) {
-        // ---- primal infeasibility certificate (OSQP's, generalised to the sets B and C; acn_qp_tiled.hpp) ----------
-        // v = y - y(previous check).  If A'v ~ 0 and the support function of B x C at v is negative, no point of
-        // B x C satisfies A r = z.  For B the support function of a session is bounded above by
-        // phi(l) = l cap + sum_t [ub (v_t - l)+ + lb (v_t - l)-] for any admissible l.
+        // ---- primal infeasibility certificate (acn_qp_check.hpp): v = y - y(previous check) ----------
         real w6[2] = {0, 0};   // |v|, |v1 + G'v2|
 #pragma unroll 1
         for (int tl = wave; tl < MT * CT; tl += kStreamWaves) {
@@ -1265,8 +1262,8 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
         }
         stream_block_max<2, NWV>(w6, SC, lane, wave);
         const real vn = w6[0];
-        const real vtol = 1e-4 * vn;
-        if (vn > 1e-12 * fmax(1.0, qnorm) && w6[1] <= vtol) {   // block-uniform
+        real vtol;
+        if (cert_gate<real>(vn, w6[1], qnorm, vtol)) {   // block-uniform
           real ssum = 0, badv = 0;
 #pragma unroll 1
           for (int tl = wave; tl < MT * CT; tl += kStreamWaves) {   // site rows
@@ -1277,20 +1274,11 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
             if (A.peak && tt < Tm) { const double pv = A.peak[(size_t)b * Tm + tt]; pk = pv < M::big ? pv * A.peak_scale : M::big; }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const int i = (tl * 4 + r) * 64 + lane;
+              const int i = (tl * 4 + r) * 64 + lane, i2 = (tl * 4 + ((r + 1) & 3)) * 64 + lane;
               const int j = 16 * m + M::rowof(g, r);
-              const real v2_ = Y2[i] - (real)Y2P[i];
               const int ty = RTi[j];
-              if (ty == kRowBox) { ssum += RLi[j] * fmax(v2_, 0.0); if (v2_ < -vtol) badv = 1; }
-              else if (ty == kRowPeak) {
-                if (pk < M::big) ssum += pk * fmax(v2_, 0.0); else if (v2_ > vtol) badv = 1;
-                if (v2_ < -vtol) badv = 1;
-              } else if (ty == kRowSocRe) {
-                const int i2 = (tl * 4 + ((r + 1) & 3)) * 64 + lane;
-                const real vi = Y2[i2] - (real)Y2P[i2];
-                ssum += RLi[j] * sqrt(v2_ * v2_ + vi * vi);
-              } else if (ty == kRowSocIm) {
-              } else if (fabs(v2_) > vtol) badv = 1;   // free / prox rows admit no ray
+              cert_row_ray<real>(ty, Y2[i] - (real)Y2P[i], ty == kRowSocRe ? Y2[i2] - (real)Y2P[i2] : 0.0,
+                                 cert_row_has_limit(ty) ? RLi[j] : 0.0, pk, M::big, vtol, ssum, badv);
             }
           }
           // sessions (one register row at a time): bound each session's support function; periods outside every
@@ -1330,16 +1318,12 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
               real best = M::big;
 #pragma unroll
               for (int j = 0; j < 3; ++j) {
-                real l_ = lam3[j];
-                if (!eq) l_ = fmax(l_, 0.0);
+                const real l_ = cert_session_candidate<real>(lam3[j], eq);
                 real ph = 0;
 #pragma unroll
                 for (int c = 0; c < CT; ++c) {
                   const int tp = 16 * c + t;
-                  if (tp >= off && tp < off + len) {
-                    const real dv = vv[c] - l_;
-                    ph += ubv[c] * fmax(dv, 0.0) + lbv[c] * fmin(dv, 0.0);
-                  }
+                  if (tp >= off && tp < off + len) ph += cert_support_term<real>(ubv[c], lbv[c], vv[c] - l_);
                 }
                 ph = row_sum<real>(ph) + l_ * cap;
                 best = fmin(best, ph);
@@ -1358,10 +1342,10 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
           real stot = 0;
           for (int wv = 0; wv < kStreamWaves; ++wv) stot += RED0[wv];
           __syncthreads();
-          if (bd[0] == 0.0 && stot < -vtol) { status = 3; done = true; }
+          if (cert_verdict(bd[0], stot, vtol)) { status = 3; done = true; }
         }
       }
-      if (!done) {   // snapshot for the next certificate test (single precision: acn_qp_tiled.hpp)
+      if (!done) {   // snapshot for the next certificate test (single precision, as every kernel rounds it)
 #pragma unroll 1
         for (int tl = wave; tl < MT * CT; tl += kStreamWaves) {
           RELANE();
@@ -1378,21 +1362,19 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
         }
         have_prev = true;
       }
-      const real score = fmax(pri / fmax(eps_p, 1e-300), dua / fmax(eps_d, 1e-300));
-      if (score < kStallGain * best_score) { best_score = score; best_it = it; }
+      const real score = stall_score<real>(pri, dua, eps);
+      if (stall_improved<real>(score, best_score)) { best_score = score; best_it = it; }
       const bool inacc = inaccurate_ok<real>(pri, dua, npri, ndua, A.eps_abs, A.eps_rel, A.inacc_floor);
-      const bool stalled = A.stall_iters > 0 && it - best_it >= A.stall_iters && score <= kStallNear * best_score;   // acn_qp_tiled.hpp
+      const bool stalled = stall_reached<real>(A.stall_iters, it, best_it, score, best_score);
       if (done) {
       } else if (it >= max_iter_p || stalled) {
         done = true;
-        if (inacc) status = 5;
+        if (inacc) status = 5;   // solved, inaccurately
       } else if (adapt_p > 0 && it % adapt_p == 0) {
-        const real sp = pri / fmax(npri, 1e-12), sd = dua / fmax(ndua, 1e-12);
-        const real ratio = sqrt(sp / fmax(sd, 1e-30));
-        const real tol_eff = A.adapt_tol * (1.0 + (real)n_adapt * (1.0 / kAdaptWiden));
-        if (ratio > tol_eff || ratio < 1.0 / tol_eff) {
+        const real ratio = rho_ratio<real>(pri, dua, npri, ndua);
+        if (rho_outside_band(ratio, A.adapt_tol, n_adapt)) {
           ++n_adapt;
-          rho = uniform_scalar(fmin(fmax(rho * ratio, 1e-6), 1e6));
+          rho = uniform_scalar(rho_clamped<real>(rho * ratio));
           __syncthreads();     // every wave's stores of this pass are visible before the state is re-read
           rebuild_p();         // r0 depends on rho: P with the new penalty
           if (aa_m > 0) {      // the fixed-point map changed: restart the ring from the current (z, y)

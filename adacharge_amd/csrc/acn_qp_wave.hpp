@@ -33,7 +33,7 @@
 // Everything else stays with acn_qp_tiled.hpp / acn_qp_long.hpp (ACNQP_NO_WAVE=1, ACNQP_NO_WAVE2=1: the A/B switches of
 // tests/test_wave_kernel.py).
 #pragma once
-#include "acn_qp_tiled.hpp"
+#include "acn_qp_common.hpp"
 
 namespace acnqp {
 
@@ -976,11 +976,10 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
       dua = uniform_scalar(vm[1]);
       const real npri = uniform_scalar(vm[2]);
       const real ndua = fmax(uniform_scalar(vm[3]), qnorm);
-      const real eps_p = A.eps_abs + A.eps_rel * npri;
-      const real eps_d = A.eps_abs + A.eps_rel * ndua;
-      if (pri <= eps_p && dua <= eps_d) { status = 1; done = true; }
+      const CheckTol<real> eps = check_tolerances<real>(A.eps_abs, A.eps_rel, npri, ndua);
+      if (converged(pri, dua, eps)) { status = 1; done = true; }
       if (!done && have_prev) {
-        // ---- primal infeasibility certificate (acn_qp_tiled.hpp / oracle/admm_port.c) ----------------------------------
+        // ---- primal infeasibility certificate (acn_qp_check.hpp / oracle/admm_port.c) ----------------------------------
         real w0 = 0, w1 = 0;
         real dv1[TS], dv2[SR];
         {
@@ -1017,27 +1016,17 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
         pu_max(wm, 2);
         const real vn = uniform_scalar(wm[0]);
         const real atv = uniform_scalar(wm[1]);
-        const real vtol = scalar_const(1e-4) * vn;
-        if (vn > scalar_const(1e-12) * fmax(1.0, qnorm) && atv <= vtol) {
+        real vtol;
+        if (cert_gate<real, ScalarConst>(vn, atv, qnorm, vtol)) {
           real bad = 0, ssum = 0;
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
             int rty[4];
             row_types(m, rty);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const real v2_ = dv2[4 * m + r];
-              const int ty = rty[r];
-              if (ty == kRowBox) { ssum += RowLim[16 * m + M::rowof(g, r)] * fmax(v2_, 0.0); if (v2_ < -vtol) bad = 1; }
-              else if (ty == kRowPeak) {
-                if (pk_lane < BIGC) ssum += pk_lane * fmax(v2_, 0.0); else if (v2_ > vtol) bad = 1;
-                if (v2_ < -vtol) bad = 1;
-              } else if (ty == kRowSocRe) {
-                const real vi = dv2[4 * m + ((r + 1) & 3)];
-                ssum += RowLim[16 * m + M::rowof(g, r)] * sqrt(v2_ * v2_ + vi * vi);
-              } else if (ty == kRowSocIm) {
-              } else if (fabs(v2_) > vtol) bad = 1;   // free rows admit no ray
-            }
+            for (int r = 0; r < 4; ++r)
+              cert_row_ray<real>(rty[r], dv2[4 * m + r], dv2[4 * m + ((r + 1) & 3)],
+                                 cert_row_has_limit(rty[r]) ? RowLim[16 * m + M::rowof(g, r)] : 0.0, pk_lane, BIGC, vtol, ssum, bad);
           }
           {   // the lane's session: phi(l) = l cap + sum_t [ub (v_t - l)+ + lb (v_t - l)-] at l = min v, max v, 0
             real lmin = BIGC, lmax = -BIGC;
@@ -1049,15 +1038,11 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
             real ph3[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-              real l_ = lam3[j];
-              if (!eq) l_ = fmax(l_, 0.0);
+              const real l_ = cert_session_candidate<real>(lam3[j], eq);
               real ph = half == 0 ? l_ * scap : 0.0;   // (the cap term once per session)
 #pragma unroll
               for (int t = 0; t < TS; ++t)
-                if ((swm >> t) & 1u) {
-                  const real dv = dv1[t] - l_;
-                  ph += ubv[t] * fmax(dv, 0.0) + lbv[t] * fmin(dv, 0.0);
-                }
+                if ((swm >> t) & 1u) ph += cert_support_term<real>(ubv[t], lbv[t], dv1[t] - l_);
               ph3[j] = ph;
             }
             if constexpr (NPW >= 2) { real z_ = 0; pl_sum2(ph3[0], ph3[1]); pl_sum2(ph3[2], z_); }
@@ -1072,7 +1057,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
           pu_max(bm1, 1);
           const real stot = uniform_scalar(st1[0]);
           const real bmax = uniform_scalar(bm1[0]);
-          if (bmax == 0.0 && stot < -vtol) { status = 3; done = true; }
+          if (cert_verdict(bmax, stot, vtol)) { status = 3; done = true; }
         }
       }
       if (!done) {   // snapshot for the next certificate test (single precision, as the twin rounds it)
@@ -1089,36 +1074,28 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
         }
         have_prev = true;
       }
-      const real tiny_ = scalar_const(1e-300);
-      const real score = fmax(pri / fmax(eps_p, tiny_), dua / fmax(eps_d, tiny_));
-      if (score < scalar_const(kStallGain) * best_score) { best_score = uniform_scalar(score); best_it = it; }
+      const real score = stall_score<real, ScalarConst>(pri, dua, eps);
+      if (stall_improved<real, ScalarConst>(score, best_score)) { best_score = uniform_scalar(score); best_it = it; }
       const bool inacc = inaccurate_ok<real>(pri, dua, npri, ndua, A.eps_abs, A.eps_rel, A.inacc_floor);
-      const bool stalled = A.stall_iters > 0 && it - best_it >= A.stall_iters && score <= scalar_const(kStallNear) * best_score;
+      const bool stalled = stall_reached<real, ScalarConst>(A.stall_iters, it, best_it, score, best_score);
       bool hand_over = false;
       // hand-over to the polish: after polish_iters iterations -- or (polish_stall > 0: ACNQP_EARLY_HANDOVER=1, off by default)
       // from half of them on once the residual score has not improved by 10 % for polish_stall iterations
       const bool pol_due = A.polish_iters > 0 && (it >= A.polish_iters || (A.polish_stall > 0 && 2 * it >= A.polish_iters && it - best_it >= A.polish_stall));
       if (!done && pass == 0 && pol_due) {
-        // rows the polish's Schur system would have: one per tight box / peak row, two per tight disc
-        real cnt = 0;
-        const real ytol = scalar_const(1e-9) * fmax(1.0, qnorm);
+        real cnt = 0;   // rows the polish's Schur system would have (polish_row_weight)
+        const real ytol = polish_ytol<real, ScalarConst>(qnorm);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
           int rty[4];
           row_types(m, rty);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const real yr = y2[4 * m + r], yi = y2[4 * m + ((r + 1) & 3)];
-            const bool disc = rty[r] == kRowSocRe;
-            const real mag = disc ? sqrt(yr * yr + yi * yi) : yr;
-            const bool counts = (disc | (rty[r] == kRowBox) | (rty[r] == kRowPeak)) & (tc < TS) & (tb + tc < Tm) & (mag > ytol);
-            cnt += counts ? (disc ? 2.0 : 1.0) : 0.0;
-          }
+          for (int r = 0; r < 4; ++r) cnt += polish_row_weight<real>(rty[r], y2[4 * m + r], y2[4 * m + ((r + 1) & 3)], ytol, (tc < TS) & (tb + tc < Tm));
         }
         real c1[1] = {wave_sum<real>(cnt)};
         pu_sum(c1, 1);
         cnt = uniform_scalar(c1[0]);
-        hand_over = cnt + 8.0 <= (real)A.pol_rows;
+        hand_over = polish_fits(cnt, A.pol_rows);
       }
       if (done) {
       } else if (hand_over) {
@@ -1126,16 +1103,12 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
         done = true;
       } else if (it >= max_iter_p || stalled) {
         done = true;
-        if (inacc) status = 5;
+        if (inacc) status = 5;   // solved, inaccurately
       } else if (adapt_p > 0 && it % adapt_p == 0) {   // (inside the residual check only: once per check_every iterations)
-        const real e12_ = scalar_const(1e-12);
-        const real sp = pri / fmax(npri, e12_);
-        const real sd = dua / fmax(ndua, e12_);
-        const real ratio = sqrt(sp / fmax(sd, scalar_const(1e-30)));
-        const real tol_eff = A.adapt_tol * (1.0 + (real)n_adapt * (1.0 / kAdaptWiden));
-        if (ratio > tol_eff || ratio < 1.0 / tol_eff) {
+        const real ratio = rho_ratio<real, ScalarConst>(pri, dua, npri, ndua);
+        if (rho_outside_band(ratio, A.adapt_tol, n_adapt)) {
           ++n_adapt;
-          rho = uniform_scalar(fmin(fmax(rho * ratio, scalar_const(1e-6)), scalar_const(1e6)));
+          rho = uniform_scalar(rho_clamped<real, ScalarConst>(rho * ratio));
           a = sigma + pd + rho;
           inv_a = uniform_scalar(1.0 / a);
           inv_rho = uniform_scalar(1.0 / rho);

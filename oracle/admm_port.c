@@ -87,7 +87,7 @@ static void project_window(int L, const double* v, const double* lb, const doubl
 static const double kStartGain = 1e5;
 static const double kAdaptWiden = 8.0;   /* rho adaptation band: adapt_tol (1 + adaptations / kAdaptWiden) */
 static const int kAaPeriod = 5;
-/* stall rule of the device kernels (acn_qp_tiled.hpp): no 10 % improvement of max(pri / eps_pri, dua / eps_dua) for
+/* stall rule of the device kernels (acn_qp_check.hpp): no 10 % improvement of max(pri / eps_pri, dua / eps_dua) for
  * kStallIters iterations with the score within kStallNear of its best end the problem (SOLVED_INACCURATE if the
  * residuals are good enough for it, MAX_ITER otherwise) */
 static const double kStallGain = 0.9, kStallNear = 1.25;
@@ -173,7 +173,7 @@ static int solve_one(const port_site* S, const port_opts* O, int horizon, const 
     return 4;
   }
   double pd = pdiag_user;
-  /* Tikhonov floor: LP-like problems only (kRegResolve / effective_pdiag in acn_qp_tiled.hpp) */
+  /* Tikhonov floor: LP-like problems only (kRegResolve / effective_pdiag in acn_qp_common.hpp) */
   const int has_prox = (S->has_flat && lf > 0) || (S->has_max && dc > 0);
   if (ubmax > 0 && !has_prox && pdiag_user * ubmax <= 1e-6 * qnorm)
     pd = fmax(pd, O->reg_rel * qnorm / (ubmax * (double)(horizon > 1 ? horizon : 1)));
@@ -375,7 +375,7 @@ static int solve_one(const port_site* S, const port_opts* O, int horizon, const 
       const double npri = v2, ndua = fmax(fmax(v4, v5), qnorm);
       if (pri <= O->eps_abs + O->eps_rel * npri && dua <= O->eps_abs + O->eps_rel * ndua) { status = 1; done = 1; }
       if (!done && have_yprev) {
-        /* ---- primal infeasibility certificate, as the tiled kernel tests it (acn_qp_tiled.hpp): v = y - y(previous
+        /* ---- primal infeasibility certificate, as the device kernels test it (acn_qp_check.hpp): v = y - y(previous
          * check); if A'v ~ 0 and the support function of B x C at v is negative, no point of B x C solves A r = z. */
         double vn = 0, atv = 0;
         for (int i = 0; i < N; ++i)
@@ -504,7 +504,7 @@ int admm_port_solve_batch(const port_site* S, const port_opts* O, int B, const i
                           pri + b, dua + b, obj + b, warm_x ? warm_x + b * nv : 0,
                           warm_y ? warm_y + (size_t)b * S->Mg * S->Tm : 0, y_out ? y_out + (size_t)b * S->Mg * S->Tm : 0);
     int total = it, last_status = status[b], last_it = it;
-    /* retry passes of the device kernels (retry_wanted, acn_qp_tiled.hpp): a problem a pass leaves MAX_ITER /
+    /* retry passes of the device kernels (retry_wanted, acn_qp_common.hpp): a problem a pass leaves MAX_ITER /
      * SOLVED_INACCURATE after at least stall_iters (3000 if the rule is off) iterations is solved again from a cold
      * start with the fixed penalty retry_rho * 4^(pass - 1); the best pass is kept (SOLVED > SOLVED_INACCURATE >
      * MAX_ITER, the first of equals), iters is the total */

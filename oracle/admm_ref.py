@@ -54,7 +54,7 @@ class AdmmOptions:
 
 START_GAIN = 1e5
 ADAPT_WIDEN = 8.0
-STALL_GAIN, STALL_NEAR, STALL_ITERS = 0.9, 1.25, 3000   # the device kernels' stall rule (acn_qp_tiled.hpp)
+STALL_GAIN, STALL_NEAR, STALL_ITERS = 0.9, 1.25, 3000   # the device kernels' stall rule (acn_qp_check.hpp)
 AA_PERIOD, AA_REG, AA_SAFE, AA_DRIFT = 5, 1e-4, 1.2, 1e-3
 
 
@@ -259,7 +259,7 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
                     return dict(x=np.zeros((N, Tm)), status=ST_PRESOLVE_INFEASIBLE, iters=0,   # (include/acn_qp.h)
                                 pri_res=1e300, dua_res=1e300, obj=0.0, rho=opts.rho)
     pdiag = float(batch.pdiag[b])
-    # Tikhonov floor: LP-like problems only (kRegResolve / effective_pdiag in acn_qp_tiled.hpp)
+    # Tikhonov floor: LP-like problems only (kRegResolve / effective_pdiag in acn_qp_common.hpp)
     has_prox = float(batch.lf[b]) > 0 or (getattr(batch, "dc", None) is not None and float(batch.dc[b]) > 0)
     if ub.max() > 0 and not has_prox and pdiag * ub.max() <= 1e-6 * np.abs(q).max():
         pdiag = max(pdiag, opts.reg_rel * np.abs(q).max() / (ub.max() * max(1, T)))
@@ -338,7 +338,7 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
                 best_score, best_it = score, it
             ea, er = max(100 * opts.eps_abs, 1e-5), max(100 * opts.eps_rel, 1e-5)   # 100 x tolerance or cvxpy's OSQP default
             inacc = pri <= ea + er * npri and dua <= ea + er * ndua
-            # the device kernels' stall rule (acn_qp_tiled.hpp)
+            # the device kernels' stall rule (acn_qp_check.hpp)
             stalled = it - best_it >= STALL_ITERS and score <= STALL_NEAR * best_score
             if (it == opts.max_iter or stalled) and inacc:
                 status = ST_SOLVED_INACCURATE

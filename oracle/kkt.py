@@ -6,7 +6,7 @@ statement (``builder.ProblemBatch`` / ``SiteData``) alone.  numpy only; no solve
 
 Problem certified: the caller's problem with the Tikhonov floor the kernels add to LP-like problems,
 ``pd_eff = polish_ref.effective_pdiag(pdiag, reg_rel, |q_b|_inf, max_t max(lb, ub), T_b, has_prox)``
-(acn_qp_tiled.hpp::effective_pdiag: ``qnorm`` and ``ubmax`` over the whole padded problem -- padding adds zeros --,
+(acn_qp_common.hpp::effective_pdiag: ``qnorm`` and ``ubmax`` over the whole padded problem -- padding adds zeros --,
 ``ub`` raised to ``lb`` where it is below, the problem's own horizon ``T_b``).
 
 Multiplier conventions, confirmed against oracle/admm_ref.py and oracle/admm_port.c (``y2 = rho (zhat - z)`` of the

@@ -44,7 +44,7 @@ TANGENT_MIN = 1e-7      # a disc whose multiplier is below TANGENT_MIN max(1, |q
 
 
 def effective_pdiag(pd_user, reg_rel, qnorm, ubmax, horizon, has_prox=False):
-    """acn_qp_tiled.hpp::effective_pdiag (the Tikhonov floor of LP-like problems)"""
+    """acn_qp_common.hpp::effective_pdiag (the Tikhonov floor of LP-like problems)"""
     if has_prox or not ubmax > 0 or pd_user * ubmax > 1e-6 * qnorm:
         return pd_user
     return max(pd_user, reg_rel * qnorm / (ubmax * max(horizon, 1)))

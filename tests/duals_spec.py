@@ -22,7 +22,7 @@ RES_NAMES = ("stat", "energy", "site", "comp")
 
 
 def effective_pdiag(pd_user, reg_rel, qnorm, ubmax, horizon, has_prox):
-    """acn_qp_tiled.hpp::effective_pdiag"""
+    """acn_qp_common.hpp::effective_pdiag"""
     if has_prox or not ubmax > 0 or pd_user * ubmax > 1e-6 * qnorm:
         return pd_user
     return max(pd_user, reg_rel * qnorm / (ubmax * max(horizon, 1)))
