@@ -1,6 +1,7 @@
 // Host-side launchers of the four kernel families.  Each family is instantiated in its own translation unit
 // (acn_qp_tiled_ct1.hip, acn_qp_tiled_ct2.hip, acn_qp_stream.hip, acn_qp_long.hip, acn_qp_general.hip) so that
-// adacharge_amd/build.py compiles them in parallel; acn_qp_api.hip (the C ABI) only sees these declarations.
+// adacharge_amd/build.py compiles them in parallel; acn_qp_api.hip (the C ABI) only sees these declarations.  Which family
+// a shape runs is decided in acn_qp_route.hpp, not here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 #include "acn_qp_stream.hpp"
 #include "acn_qp_long.hpp"
 #include "acn_qp_polish.hpp"
+#include "acn_qp_route.hpp"
 
 namespace acnqp {
 
@@ -95,9 +97,7 @@ inline int launch_grid(Kern kern, int threads, size_t lds, const TiledArgs& a) {
 hipError_t launch_tiled_ct1(const TiledArgs& a, hipStream_t st);
 hipError_t launch_tiled_ct2(const TiledArgs& a, hipStream_t st);
 // wave-per-problem kernel (acn_qp_wave.hpp): N <= 64, one session slot, horizon <= 24 with one or two row tiles or 33 ... 48
-// with one; wave_shape says which variant a launch is routed to (0: none; by shape -- `batch` only for the diagnostic
-// ACNQP_WAVE_MIN_BATCH)
-int wave_shape(int N, int t_max, int k_sessions, int MR, bool has_max, int batch);
+// with one; wave_shape (acn_qp_route.hpp) says which variant a launch is routed to
 hipError_t launch_wave(const TiledArgs& a, hipStream_t st);
 int wave_accel_columns();   // Anderson columns compiled into it
 // large-site kernel (acn_qp_stream.hpp)

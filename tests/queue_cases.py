@@ -1,5 +1,5 @@
 """One launch of >= 768 problems per kernel family, solved through acnqp_solve_batch_device (ONE launch, so the queue
-order of acn_qp_api.hip engages).  Run as a script it solves one case under the environment it was started with
+order of acn_qp_api.hip, schedule_launch, engages).  Run as a script it solves one case under the environment it was started with
 (ACNQP_NO_ORDER=1: natural queue order; ACNQP_NO_QUEUE=1: the static one-workgroup-per-problem schedule) and saves the
 result: tests/test_gpu_parity.py::test_work_queue_and_launch_order_do_not_change_results compares the bits."""
 import os

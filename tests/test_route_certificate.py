@@ -156,6 +156,18 @@ def test_routes_cover_every_family_and_the_polish_solves():
 @pytest.mark.gpu
 @pytest.mark.parametrize("pinned", [True, False])
 def test_mixed_shape_pipelined_call_gives_each_batch_its_own_bits(pinned):
+    _mixed_shape_call(pinned, None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pinned", [True, False])
+def test_mixed_shape_pipelined_call_in_chunks_of_eight_gives_each_batch_its_own_bits(pinned, monkeypatch):
+    """... with ACNQP_CHUNK=8 (read at every call) for the pipelined call only: the batches differ in shape and in
+    want_y / warm start, so the call is not planned as a whole, and chunks also split inside a batch."""
+    _mixed_shape_call(pinned, monkeypatch)
+
+
+def _mixed_shape_call(pinned, chunked):
     """acnqp_solve_batches over batches that alternate padded shapes (so chunks split on the shape), with an empty batch,
     multiplier output on some and a warm start on one (chunks split on those too): each batch's bits equal its own
     solve() (the size-invariance rule, tests/test_batch_invariance.py)."""
@@ -170,7 +182,11 @@ def test_mixed_shape_pipelined_call_gives_each_batch_its_own_bits(pinned):
     want_y = [True, False, False, True, True, False, True]
     first = h.solve(batches[0], want_y=True)
     warm = [None] * 6 + [(first.x, first.y)]
+    if chunked is not None:
+        chunked.setenv("ACNQP_CHUNK", "8")
     many = h.solve_many(batches, pinned_results=pinned, want_y=want_y, warm=warm)
+    if chunked is not None:
+        chunked.delenv("ACNQP_CHUNK")
     assert many[1].x.shape[0] == 0
     for g, (batch, res) in enumerate(zip(batches, many)):
         if batch.B == 0:

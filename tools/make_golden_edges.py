@@ -1,7 +1,7 @@
 """Generates tests/golden/edges.npz: oracle-certified optima at the shape edges of every kernel route.
 
-The library picks one of its kernel families per launch by shape alone (wave_shape() in acn_qp_wave.hip; tiled_shape,
-lds_long_shape, stream_shape, long_shape and route_for in acn_qp_api.hip): cut points at N 64/65, horizons 12/13,
+The library picks one of its kernel families per launch by shape alone (wave_shape, tiled_shape, lds_long_shape,
+stream_shape, long_shape and route_for in acn_qp_route.hpp): cut points at N 64/65, horizons 12/13,
 16/17, 24/25, 32/33, 48/49 and 288/289, 16/32/48 padded site rows (SOC pads its 2M rows to 8 ceil(M/4)) and four
 session slots per EVSE.  Each case below sits on one side of such a cut and records the family it is written for;
 tests/test_golden_edges.py checks on the GPU that acnqp_route agrees, so that a later routing change cannot quietly
