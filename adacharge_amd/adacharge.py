@@ -168,14 +168,21 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
             station_id: rates_matrix[i, :] for i, station_id in enumerate(infrastructure.station_ids)
         }
 
-    def schedule_batch(self, session_lists, peak_limits=None, as_arrays=False):
+    def schedule_batch(self, session_lists, peak_limits=None, as_arrays=False, postprocess="host", first_period_only=False):
         """Batched extension: one schedule per state snapshot, every optimisation problem solved by one pipelined
         pass of the HIP library, and the steps either side of the solve -- the pre-processing of ada.py:141-150 and
         the post-processing of ada.py:176-189 -- done as array operations over the whole batch
         (session_table.py, postprocessing.*_batch).  ``session_lists``: a list of SessionInfo lists, or a
         ``SessionTable`` (no Python objects at all).  Returns one ``{station_id: ndarray}`` dict per snapshot
         (``{}`` for an empty one, ``None`` where the solve did not end optimal), or, with ``as_arrays=True``,
-        ``(rates (B, N, Tmax), status (B,))``."""
+        ``(rates (B, N, Tmax), status (B,))``.
+        ``postprocess="device"``: the three branches of ada.py:176-189 run on the GPU (``acnqp_pilots_device``) on the
+        copy of the schedules the solve also leaves in HBM (``acnqp_results.x_dev``; the solve still returns ``x`` to the
+        host as before), and the post-processing copies back only the pilots -- the bits of tests/pilots_spec.py, which
+        are the host path's wherever no decision of the reallocation sits within a rounding of its threshold.  A snapshot
+        whose round robin would never end (the reference's does not return on it) raises ``ValueError``.
+        ``first_period_only``: return -- and, on the device path, copy -- the first control period only: ``(B, N)``
+        arrays, or dicts of one-element arrays."""
         from . import session_table as st
         from .postprocessing import (
             diff_based_reallocation_batch,
@@ -211,11 +218,24 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
                 pl = [self.peak_limit[t : t + int(e)] for e in end]
         else:
             pl = [peak_limits[k] for k in nonempty]
-        res, batch = self._optimizer().solve_table(table, infrastructure, pl, self.interface.get_prev_peak())
+        if postprocess not in ("host", "device"):
+            raise ValueError('postprocess must be "host" or "device"')
+        on_device = postprocess == "device"
+        res, batch = self._optimizer().solve_table(table, infrastructure, pl, self.interface.get_prev_peak(), keep_on_device=on_device)
         from .adaptive_charging_optimization import warn_inaccurate
 
         warn_inaccurate(res.status, res.pri_res, res.dua_res)   # cvxpy's "Solution may be inaccurate" (aco.py:315-321)
-        if self.quantize:                                                           # ada.py:176-184
+        if on_device:
+            from .postprocessing import postprocess_batch_device, raise_if_endless
+
+            mode = ("reallocate" if self.reallocate else "discrete") if self.quantize else "continuous"
+            r, visits = postprocess_batch_device(res.x_dev, table, infrastructure, self.interface, mode, res.handle,
+                                                 first_period_only=first_period_only)
+            raise_if_endless(visits, table, infrastructure, self.interface, names=nonempty)
+            res.x_dev = None
+            if first_period_only:
+                r = r[:, :, None]
+        elif self.quantize:                                                         # ada.py:176-184
             if self.reallocate:
                 r = diff_based_reallocation_batch(res.x, table, infrastructure, self.interface)
             else:
@@ -223,18 +243,20 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         else:                                                                       # ada.py:185-188
             r = project_into_continuous_feasible_pilots_batch(res.x, infrastructure)
         r = np.maximum(r, 0)                                                        # ada.py:189
+        if first_period_only:
+            r = r[:, :, :1]
         if as_arrays:
             rates = np.zeros((B,) + r.shape[1:])
             rates[nonempty] = r
             status[nonempty] = res.status
-            return rates, status
+            return (rates[:, :, 0] if first_period_only else rates), status
         out = [{} for _ in range(B)]
         ids = infrastructure.station_ids
         for j, k in enumerate(nonempty):
             if res.status[j] not in (1, 5):   # OPTIMAL / OPTIMAL_INACCURATE, as aco.py:319
                 out[k] = None
             else:
-                rj = r[j, :, : int(batch.T[j])]
+                rj = r[j, :, : 1 if first_period_only else int(batch.T[j])]
                 out[k] = {sid: rj[i] for i, sid in enumerate(ids)}
         return out
 

@@ -366,12 +366,14 @@ class AdaptiveChargingOptimization:
         return rates[0]
 
     def solve_table(self, table, infrastructure, peak_limits=None, prev_peak=0, _defaults: Optional[dict] = None,
-                    warm_start=None):
+                    warm_start=None, keep_on_device: bool = False):
         """Batched solve of a ``session_table.SessionTable`` (every snapshot non-empty): the array-native entry --
         no Python loop over sessions anywhere on the path, and (round 4) no dense (B, N, T) problem array on the host
         either: the sessions go to the library as they are (``acnqp_solve_table``) and ``charging_rate_bounds`` /
         ``energy_constraints`` / the linear cost (aco.py:45-124, 200-218) take their array form on the device.
-        Returns ``(backend.BatchResult, builder.TablePlan)``; a warm start takes the dense entry (``plan.expand()``)."""
+        Returns ``(backend.BatchResult, builder.TablePlan)``; a warm start takes the dense entry (``plan.expand()``).
+        ``keep_on_device``: the schedules also stay in HBM (``BatchResult.x_dev``, a float64 tensor on the handle's GPU;
+        ``BatchResult.handle`` is the handle that owns it) for ``postprocessing.postprocess_batch_device``."""
         from . import backend
         from .builder import _bad_constraint_type, _objective_needs_flat, _objective_needs_max, plan_from_table
 
@@ -406,7 +408,17 @@ class AdaptiveChargingOptimization:
                     wx[b, :, :T], wy[b, :, :T] = x0[:, :T], y0[:, :T]
             res = handle.solve(batch, backend.default_options(**opts), warm=(wx, wy), want_y=True)
         else:
-            res = handle.solve_table(plan, backend.default_options(**opts), want_y=True)
+            x_dev = None
+            if keep_on_device:
+                import torch
+
+                x_dev = torch.empty((plan.B, plan.N, plan.Tm), dtype=torch.float64, device=torch.device("cuda", handle.device))
+            res = handle.solve_table(plan, backend.default_options(**opts), want_y=True, x_dev=x_dev)
+        if keep_on_device and res.x_dev is None:   # (the warm-started dense entry: upload its answer)
+            import torch
+
+            res.x_dev = torch.from_numpy(np.ascontiguousarray(res.x)).to(torch.device("cuda", handle.device))
+        res.handle = handle
         self.last_result = res
         return res, plan
 

@@ -104,6 +104,22 @@ class _Duals(C.Structure):
     _fields_ = [("mu", C.c_void_p), ("z", C.c_void_p), ("res", C.c_void_p)]
 
 
+class _PilotPlan(C.Structure):
+    """Mirror of ``acnqp_pilot_plan`` (include/acn_qp.h)."""
+
+    _fields_ = [(k, C.c_int32) for k in ("batch", "t_max", "n_evse", "n_infra", "n_levels", "n_sessions", "mode")] + [
+        (k, C.c_void_p) for k in ("cre", "cim", "limits", "max_pilot", "levels", "sess_seg", "s_evse", "s_arrived", "s_cap")]
+
+
+class _Pilots(C.Structure):
+    """Mirror of ``acnqp_pilots`` (include/acn_qp.h)."""
+
+    _fields_ = [("pilots", C.c_void_p), ("first", C.c_void_p), ("visits", C.c_void_p)]
+
+
+PILOTS_CONTINUOUS, PILOTS_DISCRETE, PILOTS_REALLOCATE = 0, 1, 2
+
+
 class Options(C.Structure):
     """Mirror of ``acnqp_options``; construct with ``default_options()``."""
 
@@ -152,6 +168,8 @@ EXPORTED_SYMBOLS = (
     "acnqp_route",
     "acnqp_duals_device",
     "acnqp_duals_host",
+    "acnqp_pilots_device",
+    "acnqp_pilots_host",
 )
 
 # kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
@@ -231,6 +249,10 @@ def load_library():
     lib.acnqp_duals_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(_Duals)]
     lib.acnqp_duals_host.restype = C.c_int
+    lib.acnqp_pilots_device.argtypes = [C.c_void_p, C.POINTER(_PilotPlan), C.c_void_p, C.POINTER(_Pilots), C.c_void_p]
+    lib.acnqp_pilots_device.restype = C.c_int
+    lib.acnqp_pilots_host.argtypes = [C.c_void_p, C.POINTER(_PilotPlan), C.c_void_p, C.POINTER(_Pilots)]
+    lib.acnqp_pilots_host.restype = C.c_int
     _lib = lib
     return lib
 
@@ -270,6 +292,8 @@ class BatchResult:
     kernel_ms: float = float("nan")   # sum of the HIP-event durations of the call's launches (chunks of the pipelined
                                       # entry overlap on the GPU: an upper bound of the time the GPU was busy)
     y: Optional[np.ndarray] = None   # (B, Mg, Tm) multipliers of the site rows (when asked for): warm_y of a later solve
+    x_dev: Optional[object] = None   # the device tensor (B, N, Tm) that also received x (acnqp_results.x_dev), when one was given
+    handle: Optional[object] = None  # the SiteHandle that solved it (set by AdaptiveChargingOptimization.solve_table)
 
 
 @dataclass
@@ -282,6 +306,46 @@ class DualResult:
     energy: np.ndarray   # (B,) worst energy-row violation / max(1, |cap|)
     site: np.ndarray     # (B,) worst site-row violation / max(1, limit)
     comp: np.ndarray     # (B,) worst multiplier x slack over the site rows (oracle-free KKT check, scaled as documented)
+
+
+@dataclass
+class PilotPlan:
+    """The arrays of ``acnqp_pilot_plan`` (include/acn_qp.h): numpy arrays for ``SiteHandle.pilots``, torch tensors on the
+    handle's GPU (``to_device``) for ``SiteHandle.pilots_device``.  ``postprocessing.pilot_plan_arrays`` builds one."""
+    mode: int
+    B: int
+    Tm: int
+    N: int
+    max_pilot: Optional[object] = None   # (N,)
+    levels: Optional[object] = None      # (N, L) ascending, padded with +inf
+    cre: Optional[object] = None         # (M, N)
+    cim: Optional[object] = None
+    limits: Optional[object] = None      # (M,)
+    sess_seg: Optional[object] = None    # (B + 1,) int32
+    s_evse: Optional[object] = None      # (S,) int32
+    s_arrived: Optional[object] = None   # (S,) uint8
+    s_cap: Optional[object] = None       # (S,)
+
+    _ARRAYS = ("cre", "cim", "limits", "max_pilot", "levels", "sess_seg", "s_evse", "s_arrived", "s_cap")
+
+    def to_device(self, device) -> "PilotPlan":
+        import torch
+
+        moved = {k: None if getattr(self, k) is None else torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
+                 for k in self._ARRAYS}
+        return PilotPlan(self.mode, self.B, self.Tm, self.N, **moved)
+
+    def _struct(self, batch=None, t_max=None) -> "_PilotPlan":
+        def ptr(a):
+            if a is None or (hasattr(a, "numel") and a.numel() == 0) or (isinstance(a, np.ndarray) and a.size == 0):
+                return None
+            return C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else _ptr(a)
+
+        M = 0 if self.cre is None else int(self.cre.shape[0])
+        L = 0 if self.levels is None else int(self.levels.shape[1])
+        S = 0 if self.s_evse is None else int(self.s_evse.shape[0])
+        return _PilotPlan(int(self.B if batch is None else batch), int(self.Tm if t_max is None else t_max), self.N, M, L, S,
+                          self.mode, *[ptr(getattr(self, k)) for k in self._ARRAYS])
 
 
 class _PinnedBlock:
@@ -423,11 +487,13 @@ class SiteHandle:
         return self._finish(batch, res)
 
     def solve_table(self, plan, options: Optional[Options] = None, pinned_results: bool = False, want_y: bool = False,
-                    out: Optional["BatchResult"] = None) -> "BatchResult":
+                    out: Optional["BatchResult"] = None, x_dev=None) -> "BatchResult":
         """acnqp_solve_table: a ``builder.TablePlan`` (sessions + one linear cost per horizon) in, schedules out; the
         dense (B, N, Tm) problem arrays are formed on the device.  Same results as ``solve(plan.expand())``.
         ``out``: a BatchResult of an earlier call of the same shape to write into (a service that solves every control
-        period keeps its -- pinned -- result arrays instead of allocating 85 MB per call)."""
+        period keeps its -- pinned -- result arrays instead of allocating 85 MB per call).  ``x_dev``: a float64 device tensor
+        (B, N, Tm) on the handle's GPU that also receives the schedules (acnqp_results.x_dev); it comes back as
+        ``BatchResult.x_dev``."""
         if plan.site is not self.site and (plan.site.N, plan.site.Mg, plan.site.cone) != (self.site.N, self.site.Mg, self.site.cone):
             raise ValueError("plan was built for another site")
         o = options if options is not None else default_options()
@@ -452,7 +518,10 @@ class SiteHandle:
             if want_y:
                 res.y = new((B, self.site.Mg, Tm))
         r = _Results(_ptr(res.x), _ptr(res.status), _ptr(res.iters), _ptr(res.pri_res), _ptr(res.dua_res), _ptr(res.obj),
-                     _ptr(res.y) if want_y else None, None)
+                     _ptr(res.y) if want_y else None, None if x_dev is None else C.c_void_p(x_dev.data_ptr()))
+        if x_dev is not None and (tuple(x_dev.shape) != (B, N, Tm) or not x_dev.is_contiguous() or x_dev.element_size() != 8):
+            raise ValueError(f"x_dev must be a contiguous float64 tensor of shape {(B, N, Tm)}")
+        res.x_dev = x_dev
         self.kernel_times()
         self._launches_seen = int(self._lib.acnqp_launch_count(self._h))
         _check(self._lib.acnqp_solve_table(self._h, C.byref(t), C.byref(o), C.byref(r)), "acnqp_solve_table")
@@ -569,6 +638,61 @@ class SiteHandle:
                                          C.c_void_p(dev.status.data_ptr()) if use_status else None, C.byref(d), C.c_void_p(stream)),
             "acnqp_duals_device",
         )
+
+    # -- pilot signals (acn_qp_pilots.hpp) ----------------------------------------------------------------------------
+    def pilots(self, plan: PilotPlan, x: np.ndarray, want_pilots: bool = True, want_first: bool = True):
+        """acnqp_pilots_host: the pilots of the schedules ``x`` (B, N, Tm) under ``plan`` (numpy arrays), computed on the
+        GPU.  Returns ``(pilots (B, N, Tm) or None, first (B, N) or None, visits (B,) int32)``."""
+        x = np.ascontiguousarray(x, np.float64)
+        if x.ndim != 3 or x.shape[1] != plan.N:
+            raise ValueError("x must have the shape (B, N, Tm) of the plan's site")
+        B, N, Tm = x.shape
+        pil = np.empty((B, N, Tm)) if want_pilots else None
+        first = np.empty((B, N)) if want_first else None
+        visits = np.empty(B, np.int32)
+        p = plan._struct(B, Tm)
+        out = _Pilots(_ptr(pil), _ptr(first), _ptr(visits))
+        _check(self._lib.acnqp_pilots_host(self._h, C.byref(p), _ptr(x), C.byref(out)), "acnqp_pilots_host")
+        return pil, first, visits
+
+    def pilots_device(self, plan: PilotPlan, x, pilots=None, first=None, visits=None, stream: int = 0) -> None:
+        """acnqp_pilots_device: the same on device memory -- ``plan`` from ``PilotPlan.to_device``, ``x`` (B, N, Tm) and the
+        outputs ``pilots`` (B, N, Tm), ``first`` (B, N) (float64) and ``visits`` (B,) (int32) torch tensors on the handle's
+        GPU; at least one of ``pilots`` / ``first``.  Asynchronous on ``stream``."""
+        import torch
+
+        here = torch.device("cuda", self.device)
+
+        def want(t, name, dtype, shape=None):
+            if t is None:
+                return
+            if not isinstance(t, torch.Tensor) or t.device != here or t.dtype != dtype or not t.is_contiguous() or (
+                    shape is not None and tuple(t.shape) != tuple(shape)):
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor on {here}" + ("" if shape is None else f" of shape {tuple(shape)}"))
+
+        want(x, "x", torch.float64)
+        if x.dim() != 3 or x.shape[1] != plan.N:
+            raise ValueError("x must have the shape (B, N, Tm) of the plan's site")
+        B, N, Tm = x.shape
+        want(pilots, "pilots", torch.float64, (B, N, Tm))
+        want(first, "first", torch.float64, (B, N))
+        want(visits, "visits", torch.int32, (B,))
+        M = 0 if plan.cre is None else int(plan.cre.shape[0])
+        L = 0 if plan.levels is None else int(plan.levels.shape[1])
+        want(plan.max_pilot, "plan.max_pilot", torch.float64, (N,))
+        want(plan.levels, "plan.levels", torch.float64, (N, L))
+        want(plan.cre, "plan.cre", torch.float64, (M, N))
+        want(plan.cim, "plan.cim", torch.float64, (M, N))
+        want(plan.limits, "plan.limits", torch.float64, (M,))
+        want(plan.sess_seg, "plan.sess_seg", torch.int32, (B + 1,))
+        S = 0 if plan.s_evse is None else int(plan.s_evse.shape[0])
+        want(plan.s_evse, "plan.s_evse", torch.int32, (S,))
+        want(plan.s_arrived, "plan.s_arrived", torch.uint8, (S,))
+        want(plan.s_cap, "plan.s_cap", torch.float64, (S,))
+        p = plan._struct(B, Tm)
+        dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        out = _Pilots(dp(pilots), dp(first), dp(visits))
+        _check(self._lib.acnqp_pilots_device(self._h, C.byref(p), dp(x), C.byref(out), C.c_void_p(stream)), "acnqp_pilots_device")
 
     def _kernel_ms_of_call(self) -> float:
         """Sum of the HIP-event durations of the launches since the previous ``kernel_times`` call; NaN when an event

@@ -14,6 +14,7 @@
 #include "acn_qp.h"
 #include "acn_qp_launch.hpp"
 #include "acn_qp_duals.hpp"
+#include "acn_qp_pilots.hpp"
 #include "acn_qp_site.hpp"
 
 namespace {
@@ -152,6 +153,7 @@ struct acnqp_handle {
   int cus = 0;   // compute units of the device (the work-queue launches size their grid from it)
   int32_t* pol_stats = nullptr;   // device counters of the polish kernel, summed over the handle's life (acnqp_polish_stats)
   DevBuf duals_stage;   // acnqp_duals_host: device staging of one chunk
+  DevBuf pilots_stage;  // acnqp_pilots_host: the plan and the device staging of one chunk
 };
 
 namespace {
@@ -324,6 +326,7 @@ void acnqp_destroy(acnqp_handle* h) {
   for (auto& ev : h->h2d_done) if (ev) (void)hipEventDestroy(ev);
   h->release_work();
   h->duals_stage.release();
+  h->pilots_stage.release();
   if (h->pol_stats) (void)hipFree(h->pol_stats);
   delete h;
 }
@@ -793,6 +796,105 @@ int acnqp_duals_host(acnqp_handle* h, const acnqp_problems* p, const acnqp_optio
     HIP_TRY(hipMemcpyAsync(out->mu + (size_t)lo * K * N, dev(MU), per[MU] * (size_t)nb, hipMemcpyDeviceToHost, st));
     if (out->z) HIP_TRY(hipMemcpyAsync(out->z + (size_t)lo * N * Tm, dev(Z), per[Z] * (size_t)nb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out->res + (size_t)lo * 4, dev(RES), per[RES] * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return ACNQP_OK;
+}
+
+// ---- pilot signals (acn_qp_pilots.hpp) --------------------------------------------------------------------------------
+static int check_pilots_args(const acnqp_handle* h, const acnqp_pilot_plan* pl, const double* x, const acnqp_pilots* out,
+                             const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!pl || !out) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  if (pl->n_evse != h->shape.N)
+    return fail(ACNQP_ERR_INVALID, w + ": n_evse is " + std::to_string(pl->n_evse) + ", the handle's site has " + std::to_string(h->shape.N));
+  if (pl->mode != ACNQP_PILOTS_CONTINUOUS && pl->mode != ACNQP_PILOTS_DISCRETE && pl->mode != ACNQP_PILOTS_REALLOCATE)
+    return fail(ACNQP_ERR_INVALID, w + ": mode must be ACNQP_PILOTS_CONTINUOUS, _DISCRETE or _REALLOCATE");
+  if (!out->pilots && !out->first) return fail(ACNQP_ERR_INVALID, w + ": no output requested (pilots and first are both null)");
+  if (pl->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (pl->batch == 0) return ACNQP_OK;
+  if (pl->t_max < 1 || pl->t_max > 4096) return fail(ACNQP_ERR_INVALID, w + ": t_max must be in [1, 4096]");
+  if (!x) return fail(ACNQP_ERR_INVALID, w + ": null x");
+  const size_t nx = (size_t)pl->batch * pl->n_evse * pl->t_max;
+  auto overlaps = [&](const double* p, size_t cnt) { return p && p < x + nx && x < p + cnt; };
+  if (overlaps(out->pilots, nx) || overlaps(out->first, (size_t)pl->batch * pl->n_evse))
+    return fail(ACNQP_ERR_INVALID, w + ": an output aliases x");
+  if (pl->mode == ACNQP_PILOTS_CONTINUOUS) {
+    if (!pl->max_pilot) return fail(ACNQP_ERR_INVALID, w + ": null max_pilot");
+    return ACNQP_OK;
+  }
+  if (pl->n_levels < 1 || pl->n_levels > 4096 || !pl->levels) return fail(ACNQP_ERR_INVALID, w + ": n_levels must be in [1, 4096] and levels given");
+  if (pl->mode == ACNQP_PILOTS_REALLOCATE) {
+    if (pl->n_infra < 0 || pl->n_infra > 63) return fail(ACNQP_ERR_INVALID, w + ": n_infra must be in [0, 63]");
+    if (pl->n_infra > 0 && (!pl->cre || !pl->cim || !pl->limits)) return fail(ACNQP_ERR_INVALID, w + ": null cre, cim or limits");
+    if (pl->n_sessions < 0 || !pl->sess_seg) return fail(ACNQP_ERR_INVALID, w + ": negative n_sessions or null sess_seg");
+    if (pl->n_sessions > 0 && (!pl->s_evse || !pl->s_arrived || !pl->s_cap)) return fail(ACNQP_ERR_INVALID, w + ": null session array");
+  }
+  return ACNQP_OK;
+}
+
+int acnqp_pilots_device(acnqp_handle* h, const acnqp_pilot_plan* pl, const double* x, acnqp_pilots* out, void* hip_stream) {
+  const int rc = check_pilots_args(h, pl, x, out, "acnqp_pilots_device");
+  if (rc != ACNQP_OK) return rc;
+  if (pl->batch == 0) return ACNQP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  acnqp::PilotsArgs a;
+  a.B = pl->batch; a.N = pl->n_evse; a.Tm = pl->t_max; a.M = pl->n_infra; a.L = pl->n_levels; a.mode = pl->mode;
+  if (a.mode != ACNQP_PILOTS_REALLOCATE) a.M = 0;
+  if (a.mode == ACNQP_PILOTS_CONTINUOUS) a.L = 0;
+  a.cre = pl->cre; a.cim = pl->cim; a.limits = pl->limits; a.max_pilot = pl->max_pilot; a.levels = pl->levels;
+  a.sess_seg = pl->sess_seg; a.s_evse = pl->s_evse; a.s_arrived = pl->s_arrived; a.s_cap = pl->s_cap;
+  a.x = x; a.pilots = out->pilots; a.first = out->first; a.visits = out->visits;
+  a.site_lds = a.levels_lds = 0;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_pilots(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("pilots kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_pilots_host(acnqp_handle* h, const acnqp_pilot_plan* pl, const double* x, acnqp_pilots* out) {
+  int rc = check_pilots_args(h, pl, x, out, "acnqp_pilots_host");
+  if (rc != ACNQP_OK) return rc;
+  if (pl->batch == 0) return ACNQP_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = h->slot[0].st;
+  const size_t B = (size_t)pl->batch, N = (size_t)pl->n_evse, Tm = (size_t)pl->t_max;
+  const bool disc = pl->mode != ACNQP_PILOTS_CONTINUOUS, re = pl->mode == ACNQP_PILOTS_REALLOCATE;
+  const size_t M = re ? (size_t)pl->n_infra : 0, L = disc ? (size_t)pl->n_levels : 0, S = re ? (size_t)pl->n_sessions : 0;
+  // the plan (whole, once), then one chunk of x and of the outputs; every array starts on a 256-byte line
+  enum { CRE, CIM, LIM, MAXP, LEV, SEG, SEV, SARR, SCAP, NPLAN, X = NPLAN, P, F, V, NARR };
+  const size_t plan_bytes[NPLAN] = {M * N * 8, M * N * 8, M * 8, disc ? 0 : N * 8, N * L * 8, re ? (B + 1) * 4 : 0, S * 4, S, S * 8};
+  const void* plan_src[NPLAN] = {pl->cre, pl->cim, pl->limits, pl->max_pilot, pl->levels, pl->sess_seg, pl->s_evse, pl->s_arrived, pl->s_cap};
+  const size_t per[NARR - NPLAN] = {N * Tm * 8, out->pilots ? N * Tm * 8 : 0, out->first ? N * 8 : 0, out->visits ? 4u : 0u};
+  size_t total = 0;
+  for (size_t b : per) total += b;
+  const size_t budget = (size_t)256 << 20;   // device staging of one chunk
+  const size_t chunk = std::max<size_t>(1, std::min<size_t>(B, budget / total));
+  size_t offs[NARR], need = 0;
+  for (int k = 0; k < NPLAN; ++k) { offs[k] = need; need += al256(plan_bytes[k]); }
+  for (int k = NPLAN; k < NARR; ++k) { offs[k] = need; need += al256(per[k - NPLAN] * chunk); }
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(h->pilots_stage.reserve(need));
+  char* base = static_cast<char*>(h->pilots_stage.p);
+  auto dev = [&](int k) -> void* { return (k < NPLAN ? plan_bytes[k] : per[k - NPLAN]) ? base + offs[k] : nullptr; };
+  for (int k = 0; k < NPLAN; ++k)
+    if (plan_bytes[k]) HIP_TRY(hipMemcpyAsync(dev(k), plan_src[k], plan_bytes[k], hipMemcpyHostToDevice, st));
+  for (size_t lo = 0; lo < B; lo += chunk) {
+    const size_t nb = std::min(chunk, B - lo);
+    HIP_TRY(hipMemcpyAsync(dev(X), x + lo * N * Tm, per[0] * nb, hipMemcpyHostToDevice, st));
+    acnqp_pilot_plan pc = *pl;
+    pc.batch = (int32_t)nb;
+    pc.cre = (const double*)dev(CRE); pc.cim = (const double*)dev(CIM); pc.limits = (const double*)dev(LIM);
+    pc.max_pilot = (const double*)dev(MAXP); pc.levels = (const double*)dev(LEV);
+    pc.sess_seg = re ? (const int32_t*)dev(SEG) + lo : nullptr;   // (absolute session indices: the session arrays stay whole)
+    pc.s_evse = (const int32_t*)dev(SEV); pc.s_arrived = (const uint8_t*)dev(SARR); pc.s_cap = (const double*)dev(SCAP);
+    acnqp_pilots oc{(double*)dev(P), (double*)dev(F), (int32_t*)dev(V)};
+    rc = acnqp_pilots_device(h, &pc, (const double*)dev(X), &oc, st);
+    if (rc != ACNQP_OK) return rc;
+    if (out->pilots) HIP_TRY(hipMemcpyAsync(out->pilots + lo * N * Tm, dev(P), per[1] * nb, hipMemcpyDeviceToHost, st));
+    if (out->first) HIP_TRY(hipMemcpyAsync(out->first + lo * N, dev(F), per[2] * nb, hipMemcpyDeviceToHost, st));
+    if (out->visits) HIP_TRY(hipMemcpyAsync(out->visits + lo, dev(V), per[3] * nb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   return ACNQP_OK;

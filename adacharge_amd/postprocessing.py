@@ -244,3 +244,91 @@ def diff_based_reallocation_batch(rates: np.ndarray, table, infrastructure, inte
         active[r_[~ok], i_[~ok]] = False
     rounded[:, :, 0] = col
     return rounded
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  The same three steps on the device (acnqp_pilots_device, include/acn_qp.h): the schedules of a batched solve stay
+#  in HBM and only the pilots -- or only their first period -- come back.  tests/pilots_spec.py is the contract.
+# ---------------------------------------------------------------------------------------------------------------
+PILOT_MODES = {"continuous": 0, "discrete": 1, "reallocate": 2}
+
+
+def pilot_plan_arrays(table, infrastructure, interface, mode, batch=None, t_max=1):
+    """The arrays of ``acnqp_pilot_plan`` as a ``backend.PilotPlan`` (numpy): the site in the SOC form of utils.py:5-12,
+    the level table, and -- for "reallocate" -- the sessions of ``table`` grouped by snapshot (order kept: it breaks ties
+    of the rounding loss) with the first-period cap of every arrived session, computed here exactly as
+    ``diff_based_reallocation_batch`` computes it."""
+    from .backend import PilotPlan
+
+    m = PILOT_MODES[mode] if isinstance(mode, str) else int(mode)
+    N = infrastructure.num_stations
+    B = int(batch if batch is not None else table.B)
+    plan = PilotPlan(mode=m, B=B, Tm=int(t_max), N=N, max_pilot=np.ascontiguousarray(infrastructure.max_pilot, float)[:N].copy())
+    if m == 0:
+        return plan
+    plan.levels = np.ascontiguousarray(_pilot_table(infrastructure))
+    if m == 1:
+        return plan
+    cm = infrastructure.constraint_matrix
+    if cm is not None and np.size(cm):
+        ph = np.deg2rad(infrastructure.phases)
+        plan.cre, plan.cim = np.ascontiguousarray(cm * np.cos(ph)), np.ascontiguousarray(cm * np.sin(ph))
+        plan.limits = np.ascontiguousarray(infrastructure.constraint_limits, float)
+    S = table.S
+    arrived = np.zeros(S, dtype=np.uint8)
+    cap = np.zeros(S)
+    here = np.flatnonzero((table.off == 0) & (np.diff(table.seg) > 0))
+    volt = np.asarray(infrastructure.voltages, float)
+    amp_periods = table.demand[here] * 1000.0 / volt[table.evse[here]] * 60.0 / interface.period
+    cap[here] = np.minimum(np.minimum(amp_periods, table.max_rates[table.seg[here]]), np.asarray(infrastructure.max_pilot, float)[table.evse[here]])
+    arrived[here] = 1
+    order = np.argsort(table.prob, kind="stable")
+    seg = np.zeros(B + 1, dtype=np.int32)
+    np.cumsum(np.bincount(table.prob, minlength=B), out=seg[1:])
+    plan.sess_seg = seg
+    plan.s_evse = np.ascontiguousarray(table.evse[order], np.int32)
+    plan.s_arrived = np.ascontiguousarray(arrived[order])
+    plan.s_cap = np.ascontiguousarray(cap[order])
+    return plan
+
+
+def postprocess_batch_device(x, table, infrastructure, interface, mode, handle, first_period_only=False, stream=0):
+    """ada.py:176-189 for the schedules ``x`` (B, N, Tm) of a batch through ``acnqp_pilots_device``: ``x`` a float64
+    torch tensor on the handle's GPU (``BatchResult.x_dev``: nothing of it is copied to the host) or a numpy array
+    (uploaded first).  ``mode``: "continuous", "discrete" or "reallocate"; ``table`` the SessionTable the batch was built
+    from (read by "reallocate" only).  Returns ``(pilots, visits)``: the pilots (B, N, Tm), or with
+    ``first_period_only`` their first period (B, N) -- the only array copied back -- and the visits of an active EVSE per
+    snapshot (-1: the round robin was stopped at its bound, ``acnqp_pilots`` in include/acn_qp.h)."""
+    import torch
+
+    dev = torch.device("cuda", handle.device)
+    xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)
+    if xt.dtype != torch.float64 or xt.dim() != 3 or not xt.is_contiguous() or xt.device != dev:
+        raise ValueError("x must be a contiguous float64 (B, N, Tm) array or tensor on the handle's GPU")
+    B, N, Tm = xt.shape
+    plan = pilot_plan_arrays(table, infrastructure, interface, mode, batch=B, t_max=Tm).to_device(dev)
+    out = torch.empty((B, N) if first_period_only else (B, N, Tm), dtype=torch.float64, device=dev)
+    visits = torch.empty(B, dtype=torch.int32, device=dev)
+    handle.pilots_device(plan, xt, pilots=None if first_period_only else out, first=out if first_period_only else None,
+                         visits=visits, stream=stream)
+    torch.cuda.synchronize(dev)
+    return out.cpu().numpy(), visits.cpu().numpy()
+
+
+def raise_if_endless(visits, table, infrastructure, interface, names=None):
+    """``ValueError`` for the first snapshot the device round robin stopped at its bound (``visits == -1``): an arrived
+    session whose cap lies above the last allowable pilot of its EVSE is raised to that pilot, never refused and never
+    retired -- post.py:189-258 does not return on it.  ``names[b]``: the caller's index of snapshot b."""
+    bad = np.flatnonzero(np.asarray(visits) < 0)
+    if len(bad) == 0:
+        return
+    b = int(bad[0])
+    plan = pilot_plan_arrays(table, infrastructure, interface, "reallocate")
+    last = np.where(np.isfinite(plan.levels), plan.levels, -np.inf).max(axis=1)
+    where = f"snapshot {b if names is None else int(names[b])}"
+    for s in range(int(plan.sess_seg[b]), int(plan.sess_seg[b + 1])):
+        i = int(plan.s_evse[s])
+        if plan.s_arrived[s] and plan.s_cap[s] > last[i]:
+            raise ValueError(f"{where}, EVSE {infrastructure.station_ids[i]}: allowable pilots end below the session's cap "
+                             f"({last[i]:g} A < {plan.s_cap[s]:g} A); the reallocation of the rounding loss would never end")
+    raise ValueError(f"{where}: allowable pilots end below the session's cap; the reallocation of the rounding loss would never end")

@@ -402,6 +402,61 @@ int acnqp_duals_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_opt
 int acnqp_duals_host(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x,
                      const double* y, const int32_t* status, acnqp_duals* out);
 
+/* ---- pilot signals (additive to ABI v10: new symbols only) -----------------------------------------------------------
+ * What the reference does to a solved schedule before it goes to the chargers (ada.py:176-189), for a whole batch:
+ *   CONTINUOUS  max(min(x, max_pilot_i), 0)
+ *   DISCRETE    max(floor_to_set(x, levels_i, eps = 0.05), 0) on every entry, padding periods included; floor_to_set is
+ *               the level pos - 1 with pos = #{k : levels_i[k] < x + 0.05} (the first level for pos = 0)
+ *   REALLOCATE  DISCRETE, then the round robin of post.py:189-258 on period 0 of every problem: with peak the sum of the
+ *               solved period 0, the sessions of the problem are visited cyclically in the stable order of the rounding
+ *               loss -(x - rounded) of their EVSE (an EVSE with two sessions is visited twice per cycle); a visit of an
+ *               active EVSE retires it when its pilot has reached its cap, else tries its next larger level (clipped at
+ *               the last finite one) and keeps it iff  sum_i trial_i <= peak,  next <= cap  and, for every row j,
+ *               re_j^2 + im_j^2 <= (limits_j + 1e-7)^2  with re_j = sum_i cre[j][i] trial_i (im_j likewise); a refused
+ *               trial retires the EVSE.  An EVSE is active, with cap s_cap[s], when a session s with s_arrived[s] sits
+ *               on it (the last such session counts).
+ * Every sum runs over the EVSEs in increasing order, every product and every sum rounded once (no fused multiply-add,
+ * no square root): tests/pilots_spec.py states the three modes in plain loops and the library returns its bits.  No
+ * atomics; a problem gives the same bits alone and at any position of any batch.  A problem makes at most
+ * n_evse * n_levels visits of an active EVSE; one that is still active then (an EVSE whose last level lies below its cap:
+ * the reference never returns on it) ends there with visits = -1.                                                      */
+#define ACNQP_PILOTS_CONTINUOUS 0
+#define ACNQP_PILOTS_DISCRETE 1
+#define ACNQP_PILOTS_REALLOCATE 2
+
+typedef struct {
+  int32_t batch, t_max, n_evse, n_infra, n_levels, n_sessions;
+  int32_t mode;               /* ACNQP_PILOTS_*                                                                    */
+  const double* cre;          /* [M*N] real part of the infrastructure rows: constraint_matrix * cos(phase)        */
+  const double* cim;          /* [M*N] imaginary part; both in the SOC form whatever the handle's cone, because
+                                 the reference's feasibility test (utils.py:5-12) always uses it                   */
+  const double* limits;       /* [M]                                                                                */
+  const double* max_pilot;    /* [N]   CONTINUOUS only                                                              */
+  const double* levels;       /* [N*L] allowable pilots per EVSE, ascending, padded with +inf (DISCRETE, REALLOCATE) */
+  const int32_t* sess_seg;    /* [B+1] problem b owns the sessions [sess_seg[b], sess_seg[b+1])   (REALLOCATE)      */
+  const int32_t* s_evse;      /* [S]   EVSE of the session; the order inside a problem breaks ties of the loss      */
+  const uint8_t* s_arrived;   /* [S]   1: arrival_offset == 0 and a non-empty window                                */
+  const double* s_cap;        /* [S]   min(remaining amp-periods, max_rates[0], max_pilot) of an arrived session    */
+} acnqp_pilot_plan;
+
+typedef struct {
+  double* pilots;    /* [B*N*Tm] or NULL                                                                            */
+  double* first;     /* [B*N]    or NULL: period 0 only (what goes to the chargers)                                 */
+  int32_t* visits;   /* [B]      or NULL: visits of an active EVSE the round robin made (0 in the other modes),
+                                 -1: stopped at the bound                                                           */
+} acnqp_pilots;
+
+/* acnqp_pilots_device -- every pointer in *plan and *out and x [B*N*Tm] is a device pointer on the handle's GPU;
+ * enqueued on `hip_stream`, returns without synchronising.  At least one of out->pilots / out->first is wanted, and no
+ * output may alias x.  A null handle, n_evse other than the handle's, a mode out of range or no output return
+ * ACNQP_ERR_INVALID with acnqp_last_error set, before any device work.                                              */
+int acnqp_pilots_device(acnqp_handle* h, const acnqp_pilot_plan* plan, const double* x, acnqp_pilots* out,
+                        void* hip_stream);
+
+/* acnqp_pilots_host -- the same with host pointers, synchronous; a large batch is processed in chunks.  Same bits as
+ * the device entry.                                                                                                  */
+int acnqp_pilots_host(acnqp_handle* h, const acnqp_pilot_plan* plan, const double* x, acnqp_pilots* out);
+
 #ifdef __cplusplus
 }
 #endif
