@@ -120,6 +120,25 @@ class _Pilots(C.Structure):
 PILOTS_CONTINUOUS, PILOTS_DISCRETE, PILOTS_REALLOCATE = 0, 1, 2
 
 
+class _AdvancePlan(C.Structure):
+    """Mirror of ``acnqp_advance_plan`` (include/acn_qp.h)."""
+
+    _fields_ = [(k, C.c_int32) for k in ("n_evse", "n_rows", "n_horizons", "step", "peak_len", "n_arrivals", "n_rates")] + [
+        ("done_tol", C.c_double), ("kw_per_amp", C.c_double), ("warm_arrival_gain", C.c_double)] + [
+        (k, C.c_void_p) for k in ("q_table", "h_scal", "h_row", "peak_series", "a_seg", "a_evse", "a_slot", "a_len", "a_cap",
+                                  "a_rate_seg", "a_min", "a_max")]
+
+
+class _Next(C.Structure):
+    """Mirror of ``acnqp_next`` (include/acn_qp.h)."""
+
+    _fields_ = [(k, C.c_void_p) for k in ("horizon", "lb", "ub", "q", "pdiag", "s_off", "s_len", "s_cap", "peak", "lf", "dc",
+                                          "dfloor", "warm_x", "warm_y")]
+
+
+ADVANCE_REFUSED, ADVANCE_NO_ROW, ADVANCE_BAD_SLOT = 1, 2, 4
+
+
 class Options(C.Structure):
     """Mirror of ``acnqp_options``; construct with ``default_options()``."""
 
@@ -170,6 +189,8 @@ EXPORTED_SYMBOLS = (
     "acnqp_duals_host",
     "acnqp_pilots_device",
     "acnqp_pilots_host",
+    "acnqp_advance_device",
+    "acnqp_advance_host",
 )
 
 # kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
@@ -253,6 +274,12 @@ def load_library():
     lib.acnqp_pilots_device.restype = C.c_int
     lib.acnqp_pilots_host.argtypes = [C.c_void_p, C.POINTER(_PilotPlan), C.c_void_p, C.POINTER(_Pilots)]
     lib.acnqp_pilots_host.restype = C.c_int
+    lib.acnqp_advance_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(_AdvancePlan), C.POINTER(_Next), C.c_void_p, C.c_void_p]
+    lib.acnqp_advance_device.restype = C.c_int
+    lib.acnqp_advance_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(_AdvancePlan), C.POINTER(_Next), C.c_void_p]
+    lib.acnqp_advance_host.restype = C.c_int
     _lib = lib
     return lib
 
@@ -346,6 +373,62 @@ class PilotPlan:
         S = 0 if self.s_evse is None else int(self.s_evse.shape[0])
         return _PilotPlan(int(self.B if batch is None else batch), int(self.Tm if t_max is None else t_max), self.N, M, L, S,
                           self.mode, *[ptr(getattr(self, k)) for k in self._ARRAYS])
+
+
+@dataclass
+class AdvancePlan:
+    """The arrays of ``acnqp_advance_plan`` (include/acn_qp.h): numpy arrays for ``SiteHandle.advance``, torch tensors on the
+    handle's GPU (``to_device``) for ``SiteHandle.advance_device``.  ``a_seg`` may hold one row of B + 1 entries per step
+    (``(steps, B + 1)``, absolute record indices): ``seg_row`` picks the step's.  ``rollout.FleetTable`` builds one."""
+    q_table: object                       # (H, N, Tm)
+    h_scal: object                        # (H, 3) pdiag, lf, dc
+    h_row: object                         # (Tm + 1,) int32
+    done_tol: float
+    kw_per_amp: float
+    peak_series: Optional[object] = None  # (B, P)
+    a_seg: Optional[object] = None        # (B + 1,) or (rows, B + 1) int32
+    a_evse: Optional[object] = None       # (A,) int32
+    a_slot: Optional[object] = None
+    a_len: Optional[object] = None
+    a_cap: Optional[object] = None        # (A,)
+    a_rate_seg: Optional[object] = None   # (A + 1,) int32
+    a_min: Optional[object] = None        # (R,)
+    a_max: Optional[object] = None
+    warm_arrival_gain: float = 0.0        # rule 9: != 0 starts an admitted session at -gain * q' instead of the shifted x
+
+    _ARRAYS = ("q_table", "h_scal", "h_row", "peak_series", "a_seg", "a_evse", "a_slot", "a_len", "a_cap", "a_rate_seg", "a_min", "a_max")
+    _INT = ("h_row", "a_seg", "a_evse", "a_slot", "a_len", "a_rate_seg")
+
+    def to_device(self, device) -> "AdvancePlan":
+        import torch
+
+        moved = {}
+        for k in self._ARRAYS:
+            a = getattr(self, k)
+            moved[k] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int32 if k in self._INT else np.float64)).to(device)
+        return AdvancePlan(done_tol=self.done_tol, kw_per_amp=self.kw_per_amp, warm_arrival_gain=self.warm_arrival_gain, **moved)
+
+    def _struct(self, N: int, Mg: int, step: int, seg_row: int = 0, keep=None) -> "_AdvancePlan":
+        def ptr(k, row=None):
+            a = getattr(self, k)
+            if a is None or (a.numel() if hasattr(a, "numel") else a.size) == 0:
+                return None
+            if row is not None and a.ndim == 2:
+                a = a[row]
+            if hasattr(a, "data_ptr"):
+                return C.c_void_p(a.data_ptr())
+            a = np.ascontiguousarray(a, np.int32 if k in self._INT else np.float64)
+            if keep is not None:
+                keep.append(a)
+            return _ptr(a)
+
+        A = 0 if self.a_evse is None else int(self.a_evse.shape[0])
+        R = 0 if self.a_min is None else int(self.a_min.shape[0])
+        P = 0 if self.peak_series is None else int(self.peak_series.shape[1])
+        return _AdvancePlan(int(N), int(Mg), int(self.q_table.shape[0]), int(step), P, A, R, float(self.done_tol), float(self.kw_per_amp),
+                            float(self.warm_arrival_gain),
+                            ptr("q_table"), ptr("h_scal"), ptr("h_row"), ptr("peak_series"), ptr("a_seg", seg_row) if A else None,
+                            ptr("a_evse"), ptr("a_slot"), ptr("a_len"), ptr("a_cap"), ptr("a_rate_seg"), ptr("a_min"), ptr("a_max"))
 
 
 class _PinnedBlock:
@@ -571,8 +654,16 @@ class SiteHandle:
         return run, results
 
     # -- device buffers (torch tensors or any object with data_ptr()) --------------
-    def solve_device(self, dev: "DeviceBatch", options: Optional[Options] = None, stream: int = 0) -> None:
+    def solve_device(self, dev: "DeviceBatch", options: Optional[Options] = None, stream: int = 0, warm_x=None, warm_y=None) -> None:
+        """acnqp_solve_batch_device on a ``DeviceBatch``; asynchronous on ``stream``.  ``warm_x`` (B, N, Tm) and ``warm_y``
+        (B, Mg, Tm): optional float64 device tensors of a warm start (both or neither; none = cold, NULL in the ABI)."""
         o = options if options is not None else default_options()
+        if (warm_x is None) != (warm_y is None):
+            raise ValueError("warm_x and warm_y go together (both or neither)")
+        if warm_x is not None and (tuple(warm_x.shape) != (dev.B, dev.N, dev.Tm) or tuple(warm_y.shape) != (dev.B, self.site.Mg, dev.Tm)
+                                   or not warm_x.is_contiguous() or not warm_y.is_contiguous()
+                                   or warm_x.element_size() != 8 or warm_y.element_size() != 8):
+            raise ValueError(f"warm start tensors must be contiguous float64 of shapes {(dev.B, dev.N, dev.Tm)} and {(dev.B, self.site.Mg, dev.Tm)}")
         p = _Problems(
             dev.B, dev.Tm, dev.K,
             dev.horizon.data_ptr(), dev.lb.data_ptr(), dev.ub.data_ptr(), dev.q.data_ptr(), dev.pdiag.data_ptr(),
@@ -581,7 +672,7 @@ class SiteHandle:
             dev.lf.data_ptr() if self.site.has_flat else None,
             dev.dc.data_ptr() if self.site.has_max else None,
             dev.dfloor.data_ptr() if self.site.has_max else None,
-            None, None,
+            None if warm_x is None else warm_x.data_ptr(), None if warm_y is None else warm_y.data_ptr(),
         )
         r = _Results(dev.x.data_ptr(), dev.status.data_ptr(), dev.iters.data_ptr(),
                      dev.pri_res.data_ptr(), dev.dua_res.data_ptr(), dev.obj.data_ptr(),
@@ -694,6 +785,64 @@ class SiteHandle:
         out = _Pilots(dp(pilots), dp(first), dp(visits))
         _check(self._lib.acnqp_pilots_device(self._h, C.byref(p), dp(x), C.byref(out), C.c_void_p(stream)), "acnqp_pilots_device")
 
+    # -- time passes (acn_qp_advance.hpp) -------------------------------------------------------------------------------
+    _NEXT = ("horizon", "lb", "ub", "q", "pdiag", "s_off", "s_len", "s_cap", "peak", "lf", "dc", "dfloor")
+
+    def advance(self, cur: dict, applied, plan: AdvancePlan, step: int, status=None, x=None, y=None, want_warm: bool = False,
+                seg_row: int = 0) -> dict:
+        """acnqp_advance_host: the next period's problems of the state ``cur`` -- a dict of numpy arrays ``lb, ub`` (B, N, Tm),
+        ``s_off, s_len, s_cap`` (B, K, N) and, on a site with a max row, ``dfloor`` (B,) -- after the pilots ``applied`` (B, N)
+        of period ``step``, under ``plan`` (numpy arrays).  Returns a dict of the same layout with ``horizon, q, pdiag, lf, dc,
+        peak, flags`` added and, with ``want_warm``, ``warm_x`` / ``warm_y`` shifted from ``x`` (B, N, Tm) / ``y`` (B, Mg, Tm)."""
+        f8 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
+        i4 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
+        lb, ub, off, ln, cap = f8(cur["lb"]), f8(cur["ub"]), i4(cur["s_off"]), i4(cur["s_len"]), f8(cur["s_cap"])
+        if lb.ndim != 3 or lb.shape[1] != self.site.N or ub.shape != lb.shape or off.ndim != 3 or off.shape != ln.shape or off.shape != cap.shape:
+            raise ValueError("cur needs lb, ub of shape (B, N, Tm) and s_off, s_len, s_cap of shape (B, K, N) for the handle's site")
+        B, N, Tm = lb.shape
+        K, Mg = off.shape[1], self.site.Mg
+        dfl = f8(cur.get("dfloor")) if self.site.has_max else None
+        app, stat, xs, ys = f8(applied), i4(status), f8(x) if want_warm else None, f8(y) if want_warm and Mg else None
+        out = dict(horizon=np.empty(B, np.int32), lb=np.empty((B, N, Tm)), ub=np.empty((B, N, Tm)), q=np.empty((B, N, Tm)),
+                   pdiag=np.empty(B), s_off=np.empty((B, K, N), np.int32), s_len=np.empty((B, K, N), np.int32), s_cap=np.empty((B, K, N)),
+                   peak=np.empty((B, Tm)) if self.site.has_peak else None, lf=np.empty(B) if self.site.has_flat else None,
+                   dc=np.empty(B) if self.site.has_max else None, dfloor=np.empty(B) if self.site.has_max else None,
+                   warm_x=np.empty((B, N, Tm)) if xs is not None else None, warm_y=np.empty((B, Mg, Tm)) if ys is not None else None)
+        flags = np.empty(B, np.int32)
+        p = _Problems(B, Tm, K, None, _ptr(lb), _ptr(ub), None, None, _ptr(off), _ptr(ln), _ptr(cap), None, None, None, None, _ptr(dfl), None, None)
+        keep = []
+        pl = plan._struct(N, Mg, step, seg_row, keep)
+        nx = _Next(*[_ptr(out[k]) for k in self._NEXT + ("warm_x", "warm_y")])
+        _check(self._lib.acnqp_advance_host(self._h, C.byref(p), _ptr(app), _ptr(stat), _ptr(xs), _ptr(ys), C.byref(pl), C.byref(nx),
+                                            _ptr(flags)), "acnqp_advance_host")
+        del keep
+        out["flags"] = flags
+        return {k: v for k, v in out.items() if v is not None}
+
+    def advance_device(self, cur: "DeviceBatch", nxt: "DeviceBatch", applied, plan: AdvancePlan, step: int, flags, use_status: bool = True,
+                       warm_x=None, warm_y=None, stream: int = 0, seg_row: int = 0) -> None:
+        """acnqp_advance_device: ``nxt`` (a second ``DeviceBatch`` of the same shape, e.g. ``DeviceBatch.empty``: the kernel
+        ping-pongs between two buffer sets, nothing may alias) receives the next period's problems of ``cur`` after the pilots
+        ``applied`` (B, N) of period ``step``; ``flags`` (B,) int32; ``plan`` from ``AdvancePlan.to_device``.  ``use_status``:
+        a problem ``cur.status`` does not call solved delivers nothing.  ``warm_x`` / ``warm_y``: optional device tensors that
+        receive ``cur.x`` / ``cur.y`` shifted by one period.  Asynchronous on ``stream``."""
+        if (cur.B, cur.N, cur.Tm, cur.K) != (nxt.B, nxt.N, nxt.Tm, nxt.K):
+            raise ValueError("cur and nxt must have the same shape (B, N, Tm, K)")
+        if warm_y is not None and cur.y is None:
+            raise ValueError("warm_y needs the site-row multipliers: DeviceBatch(..., want_y=True)")
+        if tuple(applied.shape) != (cur.B, cur.N) or applied.element_size() != 8 or not applied.is_contiguous():
+            raise ValueError(f"applied must be a contiguous float64 tensor of shape {(cur.B, cur.N)}")
+        if tuple(flags.shape) != (cur.B,) or flags.element_size() != 4 or not flags.is_contiguous():
+            raise ValueError(f"flags must be a contiguous int32 tensor of shape {(cur.B,)}")
+        dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        p = _Problems(cur.B, cur.Tm, cur.K, dp(cur.horizon), dp(cur.lb), dp(cur.ub), dp(cur.q), dp(cur.pdiag), dp(cur.s_off), dp(cur.s_len),
+                      dp(cur.s_cap), dp(cur.s_eq), dp(cur.peak), dp(cur.lf), dp(cur.dc), dp(cur.dfloor), None, None)
+        pl = plan._struct(cur.N, self.site.Mg, step, seg_row)
+        nx = _Next(*[dp(getattr(nxt, k)) for k in self._NEXT], dp(warm_x), dp(warm_y))
+        _check(self._lib.acnqp_advance_device(self._h, C.byref(p), dp(applied), dp(cur.status) if use_status else None,
+                                              dp(cur.x) if warm_x is not None else None, dp(cur.y) if warm_y is not None else None,
+                                              C.byref(pl), C.byref(nx), dp(flags), C.c_void_p(stream)), "acnqp_advance_device")
+
     def _kernel_ms_of_call(self) -> float:
         """Sum of the HIP-event durations of the launches since the previous ``kernel_times`` call; NaN when an event
         could not be read or when the call made more launches than the library's 64-entry event ring holds (the sum
@@ -774,3 +923,28 @@ class DeviceBatch:
         self.obj = torch.zeros(self.B, dtype=torch.float64, device=dev)
         # site-row multipliers (B, Mg, Tm) when wanted (acnqp_results.y), else None
         self.y = torch.zeros((self.B, batch.site.Mg, self.Tm), dtype=torch.float64, device=dev) if want_y else None
+
+    @classmethod
+    def empty(cls, site: SiteData, B: int, Tm: int, K: int, device, want_y: bool = False, s_eq: int = 0, dfloor: float = 0.0,
+              with_peak: Optional[bool] = None) -> "DeviceBatch":
+        """An empty state of shape (B, N, Tm, K) in HBM: no session in any slot, zero bounds and cost, horizon 1, no peak limit.
+        What ``SiteHandle.advance_device`` writes into, and -- with ``step = -1`` -- what a rollout starts from."""
+        import torch
+
+        dev = torch.device(device)
+        self = cls.__new__(cls)
+        self.B, self.N, self.Tm, self.K = int(B), site.N, int(Tm), int(K)
+        z = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
+        self.horizon = torch.ones(self.B, dtype=torch.int32, device=dev)
+        self.lb, self.ub, self.q = z((self.B, self.N, self.Tm)), z((self.B, self.N, self.Tm)), z((self.B, self.N, self.Tm))
+        self.pdiag, self.lf, self.dc = z(self.B), z(self.B), z(self.B)
+        self.dfloor = torch.full((self.B,), float(dfloor), dtype=torch.float64, device=dev)
+        self.s_off, self.s_len = z((self.B, self.K, self.N), torch.int32), z((self.B, self.K, self.N), torch.int32)
+        self.s_cap = z((self.B, self.K, self.N))
+        self.s_eq = torch.full((self.B,), int(s_eq), dtype=torch.uint8, device=dev)
+        self.peak = torch.full((self.B, self.Tm), float("inf"), dtype=torch.float64, device=dev) if (site.has_peak if with_peak is None else with_peak) else None
+        self.x = z((self.B, self.N, self.Tm))
+        self.status, self.iters = z(self.B, torch.int32), z(self.B, torch.int32)
+        self.pri_res, self.dua_res, self.obj = z(self.B), z(self.B), z(self.B)
+        self.y = z((self.B, site.Mg, self.Tm)) if want_y else None
+        return self

@@ -217,7 +217,7 @@ __device__ inline double rcp_small(float nf) {
 }
 
 // Anderson acceleration of the ADMM fixed-point map (restated in oracle/admm_port.c, see there)
-constexpr double kStartGain = 1e5;
+constexpr double kStartGain = 1e5;   // (adacharge_amd/rollout.py START_GAIN restates it: a warm start's arriving sessions)
 // Tikhonov floor (options.reg_rel) -- applied ONLY to problems whose own objective cannot select a unique point:
 // no prox row in use (load_flattening / demand_charge weights zero) and a quadratic the solver cannot resolve,
 // pdiag * max(ub) <= kRegResolve * |q|_inf (pure LPs; the reference's equal_share * 1e-12).  A strictly convex

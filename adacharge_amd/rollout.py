@@ -1,0 +1,250 @@
+"""Closed-loop rollout of a batch of MPC scenarios with the state resident in HBM.
+
+Every user of the reference runs it in a closed loop: each period the loop solves, sends the first-period pilots to the
+chargers, integrates the delivered energy and builds the next problem.  ``simulate`` runs that loop for B scenarios of one
+site on one stream -- ``acnqp_solve_batch_device -> acnqp_pilots_device -> acnqp_advance_device`` per period, no host
+synchronisation in between -- and copies pilots, statuses and flags back once at the end.
+
+``FleetTable`` is everything the loop needs that does not depend on what the solver answers, computed once for the whole
+run: the arrival records of every step (the layout of ``acnqp_advance_plan``), the linear cost and the scalars of every
+horizon 1 .. Tm (``builder.objective_terms``), and the peak-limit series.  This is online MPC as in the reference's closed
+loop: an EV becomes visible at its arrival step, so every EVSE carries one session at a time (K = 1).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import backend
+from .builder import _objective_needs_flat, _objective_needs_max, objective_terms
+
+
+START_GAIN = 1e5   # where a cold solve starts a session: Proj(-1e5 q) (kStartGain of the solver kernels, acn_qp_common.hpp)
+
+
+@dataclass
+class RolloutResult:
+    pilots: np.ndarray      # (steps, B, N) what went to the chargers
+    status: np.ndarray      # (steps, B) int32
+    iters: np.ndarray       # (steps, B) int32
+    flags: np.ndarray       # (steps, B) int32: flags of the advance that built the step's problems (0 = nothing refused)
+    delivered: List[np.ndarray]   # per scenario: kWh delivered to each EV of the fleet, in the fleet's order
+    x: Optional[np.ndarray] = None   # (steps, B, N, Tm) the solved schedules, when asked for
+
+
+class FleetTable:
+    """The EV records of B scenarios of one site, and what a rollout of ``steps`` periods from ``start_time`` precomputes
+    from them.  ``fleets[b]`` is a sequence of records (dicts) with ``station``, ``arrival``, ``departure`` (periods),
+    ``requested`` (kWh) and optionally ``min_rate`` / ``max_rate``: a scalar, or one value per period of the stay.
+    ``enforce_pilot_limit`` (time-invariant) is applied to the records here.  The objective must not depend on the clock
+    (one linear cost per horizon serves the whole run).  That is checked by evaluating the cost one period later on an
+    interface that keeps its clock in ``interface.data["current_time"]`` (this package's ``Interface``; the entry is put
+    back); behind any other interface only this package's clock-free components (quick_charge, equal_share, total_energy,
+    load_flattening, peak, demand_charge) are accepted.  Either way a cost that reads the clock (``tou_energy_cost``) is
+    refused.  An ``external_signal`` of ``load_flattening`` is the caller's fixed array: it is read from its first entry
+    at every step, as ``schedule`` reads it."""
+
+    def __init__(self, fleets: Sequence[Sequence[dict]], infrastructure, interface, objective, steps: int, start_time: int = 0,
+                 peak_limit=None, done_kwh: float = 1e-9, t_max: Optional[int] = None):
+        self.fleets = [list(f) for f in fleets]
+        self.objective, self.peak_limit = objective, peak_limit   # (simulate checks them against the algorithm's)
+        self.B, self.N = len(self.fleets), infrastructure.num_stations
+        self.steps, self.start = int(steps), int(start_time)
+        if self.B < 1 or self.steps < 1:
+            raise ValueError("a rollout needs at least one scenario and one step")
+        volt = np.asarray(infrastructure.voltages, float)
+        self.kwh_per_amp_period = volt * interface.period / 1e3 / 60          # aco.py:114
+        if np.any(volt != volt[0]):
+            raise ValueError("the rollout's demand-charge floor and done tolerance assume one voltage for the whole site")
+        self.kw_per_amp = float(volt[0] / 1000.0)
+        self.done_tol = float(done_kwh / self.kwh_per_amp_period[0])
+        max_pilot = np.asarray(infrastructure.max_pilot, float)
+        index = {s: i for i, s in enumerate(infrastructure.station_ids)}
+        recs = []   # (visible step, scenario, evse, len, cap, min rates, max rates, ev index)
+        self.windows = []   # per scenario: (evse, first step, end step) of every EV, relative to start (clipped to the run)
+        longest = 1
+        for b, fleet in enumerate(self.fleets):
+            wins, busy = [], {}
+            for n, ev in enumerate(fleet):
+                i = index[ev["station"]]
+                arr, dep = int(ev["arrival"]), int(ev["departure"])
+                tv = max(arr, self.start)
+                ln = dep - tv
+                wins.append((i, tv - self.start, dep - self.start))
+                cap = float(ev["requested"]) / self.kwh_per_amp_period[i]
+                if ln <= 0 or tv >= self.start + self.steps or cap <= self.done_tol:
+                    continue
+                for lo, hi in busy.get(i, ()):
+                    if tv < hi and lo < dep:
+                        raise ValueError(f"scenario {b}: two stays on EVSE {ev['station']} overlap; online MPC carries one session per EVSE")
+                busy.setdefault(i, []).append((tv, dep))
+                rates = []
+                for key, default in (("min_rate", 0.0), ("max_rate", np.inf)):
+                    r = ev.get(key, default)
+                    r = np.full(ln, float(r)) if np.isscalar(r) else np.asarray(r, float)[tv - arr: dep - arr]
+                    if len(r) != ln:
+                        raise ValueError(f"{key} of an EV needs one value per period of its stay")
+                    rates.append(r)
+                rates[1] = np.minimum(rates[1], max_pilot[i])                 # enforce_pilot_limit (ada.py:141)
+                if not np.all(np.isfinite(rates[1])):
+                    raise ValueError("max_rate must be finite (the site gives no max_pilot for this EVSE)")
+                recs.append((tv - self.start, b, i, ln, cap, rates[0], rates[1]))
+                longest = max(longest, ln)
+            self.windows.append(wins)
+        self.Tm = int(t_max) if t_max is not None else longest
+        if self.Tm < longest:
+            raise ValueError(f"t_max = {self.Tm} is shorter than the longest stay ({longest} periods)")
+        self.K = 1
+        recs.sort(key=lambda r: (r[0], r[1]))                                 # stable: record order inside (step, scenario)
+        A = len(recs)
+        key = np.array([r[0] * self.B + r[1] for r in recs], dtype=np.int64)
+        seg = np.searchsorted(key, np.arange(self.steps * self.B + 1)).astype(np.int32)
+        a_seg = np.empty((self.steps, self.B + 1), np.int32)                  # row s: the arrivals visible at step s, absolute
+        for s in range(self.steps):
+            a_seg[s] = seg[s * self.B: (s + 1) * self.B + 1]
+        lens = np.array([r[3] for r in recs], dtype=np.int32)
+        rate_seg = np.zeros(A + 1, np.int32)
+        np.cumsum(lens, out=rate_seg[1:])
+        cat = lambda k: np.concatenate([r[k] for r in recs]) if recs else np.zeros(0)
+        # ---- the objective, once per horizon (aco.py:200-218 depends on a problem only through T, aco.py:243-245) ----------
+        self.prev_peak = interface.get_prev_peak()
+        Tm, N = self.Tm, self.N
+        q_table, h_scal = np.zeros((Tm, N, Tm)), np.zeros((Tm, 3))
+        dfloor = 0.0
+        for T in range(1, Tm + 1):
+            q, pd, lf, _, dc, dfl = objective_terms(objective, infrastructure, interface, N, T, self.prev_peak)
+            q_table[T - 1, :, :T] = q
+            h_scal[T - 1] = pd, lf, dc
+            dfloor = dfl
+        self._refuse_clock_dependence(objective, infrastructure, interface, q_table[Tm - 1])
+        self.dfloor0 = float(dfloor)
+        self.need_flat, self.need_max = _objective_needs_flat(objective), _objective_needs_max(objective)
+        h_row = np.r_[-1, np.arange(Tm)].astype(np.int32)
+        # ---- the peak limit as a series over the run (ada.py:160-167: a scalar passes through, a vector is read from the clock)
+        self.has_peak = peak_limit is not None
+        series = None
+        if self.has_peak:
+            P = self.steps + Tm
+            if np.isscalar(peak_limit):
+                one = np.full(P, float(peak_limit))
+            else:
+                pl = np.asarray(peak_limit, float)[self.start: self.start + P]
+                one = np.full(P, np.inf)
+                one[: len(pl)] = pl
+            series = np.ascontiguousarray(np.broadcast_to(one, (self.B, P)))
+        self.plan = backend.AdvancePlan(
+            q_table=q_table, h_scal=h_scal, h_row=h_row, done_tol=self.done_tol, kw_per_amp=self.kw_per_amp, peak_series=series,
+            a_seg=a_seg, a_evse=np.array([r[2] for r in recs], np.int32), a_slot=np.zeros(A, np.int32), a_len=lens,
+            a_cap=np.array([r[4] for r in recs], np.float64), a_rate_seg=rate_seg, a_min=cat(5), a_max=cat(6))
+
+    def _refuse_clock_dependence(self, objective, infrastructure, interface, q_now):
+        data = getattr(interface, "data", None)
+        if not isinstance(data, dict):   # no clock to move: only components known not to read one
+            from . import adaptive_charging_optimization as aco
+
+            safe = (aco.quick_charge, aco.equal_share, aco.total_energy, aco.load_flattening, aco.peak, aco.demand_charge)
+            unknown = [getattr(c.function, "__name__", repr(c.function)) for c in objective if c.function not in safe]
+            if unknown:
+                raise ValueError(f"cannot tell whether the objective components {unknown} read the clock (the interface keeps no "
+                                 "data['current_time'] to move): the rollout keeps one linear cost per horizon")
+            return
+        had, old = "current_time" in data, data.get("current_time")
+        try:
+            data["current_time"] = (old or 0) + 1
+            q_later = objective_terms(objective, infrastructure, interface, self.N, self.Tm, self.prev_peak)[0]
+        finally:
+            if had:
+                data["current_time"] = old
+            else:
+                del data["current_time"]
+        if not np.array_equal(q_later, q_now[:, : self.Tm]):
+            raise ValueError("the objective depends on the clock (e.g. tou_energy_cost): the rollout keeps one linear cost per horizon")
+
+    def delivered(self, pilots: np.ndarray) -> List[np.ndarray]:
+        """kWh delivered to every EV by the applied ``pilots`` (steps, B, N): what the plant integrates, capped at the request."""
+        out = []
+        for b, fleet in enumerate(self.fleets):
+            d = np.zeros(len(fleet))
+            for n, (ev, (i, lo, hi)) in enumerate(zip(fleet, self.windows[b])):
+                lo, hi = max(lo, 0), min(hi, self.steps)
+                if hi > lo:
+                    d[n] = min(float(ev["requested"]), float(pilots[lo:hi, b, i].sum()) * self.kwh_per_amp_period[i])
+            out.append(d)
+        return out
+
+
+def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = False, return_schedules: bool = False,
+             observer=None) -> RolloutResult:
+    """``AdaptiveSchedulingAlgorithm.simulate_batch``: see there."""
+    import torch
+
+    from .adaptive_charging_optimization import _site_handle
+    from .postprocessing import pilot_plan_arrays
+
+    for on, why in ((alg.reallocate, "reallocate=True: the round robin breaks ties by session-list order, which the slot state does not carry"),
+                    (alg.estimate_max_rate, "estimate_max_rate: per-step pre-processing that reads the evolving state"),
+                    (alg.uninterrupted_charging, "uninterrupted_charging: per-step pre-processing that reads the evolving state")):
+        if on:
+            raise ValueError(f"simulate_batch does not serve {why}")
+    if alg.constraint_type not in ("SOC", "LINEAR"):
+        from .builder import _bad_constraint_type
+
+        _bad_constraint_type(alg.constraint_type)
+    interface = alg.interface
+    infra = interface.infrastructure_info()
+    table = fleets if isinstance(fleets, FleetTable) else FleetTable(fleets, infra, interface, alg.objective, steps, start_time, alg.peak_limit)
+    if (table.steps, table.start) != (int(steps), int(start_time)):
+        raise ValueError("the FleetTable was built for another run (steps, start_time)")
+    same_objective = len(table.objective) == len(alg.objective) and all(a is b or a == b for a, b in zip(table.objective, alg.objective))
+    same_peak = (table.peak_limit is None) == (alg.peak_limit is None) and (
+        table.peak_limit is None or np.array_equal(np.asarray(table.peak_limit, float), np.asarray(alg.peak_limit, float)))
+    if not same_objective or not same_peak:
+        raise ValueError("the FleetTable was built with another objective or peak_limit than the algorithm's")
+    site, handle = _site_handle(infra, alg.constraint_type, table.has_peak, alg.device, with_flat=table.need_flat, with_max=table.need_max)
+    opts = dict(alg.solver_options or {})
+    if not bool(opts.pop("retry_stalled", True)):
+        opts["retry_passes"] = 0
+    options = backend.default_options(**opts)
+    dev = torch.device("cuda", handle.device)
+    B, N, Tm, K = table.B, table.N, table.Tm, table.K
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        plan = table.plan.to_device(dev)
+        plan.warm_arrival_gain = START_GAIN if warm_start else 0.0
+        mode = "discrete" if alg.quantize else "continuous"
+        pplan = pilot_plan_arrays(None, infra, interface, mode, batch=B, t_max=Tm).to_device(dev)
+        s_eq = 1 if alg.enforce_energy_equality else 0
+        want_y = warm_start and site.Mg > 0
+        bufs = [backend.DeviceBatch.empty(site, B, Tm, K, dev, want_y=want_y, s_eq=s_eq, dfloor=table.dfloor0) for _ in range(2)]
+        pilots = torch.zeros((steps, B, N), dtype=torch.float64, device=dev)
+        status = torch.zeros((steps, B), dtype=torch.int32, device=dev)
+        iters = torch.zeros((steps, B), dtype=torch.int32, device=dev)
+        flags = torch.zeros((steps, B), dtype=torch.int32, device=dev)
+        xs = torch.zeros((steps, B, N, Tm), dtype=torch.float64, device=dev) if return_schedules else None
+        wx = torch.zeros((B, N, Tm), dtype=torch.float64, device=dev) if want_y else None
+        wy = torch.zeros((B, site.Mg, Tm), dtype=torch.float64, device=dev) if want_y else None
+        nothing = torch.zeros((B, N), dtype=torch.float64, device=dev)
+        # the first period's problems: time "passes" on an empty state, its arrivals are admitted
+        handle.advance_device(bufs[1], bufs[0], nothing, plan, -1, flags[0], use_status=False, stream=stream, seg_row=0)
+        for s in range(steps):
+            cur, nxt = bufs[s % 2], bufs[(s + 1) % 2]
+            warm = want_y and s > 0   # (a site without rows has no multipliers to carry: it starts cold)
+            handle.solve_device(cur, options, stream=stream, warm_x=wx if warm else None, warm_y=wy if warm else None)
+            handle.pilots_device(pplan, cur.x, first=pilots[s], stream=stream)
+            status[s].copy_(cur.status)
+            iters[s].copy_(cur.iters)
+            if xs is not None:
+                xs[s].copy_(cur.x)
+            if observer is not None:
+                observer(s, cur, pilots[s])
+            if s + 1 < steps:
+                handle.advance_device(cur, nxt, pilots[s], plan, s, flags[s + 1], use_status=True, warm_x=wx,
+                                      warm_y=wy, stream=stream, seg_row=s + 1)
+        torch.cuda.synchronize(dev)
+        p = pilots.cpu().numpy()
+        st = status.cpu().numpy()
+        p[~np.isin(st, backend.ACCEPTED_STATUSES)] = 0.0   # what the advance delivered for a step that did not solve: nothing
+        return RolloutResult(p, st, iters.cpu().numpy(), flags.cpu().numpy(), table.delivered(p),
+                             None if xs is None else xs.cpu().numpy())

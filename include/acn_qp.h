@@ -457,6 +457,104 @@ int acnqp_pilots_device(acnqp_handle* h, const acnqp_pilot_plan* plan, const dou
  * the device entry.                                                                                                  */
 int acnqp_pilots_host(acnqp_handle* h, const acnqp_pilot_plan* plan, const double* x, acnqp_pilots* out);
 
+/* ---- time passes (additive to ABI v10: new symbols only) --------------------------------------------------------------
+ * The fourth link of a closed MPC loop.  Every period the reference's users solve, send the first-period pilots to the
+ * chargers, integrate the delivered energy and build the next problem (aco.py:45-124, 200-245 on new SessionInfo lists).
+ * This entry does the last two for a whole batch: the problems `cur` just solved and the pilots `applied` in period 0
+ * in, the problems of the next period out, so that the state of a batch of simulations never leaves the GPU.  For
+ * every problem b, in this order (primes mark the output):
+ *    1  a_i = applied[b][i] if status is NULL or status[b] is SOLVED or SOLVED_INACCURATE, else a_i = 0: time passes and
+ *       nothing is delivered.
+ *    2  every slot (k, i) with s_len > 0:  if s_off > 0, off' = off - 1;  otherwise len' = len - 1 and
+ *       cap' = cap - a_i (one subtraction), then cap' = 0 if cap' < 0.  The slot is retired when len' == 0 or
+ *       cap' <= done_tol; a retired or empty slot gets off' = len' = 0 and cap' = 0.  (A slot whose window does not lie
+ *       inside [0, t_max) is no state of this shape: it is retired unread, with flag bit 4.)
+ *    3  lb'[i][t] = lb[i][t + 1] for t < t_max - 1 and 0 at t_max - 1; ub' likewise; both are then set to 0 on the
+ *       shifted window [off', off' + len') of every slot retired in rule 2.
+ *    4  the arrivals of b -- the records [a_seg[b], a_seg[b + 1]), each with offset 0 -- are admitted in record order,
+ *       serially per EVSE.  A record is refused with flag bit 1, and ignored, if its EVSE or slot is out of range, if
+ *       a_len < 1 or a_len > t_max, if its rate entries [a_rate_seg[r], a_rate_seg[r] + a_len) leave the rate arrays, if
+ *       its slot is live, or if [0, a_len) meets a live window of that EVSE.  Otherwise the slot becomes
+ *       (0, a_len, a_cap), lb'[i][0 : a_len] = a_min and ub'[i][0 : a_len] = (a_max < a_min ? a_min : a_max) (aco.py:75).
+ *    5  horizon' = max(1, max over the live slots of off' + len').
+ *    6  q'[b] = q_table[h_row[horizon']] and pdiag', lf', dc' = h_scal[h_row[horizon']]; a row outside [0, n_horizons)
+ *       sets flag bit 2 and writes q' and the three scalars as zeros.
+ *    7  peak'[t] = peak_series[b][step + 1 + t] for t < horizon' and +inf beyond (the builder's padding); all +inf when
+ *       peak_series is NULL.
+ *    8  dfloor' = max(dfloor, kw_per_amp * sum_i a_i): the sum in increasing i, every operation rounded once.
+ *    9  when wanted, warm_x'[i][t] = x[i][t + 1] and warm_y'[j][t] = y[j][t + 1] for t + 1 < t_max, 0 at the last period.
+ *       With warm_arrival_gain g != 0, warm_x' of a session admitted in rule 4 is (-g) * q'[i][t] on its window [0, a_len)
+ *       instead (one product): the point a cold solve starts that session from, before its projection on the bounds and
+ *       the energy row (the solver kernels use g = 1e5).  0 leaves the shifted x, which is 0 for an EVSE that was idle.
+ *   10  flags[b] is written for every problem, 0 when nothing was refused.
+ * s_eq does not change with time and is not written.  Copies, comparisons, one subtraction per served slot and one
+ * ordered sum per problem: tests/advance_spec.py states the rules in plain loops and the library returns its bits.  No
+ * atomics; every output element is written whatever the input; a problem gives the same bits alone and at any position
+ * of any batch.  step = -1 on an empty state (every s_len 0, applied 0) builds the first period's problems from their
+ * arrivals.                                                                                                            */
+#define ACNQP_ADVANCE_REFUSED 1   /* flags: an arrival record was refused (rule 4)                  */
+#define ACNQP_ADVANCE_NO_ROW 2    /* flags: no objective row for the new horizon (rule 6)           */
+#define ACNQP_ADVANCE_BAD_SLOT 4  /* flags: a slot of the current state lay outside [0, t_max)      */
+
+typedef struct {
+  int32_t n_evse;             /* N: must be the handle's                                                              */
+  int32_t n_rows;             /* rows of the handle's G (the rows of y)                                               */
+  int32_t n_horizons;         /* H: rows of q_table and h_scal                                                       */
+  int32_t step;               /* the period just completed (>= -1): rule 7 reads peak_series from step + 1           */
+  int32_t peak_len;           /* P >= step + 1 + t_max when peak_series is given                                      */
+  int32_t n_arrivals;         /* A: arrival records                                                                   */
+  int32_t n_rates;            /* R: entries of a_min / a_max                                                          */
+  double done_tol;            /* a slot with cap' <= done_tol is done (A-periods)                                     */
+  double kw_per_amp;          /* rule 8                                                                               */
+  double warm_arrival_gain;   /* rule 9; 0 = off                                                                      */
+  const double* q_table;      /* [H*N*Tm] linear cost per horizon (what objective_terms returns, zero-padded to Tm)   */
+  const double* h_scal;       /* [H*3]    pdiag, lf, dc per horizon                                                   */
+  const int32_t* h_row;       /* [Tm+1]   row of q_table / h_scal for a horizon, -1: none                            */
+  const double* peak_series;  /* [B*P] or NULL (a site without a peak row, or no limit)                              */
+  const int32_t* a_seg;       /* [B+1]    arrivals of problem b: [a_seg[b], a_seg[b+1]); NULL iff A == 0              */
+  const int32_t* a_evse;      /* [A]      the session records of acnqp_table, every offset 0                         */
+  const int32_t* a_slot;      /* [A]                                                                                  */
+  const int32_t* a_len;       /* [A]                                                                                  */
+  const double* a_cap;        /* [A]      A-periods                                                                   */
+  const int32_t* a_rate_seg;  /* [A+1]    rate entries of record r start at a_rate_seg[r]                             */
+  const double* a_min;        /* [R]                                                                                  */
+  const double* a_max;        /* [R]                                                                                  */
+} acnqp_advance_plan;
+
+/* The next period's problems: the arrays of acnqp_problems, writable.  None may alias its source in `cur` (or x, y). */
+typedef struct {
+  int32_t* horizon;  /* [B]                                                  */
+  double* lb;        /* [B*N*Tm]                                             */
+  double* ub;        /* [B*N*Tm]                                             */
+  double* q;         /* [B*N*Tm]                                             */
+  double* pdiag;     /* [B]                                                  */
+  int32_t* s_off;    /* [B*K*N]                                              */
+  int32_t* s_len;    /* [B*K*N]                                              */
+  double* s_cap;     /* [B*K*N]                                              */
+  double* peak;      /* [B*Tm]; required iff the site has a peak row         */
+  double* lf;        /* [B];    required iff the site has a flat row         */
+  double* dc;        /* [B];    required iff the site has a max row          */
+  double* dfloor;    /* [B];    required iff the site has a max row          */
+  double* warm_x;    /* [B*N*Tm] or NULL (not wanted)                        */
+  double* warm_y;    /* [B*n_rows*Tm] or NULL (not wanted)                   */
+} acnqp_next;
+
+/* acnqp_advance_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns
+ * without synchronising.  cur: batch, t_max, k_sessions and lb, ub, s_off, s_len, s_cap (dfloor on a site with a max
+ * row) are read; applied [B*N]; status [B] or NULL; x [B*N*Tm] and y [B*n_rows*Tm] are read only for next->warm_x /
+ * next->warm_y.  A null handle or argument, n_evse or n_rows other than the handle's, a site row without its array, a
+ * shape out of range, step < -1, a peak_len below step + 1 + t_max, or an output that overlaps an input or another
+ * output return ACNQP_ERR_INVALID with acnqp_last_error set, before any device work.                                 */
+int acnqp_advance_device(acnqp_handle* h, const acnqp_problems* cur, const double* applied, const int32_t* status,
+                         const double* x, const double* y, const acnqp_advance_plan* plan, acnqp_next* next,
+                         int32_t* flags, void* hip_stream);
+
+/* acnqp_advance_host -- the same with host pointers, synchronous; a large batch is processed in chunks.  Same bits as
+ * the device entry.                                                                                                  */
+int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* cur, const double* applied, const int32_t* status,
+                       const double* x, const double* y, const acnqp_advance_plan* plan, acnqp_next* next,
+                       int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif
