@@ -308,6 +308,11 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dptr(t):
+    """the device address of a torch tensor (None stays None)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 @dataclass
 class BatchResult:
     x: np.ndarray        # (B, N, Tm)
@@ -781,9 +786,8 @@ class SiteHandle:
         want(plan.s_arrived, "plan.s_arrived", torch.uint8, (S,))
         want(plan.s_cap, "plan.s_cap", torch.float64, (S,))
         p = plan._struct(B, Tm)
-        dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        out = _Pilots(dp(pilots), dp(first), dp(visits))
-        _check(self._lib.acnqp_pilots_device(self._h, C.byref(p), dp(x), C.byref(out), C.c_void_p(stream)), "acnqp_pilots_device")
+        out = _Pilots(_dptr(pilots), _dptr(first), _dptr(visits))
+        _check(self._lib.acnqp_pilots_device(self._h, C.byref(p), _dptr(x), C.byref(out), C.c_void_p(stream)), "acnqp_pilots_device")
 
     # -- time passes (acn_qp_advance.hpp) -------------------------------------------------------------------------------
     _NEXT = ("horizon", "lb", "ub", "q", "pdiag", "s_off", "s_len", "s_cap", "peak", "lf", "dc", "dfloor")
@@ -834,14 +838,13 @@ class SiteHandle:
             raise ValueError(f"applied must be a contiguous float64 tensor of shape {(cur.B, cur.N)}")
         if tuple(flags.shape) != (cur.B,) or flags.element_size() != 4 or not flags.is_contiguous():
             raise ValueError(f"flags must be a contiguous int32 tensor of shape {(cur.B,)}")
-        dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        p = _Problems(cur.B, cur.Tm, cur.K, dp(cur.horizon), dp(cur.lb), dp(cur.ub), dp(cur.q), dp(cur.pdiag), dp(cur.s_off), dp(cur.s_len),
-                      dp(cur.s_cap), dp(cur.s_eq), dp(cur.peak), dp(cur.lf), dp(cur.dc), dp(cur.dfloor), None, None)
+        p = _Problems(cur.B, cur.Tm, cur.K, _dptr(cur.horizon), _dptr(cur.lb), _dptr(cur.ub), _dptr(cur.q), _dptr(cur.pdiag), _dptr(cur.s_off),
+                      _dptr(cur.s_len), _dptr(cur.s_cap), _dptr(cur.s_eq), _dptr(cur.peak), _dptr(cur.lf), _dptr(cur.dc), _dptr(cur.dfloor), None, None)
         pl = plan._struct(cur.N, self.site.Mg, step, seg_row)
-        nx = _Next(*[dp(getattr(nxt, k)) for k in self._NEXT], dp(warm_x), dp(warm_y))
-        _check(self._lib.acnqp_advance_device(self._h, C.byref(p), dp(applied), dp(cur.status) if use_status else None,
-                                              dp(cur.x) if warm_x is not None else None, dp(cur.y) if warm_y is not None else None,
-                                              C.byref(pl), C.byref(nx), dp(flags), C.c_void_p(stream)), "acnqp_advance_device")
+        nx = _Next(*[_dptr(getattr(nxt, k)) for k in self._NEXT], _dptr(warm_x), _dptr(warm_y))
+        _check(self._lib.acnqp_advance_device(self._h, C.byref(p), _dptr(applied), _dptr(cur.status) if use_status else None,
+                                              _dptr(cur.x) if warm_x is not None else None, _dptr(cur.y) if warm_y is not None else None,
+                                              C.byref(pl), C.byref(nx), _dptr(flags), C.c_void_p(stream)), "acnqp_advance_device")
 
     def _kernel_ms_of_call(self) -> float:
         """Sum of the HIP-event durations of the launches since the previous ``kernel_times`` call; NaN when an event
