@@ -6,9 +6,11 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -334,6 +336,14 @@ void acnqp_destroy(acnqp_handle* h) {
   delete h;
 }
 
+// NaN by its bits: this file is compiled with -fno-honor-nans, under which `!(v >= 0)` is folded to `v < 0` and lets a
+// NaN option through the comparisons below.
+static bool is_nan(double v) {
+  uint64_t u;
+  std::memcpy(&u, &v, sizeof u);
+  return (u & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
+
 static int check_problem_shapes(const acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o,
                                 const acnqp_results* r) {
   if (!h || !p || !o || !r) return fail(ACNQP_ERR_INVALID, "acnqp_solve_batch: null argument");
@@ -352,6 +362,8 @@ static int check_problem_shapes(const acnqp_handle* h, const acnqp_problems* p, 
     return fail(ACNQP_ERR_INVALID, "acnqp_solve_batch: warm_x and warm_y must be given together");
   if (!r->x || !r->status || !r->iters || !r->pri_res || !r->dua_res || !r->obj)
     return fail(ACNQP_ERR_INVALID, "acnqp_solve_batch: null result array");
+  for (double v : {o->eps_abs, o->eps_rel, o->rho, o->sigma, o->alpha, o->adapt_tol, o->reg_rel, o->retry_rho, o->inaccurate_floor})
+    if (is_nan(v)) return fail(ACNQP_ERR_INVALID, "acnqp_solve_batch: invalid option value");
   if (!(o->eps_abs >= 0) || !(o->eps_rel >= 0) || o->max_iter < 1 || o->check_every < 1 || !(o->rho > 0) ||
       !(o->sigma >= 0) || !(o->alpha > 0 && o->alpha < 2) || !(o->adapt_tol > 1) || !(o->reg_rel >= 0) ||
       o->adapt_every < 0 || o->polish_iters < 0 || o->polish_stall < 0 || o->stall_iters < 0 || o->retry_passes < 0 || o->retry_passes > 8 || o->retry_max_iter < 1 ||

@@ -318,15 +318,27 @@ def route_shapes(h, batch):
     return out
 
 
-def launch_poisoned(h, batch, options=None):
-    """one launch through the device entry with every output poisoned (NaN, iters -1); returns host arrays"""
-    import torch
+def poisoned_device_batch(batch):
+    """a ``DeviceBatch`` of ``batch`` with every output poisoned: NaN in x, y, pri_res, dua_res and obj, -1 in iters and status"""
     from adacharge_amd.backend import DeviceBatch
 
     dev = DeviceBatch(batch, "cuda:0", want_y=True)
     for a in (dev.x, dev.y, dev.pri_res, dev.dua_res, dev.obj):
         a.fill_(float("nan"))
     dev.iters.fill_(-1)
+    dev.status.fill_(-1)
+    return dev
+
+
+def device_outputs(dev):
+    return {k: getattr(dev, k).cpu().numpy() for k in ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")}
+
+
+def launch_poisoned(h, batch, options=None):
+    """one launch through the device entry with every output poisoned (NaN, iters -1); returns host arrays"""
+    import torch
+
+    dev = poisoned_device_batch(batch)
     h.solve_device(dev, options, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    return {k: getattr(dev, k).cpu().numpy() for k in ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")}
+    return device_outputs(dev)
