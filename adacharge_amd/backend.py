@@ -866,6 +866,16 @@ class SiteHandle:
         out["phase_us"] = [int(v) // 100 for v in buf[8:16]]   # summed over the polish workgroups
         return out
 
+    def wave_rank(self) -> dict:
+        """The site's live eigenpairs, the MFMA k-steps that hold them once compacted, and the eigen extent (k-steps) of
+        the wave kernel's instantiation this handle runs (acnqp_debug_wave_rank: introspection, not part of the ABI)."""
+        buf = (C.c_int32 * 3)()
+        fn = self._lib.acnqp_debug_wave_rank
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
+        if fn(self._h, buf) != 0:
+            raise RuntimeError("acnqp_debug_wave_rank failed")
+        return dict(rank=int(buf[0]), eig_ksteps=int(buf[1]), extent=int(buf[2]))
+
     def ordered_launches(self) -> int:
         """Launches of this handle whose queue order was sorted by session count (acnqp_ordered_launch_count)."""
         return int(self._lib.acnqp_ordered_launch_count(self._h))

@@ -472,8 +472,19 @@ int reserve_workspace(acnqp_handle::Work* wk, const acnqp::Route& rt, hipStream_
   return ACNQP_OK;
 }
 
-hipError_t launch_solver(const acnqp::Route& rt, const acnqp::TiledArgs& aa, const Workspace& ws, hipStream_t st) {
-  if (rt.wv > 0) return acnqp::launch_wave(aa, st);
+// The eigen extent of the wave kernel's instantiation for this handle's site (acn_qp_rank.hpp; 0: the full one).
+// ACNQP_WAVE_FULL_RANK=1 (diagnostic, read once per process): the full extent for every site -- the kernel as it was.
+int wave_extent_of(const acnqp_handle* h) {
+  static const bool full_rank = std::getenv("ACNQP_WAVE_FULL_RANK") != nullptr;
+  return acnqp::wave_eig_extent(h->site.eig_ksteps, full_rank);
+}
+
+hipError_t launch_solver(const acnqp_handle* h, const acnqp::Route& rt, const acnqp::TiledArgs& aa, const Workspace& ws, hipStream_t st) {
+  if (rt.wv > 0) {
+    acnqp::WaveSite w;
+    w.Ghat = h->site.GhatW; w.lam = h->site.lamW; w.fragQ = h->site.fragQW; w.extent = wave_extent_of(h);
+    return acnqp::launch_wave(aa, w, st);
+  }
   if (rt.tiled) return rt.t_max <= 16 ? acnqp::launch_tiled_ct1(aa, st) : acnqp::launch_tiled_ct2(aa, st);
   if (rt.stream || rt.lng) {
     acnqp::StreamArgs sa;
@@ -521,7 +532,7 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   static const int early = std::getenv("ACNQP_EARLY_HANDOVER") ? std::atoi(std::getenv("ACNQP_EARLY_HANDOVER")) : 0;   // diagnostic: the window (1: polish_iters / 4)
   a1.polish_stall = early > 1 ? early : (early == 1 ? std::max(o->check_every, a1.polish_iters / 4) : o->polish_stall);
   a1.y_for_polish_only = r->y ? 0 : 1;
-  *e = launch_solver(rt, a1, ws, st);
+  *e = launch_solver(h, rt, a1, ws, st);
   if (*e == hipSuccess) {
     acnqp::PolishArgs pa;
     pa.B = p->batch; pa.N = s.N; pa.Tm = p->t_max; pa.K = p->k_sessions; pa.M = s.M; pa.Mg = s.Mg; pa.cone = s.cone;
@@ -544,7 +555,7 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
     a3.warm_x = r->x; a3.warm_y = ybuf;
     a3.ws_by_slot = 1; a3.grid_cap = std::min(p->batch, a.grid_oversub > 1 ? 64 : 2 * h->cus);   // (<= the grid the workspace was sized for)
     if (!a.ws_by_slot) a3.grid_cap = std::min(a3.grid_cap, a.grid_cap);
-    *e = launch_solver(rt, a3, ws, st);
+    *e = launch_solver(h, rt, a3, ws, st);
   }
   return ACNQP_OK;
 }
@@ -577,7 +588,7 @@ int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acn
   if (pol_blk >= 0) {
     if ((rc = launch_with_polish(h, wk, rt, a, ws, pol_blk, p, o, r, st, &e)) != ACNQP_OK) return rc;
   } else {
-    e = launch_solver(rt, a, ws, st);
+    e = launch_solver(h, rt, a, ws, st);
   }
   if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   HIP_TRY(hipEventRecord(h->ev_stop[evk], st));
@@ -612,6 +623,16 @@ int acnqp_polish_stats(acnqp_handle* h, int64_t* out, int32_t capacity) {
   HIP_TRY(hipMemcpy(v, h->pol_stats, sizeof(v), hipMemcpyDeviceToHost));
   for (int k = 0; k < capacity && k < 16; ++k) out[k] = v[k];
   return ACNQP_OK;
+}
+
+// Introspection outside include/acn_qp.h (every build): out[0] = live eigenpairs of the site's G G', out[1] = the MFMA
+// k-steps that hold them once compacted (acn_qp_rank.hpp), out[2] = the eigen extent in k-steps of the wave kernel's
+// instantiation this handle's launches run (the full one is MR / 4).  Returns 0, -1 without a handle.
+extern "C" int acnqp_debug_wave_rank(acnqp_handle* h, int32_t* out) {
+  if (!h || !out) return -1;
+  const int ext = wave_extent_of(h);
+  out[0] = h->site.rank; out[1] = h->site.eig_ksteps; out[2] = ext > 0 ? ext : h->shape.MR / 4;
+  return 0;
 }
 
 #ifdef ACNQP_DEBUG_WS

@@ -98,7 +98,10 @@ hipError_t launch_tiled_ct1(const TiledArgs& a, hipStream_t st);
 hipError_t launch_tiled_ct2(const TiledArgs& a, hipStream_t st);
 // wave-per-problem kernel (acn_qp_wave.hpp): N <= 64, one session slot, horizon <= 24 with one or two row tiles or 33 ... 48
 // with one; wave_shape (acn_qp_route.hpp) says which variant a launch is routed to
-hipError_t launch_wave(const TiledArgs& a, hipStream_t st);
+// ws: the site in the wave kernel's compacted eigenbasis (acn_qp_rank.hpp) and the eigen extent of the instantiation to
+// run -- 0: every k-step on a.Ghat / a.lam / a.fragQ as they are (the pointers of ws are then not read)
+struct WaveSite { const void *Ghat = nullptr, *lam = nullptr, *fragQ = nullptr; int extent = 0; };
+hipError_t launch_wave(const TiledArgs& a, const WaveSite& ws, hipStream_t st);
 int wave_accel_columns();   // Anderson columns compiled into it
 // large-site kernel (acn_qp_stream.hpp)
 hipError_t launch_stream(const StreamArgs& sa, hipStream_t st);

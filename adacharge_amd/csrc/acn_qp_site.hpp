@@ -11,6 +11,7 @@
 
 #include "acn_qp.h"
 #include "acn_qp_common.hpp"
+#include "acn_qp_rank.hpp"
 #include "acn_qp_route.hpp"
 
 namespace acnqp {
@@ -63,6 +64,9 @@ struct SiteDev {
   void *G = nullptr, *Ghat = nullptr, *Q = nullptr, *lam = nullptr, *rowlim = nullptr;
   void *fragG = nullptr, *fragQ = nullptr;   // Ghat / Q in MFMA A-operand fragment order (tiled kernel)
   void *fragG2 = nullptr, *fragQ2 = nullptr; // the same with the four k-slices of a fragment as two adjacent pairs per lane (long-horizon kernel)
+  // the wave kernel's own copies in the compacted eigenbasis (acn_qp_rank.hpp: live eigenpairs first); no other kernel reads them
+  void *GhatW = nullptr, *lamW = nullptr, *fragQW = nullptr;
+  int rank = 0, eig_ksteps = 0;  // live eigenpairs, and the MFMA k-steps that hold them once compacted
   int32_t* rowtype = nullptr;
   int32_t* rowabi = nullptr;     // internal row -> row of acnqp_site.G (-1: padding)
   void* rowscale = nullptr;      // equilibration factor of each internal row
@@ -71,7 +75,7 @@ struct SiteDev {
     if (Gabi) (void)hipFree(Gabi);
     if (limabi) (void)hipFree(limabi);
     Gabi = limabi = nullptr;
-    for (void** p : {&G, &Ghat, &Q, &lam, &rowlim, &fragG, &fragQ, &fragG2, &fragQ2, &rowscale}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    for (void** p : {&G, &Ghat, &Q, &lam, &rowlim, &fragG, &fragQ, &fragG2, &fragQ2, &rowscale, &GhatW, &lamW, &fragQW}) { if (*p) (void)hipFree(*p); *p = nullptr; }
     if (rowtype) (void)hipFree(rowtype);
     if (rowabi) (void)hipFree(rowabi);
     rowtype = nullptr; rowabi = nullptr;
@@ -164,27 +168,48 @@ inline int build_site_dev(const SiteShape* h, const std::vector<double>& G, cons
   // MFMA A-operand fragments in the order the tiled and the large-site kernel read them (one coalesced
   // 64-lane row per fragment register): see acn_qp_tiled.hpp / acn_qp_stream.hpp.  NP / 16 EVSE tiles.
   std::vector<double> fragG, fragQ;
-  {
-    const int NWv = NP / 16, MT = MR / 16;
-    fragG.assign((size_t)NWv * MT * 2 * 4 * 64, 0.0);
-    fragQ.assign((size_t)MT * MT * 2 * 4 * 64, 0.0);
+  const int NWv = NP / 16, MT = MR / 16;
+  auto frag_of_Q = [&](const std::vector<double>& Qm) {   // [mo][mi][0]: Q' (eigen tile mo x row tile mi), [..][1]: Q (row tile mo x eigen tile mi)
+    std::vector<double> f((size_t)MT * MT * 2 * 4 * 64, 0.0);
     for (int lane = 0; lane < 64; ++lane) {
       const int g = lane >> 4, t = lane & 15;
       for (int sI = 0; sI < 4; ++sI) {
         const int ro = acnqp::Mfma<double>::rowof(g, sI);
-        for (int m = 0; m < MT; ++m) {
+        for (int m = 0; m < MT; ++m)
+          for (int mi = 0; mi < MT; ++mi) {   // m plays the role of mo
+            f[((((size_t)m * MT + mi) * 2 + 0) * 4 + sI) * 64 + lane] = Qm[(size_t)(16 * mi + ro) * MR + 16 * m + t];
+            f[((((size_t)m * MT + mi) * 2 + 1) * 4 + sI) * 64 + lane] = Qm[(size_t)(16 * m + t) * MR + 16 * mi + ro];
+          }
+      }
+    }
+    return f;
+  };
+  {
+    fragG.assign((size_t)NWv * MT * 2 * 4 * 64, 0.0);
+    for (int lane = 0; lane < 64; ++lane) {
+      const int g = lane >> 4, t = lane & 15;
+      for (int sI = 0; sI < 4; ++sI) {
+        const int ro = acnqp::Mfma<double>::rowof(g, sI);
+        for (int m = 0; m < MT; ++m)
           for (int w = 0; w < NWv; ++w) {
             fragG[((((size_t)w * MT + m) * 2 + 0) * 4 + sI) * 64 + lane] = Gh[(size_t)(16 * m + t) * NP + 16 * w + ro];
             fragG[((((size_t)w * MT + m) * 2 + 1) * 4 + sI) * 64 + lane] = Gh[(size_t)(16 * m + ro) * NP + 16 * w + t];
           }
-          for (int mi = 0; mi < MT; ++mi) {   // m plays the role of mo
-            fragQ[((((size_t)m * MT + mi) * 2 + 0) * 4 + sI) * 64 + lane] = Q[(size_t)(16 * mi + ro) * MR + 16 * m + t];
-            fragQ[((((size_t)m * MT + mi) * 2 + 1) * 4 + sI) * 64 + lane] = Q[(size_t)(16 * m + t) * MR + 16 * mi + ro];
-          }
-        }
       }
     }
+    fragQ = frag_of_Q(Q);
   }
+  // the wave kernel's copies: eigenpair perm[k] in slot k (Ghat's rows, lam, Q's columns)
+  const EigRank er = eig_rank(lam);
+  std::vector<double> GhW((size_t)MR * NP), lamW(MR), QW((size_t)MR * MR);
+  for (int k = 0; k < MR; ++k) {
+    const int src = er.perm[k];
+    lamW[k] = lam[src];
+    for (int i = 0; i < NP; ++i) GhW[(size_t)k * NP + i] = Gh[(size_t)src * NP + i];
+    for (int r = 0; r < MR; ++r) QW[(size_t)r * MR + k] = Q[(size_t)r * MR + src];
+  }
+  d->rank = er.rank;
+  d->eig_ksteps = er.eig_ksteps;
   hipError_t e = up(&d->G, Gi);
   if (e == hipSuccess && !fragG.empty()) e = up(&d->fragG, fragG);
   if (e == hipSuccess && !fragQ.empty()) e = up(&d->fragQ, fragQ);
@@ -204,6 +229,9 @@ inline int build_site_dev(const SiteShape* h, const std::vector<double>& G, cons
   if (e == hipSuccess) e = up(&d->Ghat, Gh);
   if (e == hipSuccess) e = up(&d->Q, Q);
   if (e == hipSuccess) e = up(&d->lam, lam);
+  if (e == hipSuccess) e = up(&d->GhatW, GhW);
+  if (e == hipSuccess) e = up(&d->lamW, lamW);
+  if (e == hipSuccess) e = up(&d->fragQW, frag_of_Q(QW));
   if (e == hipSuccess) e = up(&d->rowlim, lim);
   if (e == hipSuccess) e = up(&d->rowscale, rs);
   if (e == hipSuccess) e = hipMalloc((void**)&d->rowtype, MR * sizeof(int32_t));

@@ -1,5 +1,6 @@
 // Wave-per-problem kernel (acn_qp_wave.hpp): instantiation and launcher.
 #include "acn_qp_launch.hpp"
+#include "acn_qp_rank.hpp"
 #include "acn_qp_wave.hpp"
 
 namespace acnqp {
@@ -7,13 +8,16 @@ namespace acnqp {
 // (which shapes come here: wave_shape, acn_qp_route.hpp; launch_wave below dispatches on the same cut points)
 static_assert(kRouteWaveTS == kWaveTS, "acn_qp_route.hpp restates the period slots per lane");
 
-template <int NPW, int TSV, int MT, bool PROX>
-static hipError_t launch_wave_prox(const TiledArgs& a_in, hipStream_t st) {
+// EK: the eigen extent of the instantiation (0: all k-steps, on the eigenbasis every kernel shares; otherwise the site's
+// arrays in the compacted eigenbasis replace them in this launch's copy of the arguments)
+template <int NPW, int TSV, int MT, bool PROX, int EK>
+static hipError_t launch_wave_prox(const TiledArgs& a_in, const WaveSite& ws, hipStream_t st) {
   TiledArgs a = a_in;
+  if (EK > 0) { a.Ghat = ws.Ghat; a.lam = ws.lam; a.fragQ = ws.fragQ; }
   a.accel_mem = std::min(a.accel_mem, kWaveAM);
   const WaveLds L(a.accel_mem, NPW, MT, TSV);
   const size_t lds = (size_t)L.total * 8;
-  auto kern = &admm_wave_kernel<kWaveAM, NPW, TSV, MT, PROX>;
+  auto kern = &admm_wave_kernel<kWaveAM, NPW, TSV, MT, PROX, EK>;
   if (lds > 64 * 1024) {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
@@ -40,17 +44,24 @@ static hipError_t launch_wave_prox(const TiledArgs& a_in, hipStream_t st) {
 }
 
 // (sites without a prox row run the instantiation that carries no prox code)
+template <int NPW, int TSV, int MT, int EK>
+static hipError_t launch_wave_ek(const TiledArgs& a, const WaveSite& ws, hipStream_t st) {
+  return a.lf != nullptr || a.dc != nullptr ? launch_wave_prox<NPW, TSV, MT, true, EK>(a, ws, st) : launch_wave_prox<NPW, TSV, MT, false, EK>(a, ws, st);
+}
+// (the eigen extent: wave_eig_extent, acn_qp_rank.hpp -- a function of the site, decided once at acnqp_create)
 template <int NPW, int TSV, int MT>
-static hipError_t launch_wave_npw(const TiledArgs& a, hipStream_t st) {
-  return a.lf != nullptr || a.dc != nullptr ? launch_wave_prox<NPW, TSV, MT, true>(a, st) : launch_wave_prox<NPW, TSV, MT, false>(a, st);
+static hipError_t launch_wave_npw(const TiledArgs& a, const WaveSite& ws, hipStream_t st) {
+  if (ws.extent == kWaveExtentSmall) return launch_wave_ek<NPW, TSV, MT, kWaveExtentSmall>(a, ws, st);
+  if (ws.extent == kWaveExtentMid) return launch_wave_ek<NPW, TSV, MT, kWaveExtentMid>(a, ws, st);
+  return launch_wave_ek<NPW, TSV, MT, 0>(a, ws, st);
 }
 
 int wave_accel_columns() { return kWaveAM; }
 
-hipError_t launch_wave(const TiledArgs& a, hipStream_t st) {
-  if (a.MR == 32) return a.Tm <= kWaveTS ? launch_wave_npw<2, 6, 2>(a, st) : launch_wave_npw<4, 6, 2>(a, st);
-  if (a.Tm > 2 * kWaveTS) return launch_wave_npw<4, 12, 1>(a, st);
-  return a.Tm <= kWaveTS ? launch_wave_npw<1, 12, 1>(a, st) : launch_wave_npw<2, 12, 1>(a, st);
+hipError_t launch_wave(const TiledArgs& a, const WaveSite& ws, hipStream_t st) {
+  if (a.MR == 32) return a.Tm <= kWaveTS ? launch_wave_npw<2, 6, 2>(a, ws, st) : launch_wave_npw<4, 6, 2>(a, ws, st);
+  if (a.Tm > 2 * kWaveTS) return launch_wave_npw<4, 12, 1>(a, ws, st);
+  return a.Tm <= kWaveTS ? launch_wave_npw<1, 12, 1>(a, ws, st) : launch_wave_npw<2, 12, 1>(a, ws, st);
 }
 
 }  // namespace acnqp

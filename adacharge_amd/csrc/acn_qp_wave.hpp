@@ -32,7 +32,16 @@
 //   <5, 4, 12, 1>  horizon 33 ... 48, <= 16 site rows        four waves of twelve periods: one problem per workgroup
 // Everything else stays with acn_qp_tiled.hpp / acn_qp_long.hpp (ACNQP_NO_WAVE=1, ACNQP_NO_WAVE2=1: the A/B switches of
 // tests/test_wave_kernel.py).
+//
+// The eigen extent EK (a sixth template argument; acn_qp_rank.hpp): the sites are rank-deficient (caltech54 SOC: 7 live
+// eigenpairs of 16 padded rows), and a null eigen-row contributes exact zeros to every product.  With the live
+// eigenpairs compacted to the front, EK = 2 or 3 runs the eigen-side chains over the live k-steps only -- corr 4 EK
+// MFMA instead of 16 per row tile, Q h^ EK instead of 4, and ONE eigen tile on the two-row-tile variants (P 16 instead of
+// 32, w^ 8 instead of 16) -- the same bits as EK = 0, the full extent on the eigenbasis the other kernels share
+// (ACNQP_WAVE_FULL_RANK=1: the A/B switch of tests/test_wave_rank_gpu.py).  The counts above are the full extent's.
 #pragma once
+#include <type_traits>
+
 #include "acn_qp_common.hpp"
 
 namespace acnqp {
@@ -91,7 +100,7 @@ __device__ inline void wave_lds_sync() {   // this wave's LDS writes are visible
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int AM, int NPW, int TSV, int MT, bool PROX>
+template <int AM, int NPW, int TSV, int MT, bool PROX, int EK = 0>
 __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledArgs A_kernarg) {
   static_assert(NPW == 1 || NPW == 2 || NPW == 4, "one, two or four waves per problem");
   static_assert((TSV == 12 && MT == 1) || (TSV == 6 && MT == 2 && NPW >= 2), "instantiated: 12 periods x one row tile, 6 periods x two row tiles");
@@ -99,7 +108,14 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
   using vec4 = typename M::vec4;
   typedef double real;
   constexpr int TS = TSV, XS = TSV > 8 ? kWaveXS : 9, XC = TSV > 8 ? 16 : 8;   // period slots, scratch stride, its live columns
-  constexpr int SR = 4 * MT, KS = 4 * MT;                                         // site-row registers per lane, k-steps of corr
+  constexpr int SR = 4 * MT, KS = 4 * MT;                                         // site-row registers per lane, k-steps of a row-side product
+  // The eigen side: EK > 0 = the site's live eigenpairs sit in the first EK k-steps (four eigen-rows each) of a compacted
+  // eigenbasis (acn_qp_rank.hpp; launch_wave hands over Ghat, lam and fragQ in that basis) and the rest are null rows --
+  // lam = 0, Ghat row = 0, so g0 = h^ = 0 there and e^ meets only zeros: their k-steps and tiles are not computed.
+  // Compile-time extents, everything still fully unrolled: no branch inside a chain.  EK = 0: every k-step (as ever).
+  constexpr int EKS = EK > 0 ? EK : KS, ET = (EKS + 3) / 4;                        // live eigen k-steps, eigen tiles
+  static_assert(EKS <= KS, "eigen extent");
+#define EKOF(m) (EKS - 4 * (m) < 4 ? EKS - 4 * (m) : 4)                            /* live k-steps of eigen tile m (= its live C-layout registers) */
 #define BIGC (scalar_const(1e300))
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   real* sm = reinterpret_cast<real*>(smem_raw);
@@ -291,7 +307,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
 
   // ---- layout changes through the wave's scratch -----------------------------------------------------------------------
   // EVSE layout (lane = EVSE, register = period) -> C-layout tile (rows x periods) of Amat v, Amat given as A fragments
-  auto evse_to_rows = [&](const real (&v)[TS], const real* frag, vec4 (&out)[MT]) __attribute__((always_inline)) {
+  auto evse_to_rows = [&](const real (&v)[TS], const real* frag, vec4 (&out)[MT]) __attribute__((always_inline)) {   // (the first ET tiles: Amat = Ghat)
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int t = 0; t < TS; ++t) XT[lane * XS + t] = v[t];
@@ -305,7 +321,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
       else bop[s] = tc < XC ? XT[(4 * s + g) * XS + (tc < XC ? tc : 0)] : 0.0;   // (the scratch holds 8 period columns)
     }
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
+    for (int m = 0; m < ET; ++m) {
       real aop[16];
 #pragma unroll
       for (int s = 0; s < 16; ++s) aop[s] = frag[(m * 16 + s) * 64 + lane];
@@ -319,17 +335,19 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     }
   };
   // C-layout tiles c4 (rows x periods) -> EVSE layout of Bmat' c4, Bmat (rows x EVSEs) given by bfrag(tile, k-step)
-  auto rows_to_evse = [&](const vec4 (&c4)[MT], auto&& bfrag, real (&out)[TS]) __attribute__((always_inline)) {
-    real bf[4][KS];
+  // (kn: the k-steps that count -- all KS in the site's row basis, the live EKS in the eigenbasis)
+  auto rows_to_evse = [&](const vec4 (&c4)[MT], auto&& bfrag, real (&out)[TS], auto kn) __attribute__((always_inline)) {
+    constexpr int KN = decltype(kn)::value;
+    real bf[4][KN];
 #pragma unroll
     for (int w = 0; w < 4; ++w)
 #pragma unroll
-      for (int s = 0; s < KS; ++s) bf[w][s] = bfrag(w, s);
+      for (int s = 0; s < KN; ++s) bf[w][s] = bfrag(w, s);
     vec4 acc[4];
 #pragma unroll
     for (int w = 0; w < 4; ++w) acc[w] = vec4{0, 0, 0, 0};
 #pragma unroll
-    for (int s = 0; s < KS; ++s)
+    for (int s = 0; s < KN; ++s)
 #pragma unroll
       for (int w = 0; w < 4; ++w) acc[w] = M::mma(c4[s >> 2][s & 3], bf[w][s], acc[w]);   // (four independent chains, interleaved)
     __builtin_amdgcn_wave_barrier();
@@ -345,6 +363,8 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     for (int t = 0; t < TS; ++t) out[t] = XT[lane * XS + t];
   };
   auto frag_ghat = [&](int w, int s) __attribute__((always_inline)) -> real { return FragX[(w * KS + s) * 64 + lane]; };
+  constexpr std::integral_constant<int, KS> all_rows{};
+  constexpr std::integral_constant<int, EKS> live_eigen{};
   auto frag_g = [&](int w, int s) __attribute__((always_inline)) -> real { return Gm[(size_t)(16 * (s >> 2) + 4 * (s & 3) + g) * A.NP + 16 * w + tc]; };
 
   // ---- problem data -> registers (EVSE layout) ------------------------------------------------------------------------
@@ -619,7 +639,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
         y2[r] = ok ? A.warm_y[((size_t)b * A.Mg + (ok ? ja : 0)) * Tm + (ok ? tb + tc : 0)] / RS[j] : 0.0;
         yv[r >> 2][r & 3] = y2[r];
       }
-      rows_to_evse(yv, frag_g, gty);
+      rows_to_evse(yv, frag_g, gty, all_rows);
     }
 #pragma unroll
     for (int t = 0; t < TS; ++t) {
@@ -634,9 +654,9 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     for (int mo = 0; mo < MT; ++mo) {
       vec4 zt = {0, 0, 0, 0};
 #pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
+      for (int mi = 0; mi < ET; ++mi)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) zt = M::mma(FQs[(((mo * MT + mi) * 2 + 1) * 4 + s) * 64 + lane], g0[mi][s], zt);
+        for (int s = 0; s < EKOF(mi); ++s) zt = M::mma(FQs[(((mo * MT + mi) * 2 + 1) * 4 + s) * 64 + lane], g0[mi][s], zt);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int k = 4 * mo + r;
@@ -665,7 +685,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     for (int t = 0; t < TS; ++t) r0[t] = sigma * x[t] - qv[t] + rho * z1[t] - y1[t];
     vec4 wh[MT];
 #pragma unroll
-    for (int mo = 0; mo < MT; ++mo) {
+    for (int mo = 0; mo < ET; ++mo) {
       vec4 acc = {0, 0, 0, 0};
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi)
@@ -680,9 +700,9 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     // ---- e^ = w^ - D (g0 + Lam w^);  h^ = (g0 + Lam e^)/a -----------------------------------------------------------------
     vec4 eh[MT], hh[MT];
 #pragma unroll
-    for (int m = 0; m < MT; ++m)
+    for (int m = 0; m < ET; ++m)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
+      for (int r = 0; r < EKOF(m); ++r) {   // (register r = eigen-rows 4 r ... 4 r + 3 of the tile = its k-step r)
         const real w_ = wh[m][r];
         const real lam_ = RowLam[16 * m + M::rowof(g, r)];
         const real e_ = w_ - RowDj[16 * m + M::rowof(g, r)] * (g0[m][r] + lam_ * w_);
@@ -695,9 +715,9 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     for (int mo = 0; mo < MT; ++mo) {
       vec4 zt = {0, 0, 0, 0};
 #pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
+      for (int mi = 0; mi < ET; ++mi)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) zt = M::mma(FQs[(((mo * MT + mi) * 2 + 1) * 4 + s) * 64 + lane], hh[mi][s], zt);
+        for (int s = 0; s < EKOF(mi); ++s) zt = M::mma(FQs[(((mo * MT + mi) * 2 + 1) * 4 + s) * 64 + lane], hh[mi][s], zt);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int k = 4 * mo + r;
@@ -710,7 +730,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     real zh[TS];
     {
       real corr[TS];
-      rows_to_evse(eh, frag_ghat, corr);
+      rows_to_evse(eh, frag_ghat, corr, live_eigen);
 #pragma unroll
       for (int t = 0; t < TS; ++t) {
         const real xn = (r0[t] + corr[t]) * inv_a;
@@ -955,7 +975,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
         vec4 yv[MT];
 #pragma unroll
         for (int r = 0; r < SR; ++r) yv[r >> 2][r & 3] = y2[r];
-        rows_to_evse(yv, frag_g, gty);
+        rows_to_evse(yv, frag_g, gty, all_rows);
 #pragma unroll
         for (int t = 0; t < TS; ++t) {
           v0 = fmax(v0, fabs(x[t] - z1[t]));
@@ -994,7 +1014,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
 #pragma unroll
           for (int r = 0; r < SR; ++r) { dy[r >> 2][r & 3] = dv2[r]; w0 = fmax(w0, fabs(dv2[r])); }
           real gtv[TS];
-          rows_to_evse(dy, frag_g, gtv);
+          rows_to_evse(dy, frag_g, gtv, all_rows);
           if constexpr (NPW >= 2) {
 #pragma unroll
             for (int t = 0; t < TS; ++t) dv1[t] = y1[t] - (real)sn1[t];
@@ -1179,6 +1199,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
   }   // passes
   }   // work queue
 #undef BIGC
+#undef EKOF
 }
 
 }  // namespace acnqp
