@@ -876,6 +876,16 @@ class SiteHandle:
             raise RuntimeError("acnqp_debug_wave_rank failed")
         return dict(rank=int(buf[0]), eig_ksteps=int(buf[1]), extent=int(buf[2]))
 
+    def wave_evse_extent(self) -> dict:
+        """The site's EVSEs, the MFMA k-steps of P = Ghat r0 that hold one, and the EVSE k-steps the wave kernel's
+        instantiation this handle runs sums over (acnqp_debug_wave_evse_extent: introspection, not part of the ABI)."""
+        buf = (C.c_int32 * 3)()
+        fn = self._lib.acnqp_debug_wave_evse_extent
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
+        if fn(self._h, buf) != 0:
+            raise RuntimeError("acnqp_debug_wave_evse_extent failed")
+        return dict(n_evse=int(buf[0]), evse_ksteps=int(buf[1]), extent=int(buf[2]))
+
     def ordered_launches(self) -> int:
         """Launches of this handle whose queue order was sorted by session count (acnqp_ordered_launch_count)."""
         return int(self._lib.acnqp_ordered_launch_count(self._h))

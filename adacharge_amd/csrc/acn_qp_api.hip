@@ -479,10 +479,18 @@ int wave_extent_of(const acnqp_handle* h) {
   return acnqp::wave_eig_extent(h->site.eig_ksteps, full_rank);
 }
 
+// The EVSE k-steps of P = Ghat r0 in the wave kernel's instantiation for this handle's site (acn_qp_rank.hpp).
+// ACNQP_WAVE_FULL_EVSE=1 (diagnostic, read once per process): all 16 for every site -- the kernel as it was.
+int wave_evse_extent_of(const acnqp_handle* h) {
+  static const bool full_evse = std::getenv("ACNQP_WAVE_FULL_EVSE") != nullptr;
+  return acnqp::wave_evse_extent(h->shape.N, full_evse);
+}
+
 hipError_t launch_solver(const acnqp_handle* h, const acnqp::Route& rt, const acnqp::TiledArgs& aa, const Workspace& ws, hipStream_t st) {
   if (rt.wv > 0) {
     acnqp::WaveSite w;
     w.Ghat = h->site.GhatW; w.lam = h->site.lamW; w.fragQ = h->site.fragQW; w.extent = wave_extent_of(h);
+    w.evse_ksteps = wave_evse_extent_of(h);
     return acnqp::launch_wave(aa, w, st);
   }
   if (rt.tiled) return rt.t_max <= 16 ? acnqp::launch_tiled_ct1(aa, st) : acnqp::launch_tiled_ct2(aa, st);
@@ -632,6 +640,15 @@ extern "C" int acnqp_debug_wave_rank(acnqp_handle* h, int32_t* out) {
   if (!h || !out) return -1;
   const int ext = wave_extent_of(h);
   out[0] = h->site.rank; out[1] = h->site.eig_ksteps; out[2] = ext > 0 ? ext : h->shape.MR / 4;
+  return 0;
+}
+
+// Introspection outside include/acn_qp.h (every build): out[0] = the site's EVSEs, out[1] = the MFMA k-steps of P = Ghat r0
+// that hold one (four EVSEs each), out[2] = the EVSE k-steps the wave kernel's instantiation for this handle runs
+// (acn_qp_rank.hpp; 16 = all of them).  Returns 0, -1 without a handle.
+extern "C" int acnqp_debug_wave_evse_extent(acnqp_handle* h, int32_t* out) {
+  if (!h || !out) return -1;
+  out[0] = h->shape.N; out[1] = (h->shape.N + 3) / 4; out[2] = wave_evse_extent_of(h);
   return 0;
 }
 

@@ -1,5 +1,5 @@
 // Host-side launchers of the four kernel families.  Each family is instantiated in its own translation unit
-// (acn_qp_tiled_ct1.hip, acn_qp_tiled_ct2.hip, acn_qp_stream.hip, acn_qp_long.hip, acn_qp_general.hip) so that
+// (acn_qp_tiled_ct1.hip, acn_qp_tiled_ct2.hip, acn_qp_wave.hip, acn_qp_wave_e14.hip, acn_qp_stream.hip, acn_qp_long.hip, acn_qp_general.hip) so that
 // adacharge_amd/build.py compiles them in parallel; acn_qp_api.hip (the C ABI) only sees these declarations.  Which family
 // a shape runs is decided in acn_qp_route.hpp, not here.
 #pragma once
@@ -99,9 +99,11 @@ hipError_t launch_tiled_ct2(const TiledArgs& a, hipStream_t st);
 // wave-per-problem kernel (acn_qp_wave.hpp): N <= 64, one session slot, horizon <= 24 with one or two row tiles or 33 ... 48
 // with one; wave_shape (acn_qp_route.hpp) says which variant a launch is routed to
 // ws: the site in the wave kernel's compacted eigenbasis (acn_qp_rank.hpp) and the eigen extent of the instantiation to
-// run -- 0: every k-step on a.Ghat / a.lam / a.fragQ as they are (the pointers of ws are then not read)
-struct WaveSite { const void *Ghat = nullptr, *lam = nullptr, *fragQ = nullptr; int extent = 0; };
+// run -- 0: every k-step on a.Ghat / a.lam / a.fragQ as they are (the pointers of ws are then not read); evse_ksteps: the
+// EVSE k-steps of P = Ghat r0 that instantiation runs (wave_evse_extent, acn_qp_rank.hpp; 16: all of them)
+struct WaveSite { const void *Ghat = nullptr, *lam = nullptr, *fragQ = nullptr; int extent = 0, evse_ksteps = 16; };
 hipError_t launch_wave(const TiledArgs& a, const WaveSite& ws, hipStream_t st);
+hipError_t launch_wave_e14(const TiledArgs& a, const WaveSite& ws, hipStream_t st);   // (acn_qp_wave_e14.hip: what launch_wave routes the 14-k-step extent to)
 int wave_accel_columns();   // Anderson columns compiled into it
 // large-site kernel (acn_qp_stream.hpp)
 hipError_t launch_stream(const StreamArgs& sa, hipStream_t st);

@@ -126,6 +126,18 @@ using acnqp::ChunkLayout;
 // predicts its iteration count well enough (rank correlation 0.81 on that workload: the list schedule by it ends 1.8 %
 // above the mean): two tiny kernels sort the problems by it, descending, and every solver kernel maps workgroup ->
 // problem through the result.  Results do not depend on the order (a workgroup only touches its own problem).
+//
+// That 1.8 % was measured at 32 problems per slot on 64 slots.  The wave kernel's headline launch has 16 problems per
+// slot on 1,024 wave slots, and there no key levels the tail.  A SIMULATION (tools/sim_launch_tail.py: the CPU twin's
+// iteration counts of the bench's 16,384 problems, capped at the polish hand-over, list-scheduled on 1,024 wave slots at
+// 3.67 us per iteration; nothing of it measured on a GPU): the work spread evenly 11.4 ms; one launch in session order
+// 13.6 ms (+19 %), by sum of s_len / sum of ub 13.0, by deliverable energy 13.5, natural order 13.2, a second seed set
+// 13.4-13.8; the chunk plan 2,048 / 4,096 / 8,192 / 2,048 with four-wave workgroups 14.2 ms for each of the four sorted
+// keys (second seed set 14.8-14.9), natural order 14.8 (15.3).  Only the TRUE iteration counts as the key reach the even
+// spread (11.45 ms lone, 12.9 pipelined), and no key known before the solve predicts them: a handful of problems with
+// few sessions run 400 ... 808 iterations (22 of the last 6,384 in session order), a serial chain that starts late ends
+// late whatever the order, and a CU passes to the next launch only when the slowest of its four waves is done.  What is
+// left as a lever is the latency of one wave-iteration.
 constexpr int kOrderKeys = 1024;
 constexpr int kOrderMinBatch = 768;   // fewer problems than ~1.5 x the resident slots: nothing to level
 __global__ __launch_bounds__(256) void order_keys_kernel(const int32_t* s_len, int KN, int B, int32_t* keys) {

@@ -45,4 +45,15 @@ inline int wave_eig_extent(int eig_ksteps, bool full_rank) {
   return 0;
 }
 
+// The EVSE extent of P = Ghat r0: the chain sums over the EVSEs, four per MFMA k-step, and a site of N <= 64 EVSEs fills
+// ceil(N / 4) of the 16 k-steps; beyond them the scratch rows and the columns of Ghat are zeros for good.  The wave kernel
+// is instantiated for 14 k-steps (N <= 56: caltech54, jpl52) and for all 16.  A function of the site's N only, never of
+// the batch.  full_evse: the diagnostic switch ACNQP_WAVE_FULL_EVSE=1.
+constexpr int kWaveEvseKsteps = 16, kWaveEvseExtent = 14;
+
+inline int wave_evse_extent(int N, bool full_evse) {
+  const int ks = (N + 3) / 4;
+  return !full_evse && ks <= kWaveEvseExtent ? kWaveEvseExtent : kWaveEvseKsteps;
+}
+
 }  // namespace acnqp

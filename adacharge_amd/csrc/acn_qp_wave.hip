@@ -1,23 +1,33 @@
 // Wave-per-problem kernel (acn_qp_wave.hpp): instantiation and launcher.
+// Compiled twice, so that the two halves of the instantiations build in parallel: as it is (every EVSE k-step of
+// P = Ghat r0; launch_wave, the entry) and through acn_qp_wave_e14.hip with ACNQP_WAVE_NE = 14 (the EVSE extent of the
+// sites of at most 56 EVSEs; launch_wave_e14).
 #include "acn_qp_launch.hpp"
 #include "acn_qp_rank.hpp"
 #include "acn_qp_wave.hpp"
 
+#ifndef ACNQP_WAVE_NE
+#define ACNQP_WAVE_NE 0
+#endif
+
 namespace acnqp {
+
+static_assert(ACNQP_WAVE_NE == 0 || ACNQP_WAVE_NE == kWaveEvseExtent, "the EVSE extents instantiated: 14 k-steps and all 16");
 
 // (which shapes come here: wave_shape, acn_qp_route.hpp; launch_wave below dispatches on the same cut points)
 static_assert(kRouteWaveTS == kWaveTS, "acn_qp_route.hpp restates the period slots per lane");
 
 // EK: the eigen extent of the instantiation (0: all k-steps, on the eigenbasis every kernel shares; otherwise the site's
 // arrays in the compacted eigenbasis replace them in this launch's copy of the arguments)
-template <int NPW, int TSV, int MT, bool PROX, int EK>
+// NE: the EVSE extent of P = Ghat r0 (0: all 16 k-steps), this unit's
+template <int NPW, int TSV, int MT, bool PROX, int EK, int NE = ACNQP_WAVE_NE>
 static hipError_t launch_wave_prox(const TiledArgs& a_in, const WaveSite& ws, hipStream_t st) {
   TiledArgs a = a_in;
   if (EK > 0) { a.Ghat = ws.Ghat; a.lam = ws.lam; a.fragQ = ws.fragQ; }
   a.accel_mem = std::min(a.accel_mem, kWaveAM);
   const WaveLds L(a.accel_mem, NPW, MT, TSV);
   const size_t lds = (size_t)L.total * 8;
-  auto kern = &admm_wave_kernel<kWaveAM, NPW, TSV, MT, PROX, EK>;
+  auto kern = &admm_wave_kernel<kWaveAM, NPW, TSV, MT, PROX, EK, NE>;
   if (lds > 64 * 1024) {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
@@ -56,17 +66,29 @@ static hipError_t launch_wave_npw(const TiledArgs& a, const WaveSite& ws, hipStr
   return launch_wave_ek<NPW, TSV, MT, 0>(a, ws, st);
 }
 
-int wave_accel_columns() { return kWaveAM; }
-
-hipError_t launch_wave(const TiledArgs& a, const WaveSite& ws, hipStream_t st) {
+template <int = 0>
+static hipError_t launch_wave_shape(const TiledArgs& a, const WaveSite& ws, hipStream_t st) {
   if (a.MR == 32) return a.Tm <= kWaveTS ? launch_wave_npw<2, 6, 2>(a, ws, st) : launch_wave_npw<4, 6, 2>(a, ws, st);
   if (a.Tm > 2 * kWaveTS) return launch_wave_npw<4, 12, 1>(a, ws, st);
   return a.Tm <= kWaveTS ? launch_wave_npw<1, 12, 1>(a, ws, st) : launch_wave_npw<2, 12, 1>(a, ws, st);
 }
 
+#if ACNQP_WAVE_NE == 0
+int wave_accel_columns() { return kWaveAM; }
+
+// (the EVSE extent: wave_evse_extent, acn_qp_rank.hpp -- a function of the site's N, decided by the caller; a site it
+//  does not hold never runs it)
+hipError_t launch_wave(const TiledArgs& a, const WaveSite& ws, hipStream_t st) {
+  if (ws.evse_ksteps == kWaveEvseExtent && a.N <= 4 * kWaveEvseExtent) return launch_wave_e14(a, ws, st);
+  return launch_wave_shape(a, ws, st);
+}
+#else
+hipError_t launch_wave_e14(const TiledArgs& a, const WaveSite& ws, hipStream_t st) { return launch_wave_shape(a, ws, st); }
+#endif
+
 }  // namespace acnqp
 
-#ifdef ACNQP_STAMPS
+#if defined(ACNQP_STAMPS) && ACNQP_WAVE_NE == 0
 /* diagnostic build only: the per-phase cycle counters of the wave-per-problem kernel (this unit's own g_stamps) */
 extern "C" int acnqp_debug_read_wave_stamps(unsigned long long* out, int n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(acnqp::g_stamps), sizeof(unsigned long long) * n);

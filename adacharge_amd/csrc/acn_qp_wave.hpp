@@ -39,6 +39,14 @@
 // MFMA instead of 16 per row tile, Q h^ EK instead of 4, and ONE eigen tile on the two-row-tile variants (P 16 instead of
 // 32, w^ 8 instead of 16) -- the same bits as EK = 0, the full extent on the eigenbasis the other kernels share
 // (ACNQP_WAVE_FULL_RANK=1: the A/B switch of tests/test_wave_rank_gpu.py).  The counts above are the full extent's.
+//
+// The EVSE extent NE (a seventh template argument; wave_evse_extent, acn_qp_rank.hpp): P = Ghat r0 sums over the EVSEs,
+// four per k-step.  A site of N EVSEs fills ceil(N / 4) of the 16 k-steps; in the others both operands are zeros for
+// good (the scratch rows of EVSEs beyond N, the columns of Ghat beyond N).  NE = 14 (N <= 56: caltech54, jpl52) runs the
+// chain and its operand reads over the first 14 k-steps only -- 14 MFMA and 28 LDS reads instead of 16 and 32 per row
+// tile; the two accumulators keep their even / odd k-steps, so only (+-0) x 0 terms leave the sums: the same bits as
+// NE = 0, every k-step (ACNQP_WAVE_FULL_EVSE=1: the A/B switch of tests/test_wave_trim_gpu.py).  The products back
+// to the EVSE layout (corr, the residual check's G' y) keep all four EVSE tiles.
 #pragma once
 #include <type_traits>
 
@@ -100,7 +108,7 @@ __device__ inline void wave_lds_sync() {   // this wave's LDS writes are visible
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int AM, int NPW, int TSV, int MT, bool PROX, int EK = 0>
+template <int AM, int NPW, int TSV, int MT, bool PROX, int EK = 0, int NE = 0>
 __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledArgs A_kernarg) {
   static_assert(NPW == 1 || NPW == 2 || NPW == 4, "one, two or four waves per problem");
   static_assert((TSV == 12 && MT == 1) || (TSV == 6 && MT == 2 && NPW >= 2), "instantiated: 12 periods x one row tile, 6 periods x two row tiles");
@@ -115,6 +123,8 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
   // Compile-time extents, everything still fully unrolled: no branch inside a chain.  EK = 0: every k-step (as ever).
   constexpr int EKS = EK > 0 ? EK : KS, ET = (EKS + 3) / 4;                        // live eigen k-steps, eigen tiles
   static_assert(EKS <= KS, "eigen extent");
+  constexpr int NKS = NE > 0 ? NE : 16;                                            // EVSE k-steps of P = Ghat r0 (four EVSEs each) that hold an EVSE of the site
+  static_assert(NKS <= 16, "EVSE extent");
 #define EKOF(m) (EKS - 4 * (m) < 4 ? EKS - 4 * (m) : 4)                            /* live k-steps of eigen tile m (= its live C-layout registers) */
 #define BIGC (scalar_const(1e300))
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -314,22 +324,23 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     wave_lds_sync();
     // every operand requested before the first MFMA (no branch in the chain: EVSEs beyond N hold zeros); two
     // accumulators per row tile, so that a product does not wait for the previous one's result
-    real bop[16];
+    // (the k-steps beyond NKS hold EVSEs the site does not have: zeros on both sides, neither read nor multiplied)
+    real bop[NKS];
 #pragma unroll
-    for (int s = 0; s < 16; ++s) {
+    for (int s = 0; s < NKS; ++s) {
       if constexpr (XC == 16) bop[s] = XT[(4 * s + g) * XS + tc];
       else bop[s] = tc < XC ? XT[(4 * s + g) * XS + (tc < XC ? tc : 0)] : 0.0;   // (the scratch holds 8 period columns)
     }
 #pragma unroll
     for (int m = 0; m < ET; ++m) {
-      real aop[16];
+      real aop[NKS];
 #pragma unroll
-      for (int s = 0; s < 16; ++s) aop[s] = frag[(m * 16 + s) * 64 + lane];
+      for (int s = 0; s < NKS; ++s) aop[s] = frag[(m * 16 + s) * 64 + lane];
       vec4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
 #pragma unroll
-      for (int s = 0; s < 16; s += 2) {
-        acc0 = M::mma(aop[s], bop[s], acc0);
-        acc1 = M::mma(aop[s + 1], bop[s + 1], acc1);
+      for (int s = 0; s < NKS; ++s) {   // (even k-steps into acc0, odd into acc1, whatever the extent)
+        if ((s & 1) == 0) acc0 = M::mma(aop[s], bop[s], acc0);
+        else acc1 = M::mma(aop[s], bop[s], acc1);
       }
       out[m] = acc0 + acc1;
     }

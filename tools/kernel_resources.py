@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from adacharge_amd.build import CSRC, FLAGS, INC, hipcc_path  # noqa: E402
 
-KERNEL_UNITS = ("acn_qp_wave", "acn_qp_polish", "acn_qp_tiled_ct1", "acn_qp_tiled_ct2", "acn_qp_stream", "acn_qp_long", "acn_qp_general")
+KERNEL_UNITS = ("acn_qp_wave", "acn_qp_wave_e14", "acn_qp_polish", "acn_qp_tiled_ct1", "acn_qp_tiled_ct2", "acn_qp_stream", "acn_qp_long", "acn_qp_general")
 FIELDS = ("VGPRs", "AGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
 
 
