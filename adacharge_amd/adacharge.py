@@ -260,19 +260,24 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
                 out[k] = {sid: rj[i] for i, sid in enumerate(ids)}
         return out
 
-    def simulate_batch(self, fleets, steps, start_time=0, warm_start=False, return_schedules=False, observer=None):
+    def simulate_batch(self, fleets, steps, start_time=0, warm_start=False, return_schedules=False, observer=None, session_order=None):
         """Closed-loop extension: ``steps`` control periods of B scenarios of this site (``fleets``: one list of EV records
         per scenario, or a ``rollout.FleetTable``) with the whole state resident in HBM.  On one stream, per period:
         ``solve_device -> pilots_device (first period) -> advance_device``, with no host synchronisation inside the loop; an
         EV becomes visible at its arrival step (online MPC, one session per EVSE).  Returns a ``rollout.RolloutResult``:
         ``pilots (steps, B, N)``, ``status``, ``iters`` and ``flags (steps, B)`` and the energy delivered to every EV, copied
         back once at the end.  Serves continuous pilots and ``quantize=True``; ``reallocate``, ``estimate_max_rate`` and
-        ``uninterrupted_charging`` raise ``ValueError``.  ``warm_start``: every solve but the first starts from the previous
+        ``uninterrupted_charging`` raise ``ValueError`` -- unless the caller states the order of the session lists a plant
+        would hand to ``schedule``, which those steps of the reference read and the device state does not carry:
+        ``session_order="fleet"`` (a session stands where its record stands in its fleet) or ``"arrival"`` (plug-in order).
+        Then ``uninterrupted_charging`` and ``reallocate`` are served (``acnqp_prepare_device`` between the advance and the
+        solve; the result carries ``visits`` and ``prepare_flags``); ``estimate_max_rate`` is refused either way.
+        ``warm_start``: every solve but the first starts from the previous
         period's schedule and multipliers, shifted on the device.  ``observer(step, state, pilots)``: diagnostic hook called
         after each period's solve has been enqueued (it may synchronise and read the ``DeviceBatch``)."""
         from .rollout import simulate
 
-        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer)
+        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer, session_order)
 
 
 class AdaptiveChargingAlgorithmOffline(BaseAlgorithm):

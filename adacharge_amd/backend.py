@@ -139,6 +139,21 @@ class _Next(C.Structure):
 ADVANCE_REFUSED, ADVANCE_NO_ROW, ADVANCE_BAD_SLOT = 1, 2, 4
 
 
+class _PreparePlan(C.Structure):
+    """Mirror of ``acnqp_prepare_plan`` (include/acn_qp.h)."""
+
+    _fields_ = [("n_evse", C.c_int32), ("n_infra", C.c_int32)] + [(k, C.c_void_p) for k in ("key", "cre", "cim", "limits", "min_pilot")]
+
+
+class _PrepareView(C.Structure):
+    """Mirror of ``acnqp_prepare_view`` (include/acn_qp.h)."""
+
+    _fields_ = [("v_evse", C.c_void_p), ("v_arrived", C.c_void_p), ("v_cap", C.c_void_p)]
+
+
+PREPARE_FUTURE = 1
+
+
 class Options(C.Structure):
     """Mirror of ``acnqp_options``; construct with ``default_options()``."""
 
@@ -191,6 +206,8 @@ EXPORTED_SYMBOLS = (
     "acnqp_pilots_host",
     "acnqp_advance_device",
     "acnqp_advance_host",
+    "acnqp_prepare_device",
+    "acnqp_prepare_host",
 )
 
 # kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
@@ -280,6 +297,12 @@ def load_library():
     lib.acnqp_advance_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(_AdvancePlan), C.POINTER(_Next), C.c_void_p]
     lib.acnqp_advance_host.restype = C.c_int
+    lib.acnqp_prepare_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(_PreparePlan), C.c_void_p, C.c_void_p,
+                                         C.POINTER(_PrepareView), C.c_void_p, C.c_void_p]
+    lib.acnqp_prepare_device.restype = C.c_int
+    lib.acnqp_prepare_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(_PreparePlan), C.c_void_p, C.c_void_p,
+                                       C.POINTER(_PrepareView), C.c_void_p]
+    lib.acnqp_prepare_host.restype = C.c_int
     _lib = lib
     return lib
 
@@ -434,6 +457,46 @@ class AdvancePlan:
                             float(self.warm_arrival_gain),
                             ptr("q_table"), ptr("h_scal"), ptr("h_row"), ptr("peak_series"), ptr("a_seg", seg_row) if A else None,
                             ptr("a_evse"), ptr("a_slot"), ptr("a_len"), ptr("a_cap"), ptr("a_rate_seg"), ptr("a_min"), ptr("a_max"))
+
+
+@dataclass
+class PreparePlan:
+    """The arrays of ``acnqp_prepare_plan`` (include/acn_qp.h): numpy arrays for ``SiteHandle.prepare_host``, torch tensors on the
+    handle's GPU (``to_device``) for ``SiteHandle.prepare_device``.  ``key`` may hold one (B, N) block per step
+    (``(steps, B, N)``): ``key_row`` picks the step's.  ``min_pilot=None``: no minimum-rate step."""
+    key: object                          # (B, N) or (rows, B, N) int32: list position of the session on each EVSE
+    cre: Optional[object] = None         # (M, N) the site in the SOC form of ``PilotPlan``
+    cim: Optional[object] = None
+    limits: Optional[object] = None      # (M,)
+    min_pilot: Optional[object] = None   # (N,)
+
+    _ARRAYS = ("key", "cre", "cim", "limits", "min_pilot")
+
+    def to_device(self, device) -> "PreparePlan":
+        import torch
+
+        moved = {}
+        for k in self._ARRAYS:
+            a = getattr(self, k)
+            moved[k] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int32 if k == "key" else np.float64)).to(device)
+        return PreparePlan(**moved)
+
+    def _struct(self, N: int, key_row=None, min_rates: bool = True, keep=None) -> "_PreparePlan":
+        def ptr(k):
+            a = getattr(self, k)
+            if a is None or (a.numel() if hasattr(a, "numel") else a.size) == 0:
+                return None
+            if k == "key" and a.ndim == 3:
+                a = a[0 if key_row is None else key_row]
+            if hasattr(a, "data_ptr"):
+                return C.c_void_p(a.data_ptr())
+            a = np.ascontiguousarray(a, np.int32 if k == "key" else np.float64)
+            if keep is not None:
+                keep.append(a)
+            return _ptr(a)
+
+        M = 0 if self.cre is None else int(self.cre.shape[0])
+        return _PreparePlan(int(N), M, ptr("key"), ptr("cre"), ptr("cim"), ptr("limits"), ptr("min_pilot") if min_rates else None)
 
 
 class _PinnedBlock:
@@ -845,6 +908,75 @@ class SiteHandle:
         _check(self._lib.acnqp_advance_device(self._h, C.byref(p), _dptr(applied), _dptr(cur.status) if use_status else None,
                                               _dptr(cur.x) if warm_x is not None else None, _dptr(cur.y) if warm_y is not None else None,
                                               C.byref(pl), C.byref(nx), _dptr(flags), C.c_void_p(stream)), "acnqp_advance_device")
+
+    # -- before the solve (acn_qp_prepare.hpp) ---------------------------------------------------------------------------
+    def prepare_host(self, cur: dict, plan: PreparePlan, want_view: bool = True, min_rates: bool = True, key_row=None) -> dict:
+        """acnqp_prepare_host: the state ``cur`` -- numpy arrays ``lb, ub`` (B, N, Tm) and ``s_off, s_len, s_cap`` (B, 1, N) or
+        (B, N) -- under ``plan`` (numpy arrays).  Returns ``lb, ub`` (copies, period 0 changed when the plan has ``min_pilot``
+        and ``min_rates``), ``flags`` (B,) and, with ``want_view``, ``v_evse, v_arrived, v_cap`` (B, N)."""
+        f8 = lambda a: np.array(a, np.float64, order="C")
+        i4 = lambda a: np.ascontiguousarray(a, np.int32)
+        lb, ub, off, ln, cap = f8(cur["lb"]), f8(cur["ub"]), i4(cur["s_off"]), i4(cur["s_len"]), np.ascontiguousarray(cur["s_cap"], np.float64)
+        if lb.ndim != 3 or lb.shape[1] != self.site.N or ub.shape != lb.shape:
+            raise ValueError("cur needs lb, ub of shape (B, N, Tm) for the handle's site")
+        B, N, Tm = lb.shape
+        K = off.shape[1] if off.ndim == 3 else 1
+        if off.size != B * K * N or ln.size != off.size or cap.size != off.size:
+            raise ValueError("cur needs s_off, s_len, s_cap of shape (B, K, N)")
+        view = dict(v_evse=np.empty((B, N), np.int32), v_arrived=np.empty((B, N), np.uint8), v_cap=np.empty((B, N))) if want_view else {}
+        flags = np.empty(B, np.int32)
+        p = _Problems(B, Tm, K, None, None, None, None, None, _ptr(off), _ptr(ln), _ptr(cap), None, None, None, None, None, None, None)
+        keep = []
+        pl = plan._struct(N, key_row, min_rates, keep)
+        v = _PrepareView(*[_ptr(view.get(k)) for k in ("v_evse", "v_arrived", "v_cap")])
+        _check(self._lib.acnqp_prepare_host(self._h, C.byref(p), C.byref(pl), _ptr(lb), _ptr(ub), C.byref(v), _ptr(flags)), "acnqp_prepare_host")
+        del keep
+        return dict(lb=lb, ub=ub, flags=flags, **view)
+
+    def prepare_device(self, cur: "DeviceBatch", plan: PreparePlan, flags, v_evse=None, v_arrived=None, v_cap=None, min_rates: bool = True,
+                       key_row=None, stream: int = 0) -> None:
+        """acnqp_prepare_device: period 0 of ``cur.lb`` / ``cur.ub`` gets the minimum rates (when the plan has ``min_pilot`` and
+        ``min_rates``), and ``v_evse`` (B, N) int32, ``v_arrived`` (B, N) uint8 and ``v_cap`` (B, N) float64 -- all three or
+        none -- the session view of ``cur`` in the order of ``plan.key``; ``flags`` (B,) int32.  ``plan`` from
+        ``PreparePlan.to_device``.  Asynchronous on ``stream``."""
+        import torch
+
+        here = torch.device("cuda", self.device)
+
+        def want(t, name, dtype, shape):
+            if t is None:
+                return
+            if not isinstance(t, torch.Tensor) or t.device != here or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor on {here} of shape {tuple(shape)}")
+
+        B, N, Tm = cur.B, cur.N, cur.Tm
+        M = 0 if plan.cre is None else int(plan.cre.shape[0])
+        if plan.key is None or not hasattr(plan.key, "dim"):
+            raise ValueError("plan.key must be a tensor on the handle's GPU (PreparePlan.to_device)")
+        want(plan.key, "plan.key", torch.int32, (B, N) if plan.key.dim() == 2 else (plan.key.shape[0], B, N))
+        if plan.key.dim() == 3 and not 0 <= (0 if key_row is None else int(key_row)) < plan.key.shape[0]:
+            raise ValueError("key_row is outside plan.key")
+        want(plan.cre, "plan.cre", torch.float64, (M, N))
+        want(plan.cim, "plan.cim", torch.float64, (M, N))
+        want(plan.limits, "plan.limits", torch.float64, (M,))
+        want(plan.min_pilot, "plan.min_pilot", torch.float64, (N,))
+        want(cur.lb, "cur.lb", torch.float64, (B, N, Tm))
+        want(cur.ub, "cur.ub", torch.float64, (B, N, Tm))
+        want(cur.s_off, "cur.s_off", torch.int32, (B, cur.K, N))
+        want(cur.s_len, "cur.s_len", torch.int32, (B, cur.K, N))
+        want(cur.s_cap, "cur.s_cap", torch.float64, (B, cur.K, N))
+        want(flags, "flags", torch.int32, (B,))
+        if flags is None:
+            raise ValueError("flags is required")
+        want(v_evse, "v_evse", torch.int32, (B, N))
+        want(v_arrived, "v_arrived", torch.uint8, (B, N))
+        want(v_cap, "v_cap", torch.float64, (B, N))
+        p = _Problems(B, Tm, cur.K, None, None, None, None, None, _dptr(cur.s_off), _dptr(cur.s_len), _dptr(cur.s_cap), None, None, None, None,
+                      None, None, None)
+        pl = plan._struct(N, key_row, min_rates)
+        v = _PrepareView(_dptr(v_evse), _dptr(v_arrived), _dptr(v_cap))
+        _check(self._lib.acnqp_prepare_device(self._h, C.byref(p), C.byref(pl), _dptr(cur.lb), _dptr(cur.ub), C.byref(v), _dptr(flags),
+                                              C.c_void_p(stream)), "acnqp_prepare_device")
 
     def _kernel_ms_of_call(self) -> float:
         """Sum of the HIP-event durations of the launches since the previous ``kernel_times`` call; NaN when an event

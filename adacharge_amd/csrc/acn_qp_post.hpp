@@ -1,4 +1,4 @@
-// The post-solve entries (dual report, pilot signals, time passes): argument checks, _device entries, _host entries.  A
+// The post-solve entries (dual report, pilot signals, time passes, before the solve): argument checks, _device entries, _host entries.  A
 // host entry is a TABLE of the arrays it stages and a body that rebuilds the argument structs on staging addresses and
 // calls the _device entry; ONE planner lays the table out and ONE loop (run_staged) moves it.
 // Part 1 (table row, planner, overlap predicate) is plain host code: tests/test_post_stage.py compiles it with the host
@@ -19,6 +19,7 @@ struct Staged {
   static Staged plan(const void* s, size_t b) { return {s, nullptr, b, true}; }
   static Staged in(const void* s, size_t b) { return {s, nullptr, b, false}; }
   static Staged out(void* d, size_t b) { return {nullptr, d, b, false}; }
+  static Staged inout(void* p, size_t b) { return {p, p, b, false}; }   // uploaded, changed in place, downloaded
 };
 
 struct StageAddr { void* p; template <class T> operator T*() const { return static_cast<T*>(p); } };   // a staging address, as its field's pointer type
@@ -361,6 +362,86 @@ int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* c, const double* a
     acnqp_next nc{dev(OHOR), dev(OLB), dev(OUB), dev(OQ), dev(OPD), dev(OOFF), dev(OLEN), dev(OCAP), dev(OPK), dev(OLF), dev(ODC), dev(ODFL),
                   dev(OWX), dev(OWY)};
     return acnqp_advance_device(h, &cc, dev(APP), dev(STAT), dev(X), dev(Y), &pc, &nc, dev(OFLG), h->slot[0].st);
+  });
+}
+
+// ---- before the solve (acn_qp_prepare.hpp) ------------------------------------------------------------------------------
+static int check_prepare_args(const acnqp_handle* h, const acnqp_problems* c, const acnqp_prepare_plan* pl, const double* lb, const double* ub,
+                              const acnqp_prepare_view* v, const int32_t* flags, const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!c || !pl) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  if (pl->n_evse != h->shape.N || pl->n_infra != h->shape.M)
+    return fail(ACNQP_ERR_INVALID, w + ": the plan is for " + std::to_string(pl->n_evse) + " EVSEs and " + std::to_string(pl->n_infra) +
+                                       " infrastructure rows, the handle's site has " + std::to_string(h->shape.N) + " and " + std::to_string(h->shape.M));
+  if (c->k_sessions != 1) return fail(ACNQP_ERR_INVALID, w + ": k_sessions must be 1 (online MPC: one session per EVSE)");
+  if (c->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (c->t_max < 1 || c->t_max > 4096) return fail(ACNQP_ERR_INVALID, w + ": t_max must be in [1, 4096]");
+  const bool view = v && (v->v_evse || v->v_arrived || v->v_cap);
+  if (view && (!v->v_evse || !v->v_arrived || !v->v_cap)) return fail(ACNQP_ERR_INVALID, w + ": a view needs v_evse, v_arrived and v_cap");
+  if (c->batch == 0) return ACNQP_OK;
+  const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, M = (size_t)h->shape.M;
+  if (B * N > ((size_t)1 << 31) || B * N * Tm > ((size_t)1 << 40)) return fail(ACNQP_ERR_INVALID, w + ": batch too large");
+  if (!c->s_off || !c->s_len || !c->s_cap || !lb || !ub || !pl->key || !flags)
+    return fail(ACNQP_ERR_INVALID, w + ": null slot array, lb, ub, key or flags");
+  if (pl->min_pilot && M > 0 && (!pl->cre || !pl->cim || !pl->limits)) return fail(ACNQP_ERR_INVALID, w + ": min_pilot without cre, cim or limits");
+  struct Span { const void* p; size_t n; const char* name; };
+  const size_t nb = B * N * Tm * 8, site = pl->min_pilot ? M * N * 8 : 0;
+  const Span in[] = {{c->s_off, B * N * 4, "s_off"}, {c->s_len, B * N * 4, "s_len"}, {c->s_cap, B * N * 8, "s_cap"}, {pl->key, B * N * 4, "key"},
+                     {pl->cre, site, "cre"}, {pl->cim, site, "cim"}, {pl->limits, pl->min_pilot ? M * 8 : 0, "limits"}, {pl->min_pilot, N * 8, "min_pilot"}};
+  const Span out[] = {{lb, nb, "lb"}, {ub, nb, "ub"}, {view ? v->v_evse : nullptr, B * N * 4, "v_evse"}, {view ? v->v_arrived : nullptr, B * N, "v_arrived"},
+                      {view ? v->v_cap : nullptr, B * N * 8, "v_cap"}, {flags, B * 4, "flags"}};
+  const size_t n_out = sizeof(out) / sizeof(out[0]);
+  for (size_t a = 0; a < n_out; ++a) {
+    for (const Span& s : in)
+      if (acnqp::spans_meet(out[a].p, out[a].n, s.p, s.n))
+        return fail(ACNQP_ERR_INVALID, w + ": an output aliases an input (" + out[a].name + " overlaps " + s.name + ")");
+    for (size_t b2 = a + 1; b2 < n_out; ++b2)
+      if (acnqp::spans_meet(out[a].p, out[a].n, out[b2].p, out[b2].n))
+        return fail(ACNQP_ERR_INVALID, w + ": two outputs overlap (" + out[a].name + " and " + out[b2].name + ")");
+  }
+  return ACNQP_OK;
+}
+
+int acnqp_prepare_device(acnqp_handle* h, const acnqp_problems* c, const acnqp_prepare_plan* pl, double* lb, double* ub,
+                         acnqp_prepare_view* v, int32_t* flags, void* hip_stream) {
+  const int rc = check_prepare_args(h, c, pl, lb, ub, v, flags, "acnqp_prepare_device");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  acnqp::PrepareArgs a;
+  a.B = c->batch; a.N = h->shape.N; a.Tm = c->t_max; a.M = pl->min_pilot ? h->shape.M : 0;
+  a.s_off = c->s_off; a.s_len = c->s_len; a.s_cap = c->s_cap; a.lb = lb; a.ub = ub; a.key = pl->key;
+  a.cre = pl->cre; a.cim = pl->cim; a.limits = pl->limits; a.min_pilot = pl->min_pilot;
+  const bool view = v && v->v_evse;
+  a.v_evse = view ? v->v_evse : nullptr; a.v_arrived = view ? v->v_arrived : nullptr; a.v_cap = view ? v->v_cap : nullptr;
+  a.flags = flags;
+  a.site_lds = 0;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_prepare(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("prepare kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_prepare_host(acnqp_handle* h, const acnqp_problems* c, const acnqp_prepare_plan* pl, double* lb, double* ub,
+                       acnqp_prepare_view* v, int32_t* flags) {
+  const int rc = check_prepare_args(h, c, pl, lb, ub, v, flags, "acnqp_prepare_host");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, M = pl->min_pilot ? (size_t)h->shape.M : 0, nv = N * (size_t)c->t_max * 8;
+  const bool view = v && v->v_evse;
+  enum { CRE, CIM, LIM, MINP, SOFF, SLEN, SCAP, KEY, LB, UB, VE, VA, VC, FLG, NARR };
+  const S arr[NARR] = {S::plan(pl->cre, M * N * 8), S::plan(pl->cim, M * N * 8), S::plan(pl->limits, M * 8), S::plan(pl->min_pilot, pl->min_pilot ? N * 8 : 0),
+                       S::in(c->s_off, N * 4), S::in(c->s_len, N * 4), S::in(c->s_cap, N * 8), S::in(pl->key, N * 4), S::inout(lb, nv), S::inout(ub, nv),
+                       S::out(view ? v->v_evse : nullptr, view ? N * 4 : 0), S::out(view ? v->v_arrived : nullptr, view ? N : 0),
+                       S::out(view ? v->v_cap : nullptr, view ? N * 8 : 0), S::out(flags, 4)};
+  return run_staged(h, arr, NARR, B, [&](size_t, size_t nb, auto dev) {
+    acnqp_problems cc = *c;
+    cc.batch = (int32_t)nb;
+    cc.s_off = dev(SOFF); cc.s_len = dev(SLEN); cc.s_cap = dev(SCAP);
+    acnqp_prepare_plan pc = *pl;
+    pc.key = dev(KEY); pc.cre = dev(CRE); pc.cim = dev(CIM); pc.limits = dev(LIM); pc.min_pilot = dev(MINP);
+    acnqp_prepare_view vc{dev(VE), dev(VA), dev(VC)};
+    return acnqp_prepare_device(h, &cc, &pc, dev(LB), dev(UB), &vc, dev(FLG), h->slot[0].st);
   });
 }
 

@@ -4,6 +4,8 @@ Every user of the reference runs it in a closed loop: each period the loop solve
 chargers, integrates the delivered energy and builds the next problem.  ``simulate`` runs that loop for B scenarios of one
 site on one stream -- ``acnqp_solve_batch_device -> acnqp_pilots_device -> acnqp_advance_device`` per period, no host
 synchronisation in between -- and copies pilots, statuses and flags back once at the end.
+With a stated ``session_order`` the loop also serves the two settings of the reference that read the session list,
+``uninterrupted_charging`` and ``reallocate``: ``acnqp_prepare_device`` runs between the advance and the solve.
 
 ``FleetTable`` is everything the loop needs that does not depend on what the solver answers, computed once for the whole
 run: the arrival records of every step (the layout of ``acnqp_advance_plan``), the linear cost and the scalars of every
@@ -32,6 +34,8 @@ class RolloutResult:
     flags: np.ndarray       # (steps, B) int32: flags of the advance that built the step's problems (0 = nothing refused)
     delivered: List[np.ndarray]   # per scenario: kWh delivered to each EV of the fleet, in the fleet's order
     x: Optional[np.ndarray] = None   # (steps, B, N, Tm) the solved schedules, when asked for
+    visits: Optional[np.ndarray] = None          # (steps, B) int32 visits of the reallocation's round robin (reallocate=True)
+    prepare_flags: Optional[np.ndarray] = None   # (steps, B) int32 flags of acnqp_prepare_device (a session_order was stated)
 
 
 class FleetTable:
@@ -44,10 +48,21 @@ class FleetTable:
     back); behind any other interface only this package's clock-free components (quick_charge, equal_share, total_energy,
     load_flattening, peak, demand_charge) are accepted.  Either way a cost that reads the clock (``tou_energy_cost``) is
     refused.  An ``external_signal`` of ``load_flattening`` is the caller's fixed array: it is read from its first entry
-    at every step, as ``schedule`` reads it."""
+    at every step, as ``schedule`` reads it.
+    ``session_order`` states the order of the session lists a plant would hand to ``schedule`` -- what the reference's
+    minimum-rate walk and reallocation read, and the slot state does not carry: ``"fleet"`` (a session stands where its record
+    stands in its fleet), ``"arrival"`` (plug-in order: the rank of (arrival, fleet index), with the EV's true arrival also
+    when it lies before ``start_time``) or None.  ``order_keys`` (steps, B, N) int32 then holds, for every step and EVSE, the
+    position of the record whose stay covers that step (the ``key`` of ``acnqp_prepare_plan``); None without an order."""
+
+    ORDERS = ("fleet", "arrival")
 
     def __init__(self, fleets: Sequence[Sequence[dict]], infrastructure, interface, objective, steps: int, start_time: int = 0,
-                 peak_limit=None, done_kwh: float = 1e-9, t_max: Optional[int] = None):
+                 peak_limit=None, done_kwh: float = 1e-9, t_max: Optional[int] = None, session_order: Optional[str] = None):
+        if session_order is not None and session_order not in self.ORDERS:
+            raise ValueError(f'session_order must be "fleet", "arrival" or None, not {session_order!r}')
+        self.session_order = session_order
+        self.min_pilot = np.ascontiguousarray(infrastructure.min_pilot, float)[: infrastructure.num_stations].copy()
         self.fleets = [list(f) for f in fleets]
         self.objective, self.peak_limit = objective, peak_limit   # (simulate checks them against the algorithm's)
         self.B, self.N = len(self.fleets), infrastructure.num_stations
@@ -62,7 +77,8 @@ class FleetTable:
         self.done_tol = float(done_kwh / self.kwh_per_amp_period[0])
         max_pilot = np.asarray(infrastructure.max_pilot, float)
         index = {s: i for i, s in enumerate(infrastructure.station_ids)}
-        recs = []   # (visible step, scenario, evse, len, cap, min rates, max rates, ev index)
+        recs = []   # (visible step, scenario, evse, len, cap, min rates, max rates)
+        self._stays = []   # (scenario, evse, first step, end step, fleet index, arrival) of every record admitted
         self.windows = []   # per scenario: (evse, first step, end step) of every EV, relative to start (clipped to the run)
         longest = 1
         for b, fleet in enumerate(self.fleets):
@@ -91,8 +107,10 @@ class FleetTable:
                 if not np.all(np.isfinite(rates[1])):
                     raise ValueError("max_rate must be finite (the site gives no max_pilot for this EVSE)")
                 recs.append((tv - self.start, b, i, ln, cap, rates[0], rates[1]))
+                self._stays.append((b, i, tv - self.start, dep - self.start, n, arr))
                 longest = max(longest, ln)
             self.windows.append(wins)
+        self.order_keys = None if session_order is None else self.keys_for(session_order)
         self.Tm = int(t_max) if t_max is not None else longest
         if self.Tm < longest:
             raise ValueError(f"t_max = {self.Tm} is shorter than the longest stay ({longest} periods)")
@@ -139,6 +157,21 @@ class FleetTable:
             a_seg=a_seg, a_evse=np.array([r[2] for r in recs], np.int32), a_slot=np.zeros(A, np.int32), a_len=lens,
             a_cap=np.array([r[4] for r in recs], np.float64), a_rate_seg=rate_seg, a_min=cat(5), a_max=cat(6))
 
+    def keys_for(self, session_order: str) -> np.ndarray:
+        """(steps, B, N) int32: at step s, the list position under ``session_order`` of the record staying on EVSE i of
+        scenario b (stays on one EVSE never overlap); 0 where no record stays."""
+        if session_order not in self.ORDERS:
+            raise ValueError(f'session_order must be "fleet" or "arrival", not {session_order!r}')
+        keys = np.zeros((self.steps, self.B, self.N), np.int32)
+        pos = {}
+        if session_order == "arrival":
+            for b in range(self.B):
+                mine = sorted((arr, n) for bb, _, _, _, n, arr in self._stays if bb == b)
+                pos.update({(b, n): r for r, (_, n) in enumerate(mine)})
+        for b, i, lo, hi, n, _ in self._stays:
+            keys[max(lo, 0): min(hi, self.steps), b, i] = n if session_order == "fleet" else pos[b, n]
+        return keys
+
     def _refuse_clock_dependence(self, objective, infrastructure, interface, q_now):
         data = getattr(interface, "data", None)
         if not isinstance(data, dict):   # no clock to move: only components known not to read one
@@ -176,7 +209,7 @@ class FleetTable:
 
 
 def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = False, return_schedules: bool = False,
-             observer=None) -> RolloutResult:
+             observer=None, session_order: Optional[str] = None) -> RolloutResult:
     """``AdaptiveSchedulingAlgorithm.simulate_batch``: see there."""
     import torch
 
@@ -186,17 +219,22 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
     for on, why in ((alg.reallocate, "reallocate=True: the round robin breaks ties by session-list order, which the slot state does not carry"),
                     (alg.estimate_max_rate, "estimate_max_rate: per-step pre-processing that reads the evolving state"),
                     (alg.uninterrupted_charging, "uninterrupted_charging: per-step pre-processing that reads the evolving state")):
-        if on:
+        if on and (session_order is None or why.startswith("estimate_max_rate")):
             raise ValueError(f"simulate_batch does not serve {why}")
+    if session_order is not None and session_order not in FleetTable.ORDERS:
+        raise ValueError(f'session_order must be "fleet", "arrival" or None, not {session_order!r}')
     if alg.constraint_type not in ("SOC", "LINEAR"):
         from .builder import _bad_constraint_type
 
         _bad_constraint_type(alg.constraint_type)
     interface = alg.interface
     infra = interface.infrastructure_info()
-    table = fleets if isinstance(fleets, FleetTable) else FleetTable(fleets, infra, interface, alg.objective, steps, start_time, alg.peak_limit)
+    table = fleets if isinstance(fleets, FleetTable) else FleetTable(fleets, infra, interface, alg.objective, steps, start_time, alg.peak_limit,
+                                                                            session_order=session_order)
     if (table.steps, table.start) != (int(steps), int(start_time)):
         raise ValueError("the FleetTable was built for another run (steps, start_time)")
+    if table.session_order != session_order:
+        raise ValueError(f"the FleetTable was built with session_order={table.session_order!r}, the call states {session_order!r}")
     same_objective = len(table.objective) == len(alg.objective) and all(a is b or a == b for a, b in zip(table.objective, alg.objective))
     same_peak = (table.peak_limit is None) == (alg.peak_limit is None) and (
         table.peak_limit is None or np.array_equal(np.asarray(table.peak_limit, float), np.asarray(alg.peak_limit, float)))
@@ -215,6 +253,34 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
         plan.warm_arrival_gain = START_GAIN if warm_start else 0.0
         mode = "discrete" if alg.quantize else "continuous"
         pplan = pilot_plan_arrays(None, infra, interface, mode, batch=B, t_max=Tm).to_device(dev)
+        # the two settings that read the session list: its order comes from the caller, as one key per (step, scenario, EVSE)
+        min_rates, realloc = bool(alg.uninterrupted_charging), bool(alg.reallocate)
+        prep = min_rates or realloc
+        view = [None, None, None]
+        visits = pflags = None
+        if session_order is not None:
+            pflags = torch.zeros((steps, B), dtype=torch.int32, device=dev)
+        if prep:
+            cm = infra.constraint_matrix
+            has_rows = cm is not None and np.size(cm) > 0
+            ph = np.deg2rad(infra.phases)
+            # (the reference's minimum-rate step returns the list sorted by arrival, stable: plug-in order whichever was stated)
+            keys = table.keys_for("arrival") if min_rates else table.order_keys
+            prplan = backend.PreparePlan(key=keys, cre=np.ascontiguousarray(cm * np.cos(ph)) if has_rows else None,
+                                         cim=np.ascontiguousarray(cm * np.sin(ph)) if has_rows else None,
+                                         limits=np.ascontiguousarray(infra.constraint_limits, float) if has_rows else None,
+                                         min_pilot=table.min_pilot if min_rates else None).to_device(dev)
+        if realloc:
+            view = [torch.zeros((B, N), dtype=dt, device=dev) for dt in (torch.int32, torch.uint8, torch.float64)]
+            visits = torch.zeros((steps, B), dtype=torch.int32, device=dev)
+            pplan.mode = backend.PILOTS_REALLOCATE
+            pplan.cre, pplan.cim, pplan.limits = prplan.cre, prplan.cim, prplan.limits
+            pplan.sess_seg = (torch.arange(B + 1, dtype=torch.int32) * N).to(dev)   # every problem's view holds N entries
+            pplan.s_evse, pplan.s_arrived, pplan.s_cap = (v.view(B * N) for v in view)
+
+        def prepare(state, row):
+            if prep:
+                handle.prepare_device(state, prplan, pflags[row], *view, min_rates=min_rates, key_row=row, stream=stream)
         s_eq = 1 if alg.enforce_energy_equality else 0
         want_y = warm_start and site.Mg > 0
         bufs = [backend.DeviceBatch.empty(site, B, Tm, K, dev, want_y=want_y, s_eq=s_eq, dfloor=table.dfloor0) for _ in range(2)]
@@ -228,11 +294,12 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
         nothing = torch.zeros((B, N), dtype=torch.float64, device=dev)
         # the first period's problems: time "passes" on an empty state, its arrivals are admitted
         handle.advance_device(bufs[1], bufs[0], nothing, plan, -1, flags[0], use_status=False, stream=stream, seg_row=0)
+        prepare(bufs[0], 0)
         for s in range(steps):
             cur, nxt = bufs[s % 2], bufs[(s + 1) % 2]
             warm = want_y and s > 0   # (a site without rows has no multipliers to carry: it starts cold)
             handle.solve_device(cur, options, stream=stream, warm_x=wx if warm else None, warm_y=wy if warm else None)
-            handle.pilots_device(pplan, cur.x, first=pilots[s], stream=stream)
+            handle.pilots_device(pplan, cur.x, first=pilots[s], visits=visits[s] if realloc else None, stream=stream)
             status[s].copy_(cur.status)
             iters[s].copy_(cur.iters)
             if xs is not None:
@@ -242,9 +309,15 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             if s + 1 < steps:
                 handle.advance_device(cur, nxt, pilots[s], plan, s, flags[s + 1], use_status=True, warm_x=wx,
                                       warm_y=wy, stream=stream, seg_row=s + 1)
+                prepare(nxt, s + 1)
         torch.cuda.synchronize(dev)
         p = pilots.cpu().numpy()
         st = status.cpu().numpy()
         p[~np.isin(st, backend.ACCEPTED_STATUSES)] = 0.0   # what the advance delivered for a step that did not solve: nothing
+        vis = None if visits is None else visits.cpu().numpy()
+        if vis is not None and (vis < 0).any():
+            s_bad, b_bad = (int(v[0]) for v in np.nonzero(vis < 0))
+            raise ValueError(f"step {s_bad}, scenario {b_bad}: allowable pilots end below a session's cap; the reallocation of the "
+                             "rounding loss would never end")
         return RolloutResult(p, st, iters.cpu().numpy(), flags.cpu().numpy(), table.delivered(p),
-                             None if xs is None else xs.cpu().numpy())
+                             None if xs is None else xs.cpu().numpy(), vis, None if pflags is None else pflags.cpu().numpy())

@@ -555,6 +555,62 @@ int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* cur, const double*
                        const double* x, const double* y, const acnqp_advance_plan* plan, acnqp_next* next,
                        int32_t* flags);
 
+/* ---- before the solve (additive to ABI v10: new symbols only) --------------------------------------------------------
+ * The link between the slot state an advance writes and the two steps of the reference that read the SESSION LIST:
+ * apply_minimum_charging_rate (ada.py:147-150), a greedy walk in arrival order, and diff_based_reallocation
+ * (post.py:214-218), whose round robin breaks ties of the rounding loss by list order.  The slot state carries no order:
+ * the caller states it, as key[b][i] = the list position of the session on EVSE i of problem b.  The entry runs on the
+ * problems `cur` an advance just wrote, before they are solved.  K = 1 only (online MPC: one session per EVSE).
+ * A slot is LIVE when s_len > 0 and PRESENT when it is live and s_off == 0.  For every problem b, in this order:
+ *    1  order: the live slots in ascending (key[i], i).  Comparisons only; key is read only where the slot is live.
+ *    2  minimum rates, when min_pilot is given (acn.apply_minimum_charging_rate with its default override): with
+ *       w = 0 [N], the present slots are visited in the order of rule 1.  A visit sets want = min_pilot[i], w[i] = want and
+ *       tests  s_cap[i] >= want  and, for every row j,  re_j^2 + im_j^2 <= (limits_j + 1e-7)^2  with
+ *       re_j = sum_i cre[j][i] w[i] (im_j likewise): the sums over increasing i, every product and every sum rounded once
+ *       (no fused multiply-add, no square root) -- the acceptance test of the pilots entry without its peak term.
+ *       Accepted:  lb[i][0] = max(want, lb[i][0]), then ub[i][0] = (ub[i][0] < lb[i][0] ? lb[i][0] : ub[i][0]).
+ *       Refused:   w[i] = 0 and lb[i][0] = ub[i][0] = 0.
+ *       Only period 0 of lb and ub is touched, and only of present slots.
+ *    3  the session view, when wanted: positions b*N + r, r = 0 .. N-1 -- first the live slots in the order of rule 1, then
+ *       the EVSEs without a live slot in increasing i.  v_evse = the EVSE, v_arrived = present,
+ *       v_cap = present ? min(s_cap[i], ub'[i][0]) : 0 with ub' as rule 2 left it (max_pilot is inside ub already).  These
+ *       are s_evse, s_arrived and s_cap of acnqp_pilot_plan with the constant sess_seg[b] = b*N.
+ *    4  flags[b] is written for every problem: bit 1 when a live slot has s_off > 0 (no state of online MPC; the slot is
+ *       left untouched by rule 2 and is not present in rule 3), else 0.
+ * tests/prepare_spec.py states the rules in plain loops and the library returns its bits.  No atomics; every view element
+ * is written whatever the input; a problem gives the same bits alone and at any position of any batch.                 */
+#define ACNQP_PREPARE_FUTURE 1   /* flags: a live slot with s_off > 0 */
+
+typedef struct {
+  int32_t n_evse;           /* N: must be the handle's                                                                */
+  int32_t n_infra;          /* M: must be the handle's                                                                */
+  const int32_t* key;       /* [B*N]  list position of the session on EVSE i (read where the slot is live)            */
+  const double* cre;        /* [M*N]  the site in the SOC form of acnqp_pilot_plan; read only with min_pilot          */
+  const double* cim;        /* [M*N]                                                                                  */
+  const double* limits;     /* [M]                                                                                    */
+  const double* min_pilot;  /* [N] or NULL: no rule 2                                                                 */
+} acnqp_prepare_plan;
+
+typedef struct {
+  int32_t* v_evse;     /* [B*N]                                                                                       */
+  uint8_t* v_arrived;  /* [B*N]                                                                                       */
+  double* v_cap;       /* [B*N]   all three or none (none: the view is not wanted)                                    */
+} acnqp_prepare_view;
+
+/* acnqp_prepare_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns without
+ * synchronising.  cur: batch, t_max, k_sessions and s_off, s_len, s_cap are read (its lb / ub are not: they are const);
+ * lb, ub [B*N*Tm] are the writable bounds of the same problems; view may be NULL.  A null handle or argument, n_evse or
+ * n_infra other than the handle's, k_sessions != 1, a shape out of range, a view with a missing array, min_pilot without
+ * the site arrays, or an output (lb, ub, the view, flags) that overlaps an input or another output return
+ * ACNQP_ERR_INVALID with acnqp_last_error set, before any device work.                                               */
+int acnqp_prepare_device(acnqp_handle* h, const acnqp_problems* cur, const acnqp_prepare_plan* plan, double* lb, double* ub,
+                         acnqp_prepare_view* view, int32_t* flags, void* hip_stream);
+
+/* acnqp_prepare_host -- the same with host pointers, synchronous; a large batch is processed in chunks.  Same bits as
+ * the device entry.                                                                                                  */
+int acnqp_prepare_host(acnqp_handle* h, const acnqp_problems* cur, const acnqp_prepare_plan* plan, double* lb, double* ub,
+                       acnqp_prepare_view* view, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif
