@@ -228,7 +228,8 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
     real yv = 0;
     if (warm) {
       const int ja = A.rowabi[r];
-      if (ja >= 0) yv = (real)A.warm_y[((size_t)b * A.Mg + ja) * T + t] / static_cast<const real*>(A.rowscale)[r];
+      // (warm_y reads as zero at the dead periods t >= horizon[b]: include/acn_qp.h)
+      if (ja >= 0 && t < A.horizon[b]) yv = (real)A.warm_y[((size_t)b * A.Mg + ja) * T + t] / static_cast<const real*>(A.rowscale)[r];
     }
     z2[k] = acc; gx[k] = acc; y2[k] = yv; w[k] = rho * acc - yv;
     if (aa_m > 0) { uprev[n + k] = acc + yv / rho; fprev[n + k] = 0; cprev[n + k] = 0.f; }

@@ -586,7 +586,8 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
       if (warm) {
         const int j = 16 * mo + M::rowof(g, r), tt = 16 * c + t;
         const int ja = A.rowabi[j];
-        if (ja >= 0 && tt < Tm) yv = A.warm_y[((size_t)b * A.Mg + ja) * Tm + tt] / static_cast<const real*>(A.rowscale)[j];
+        // (warm_y reads as zero at the dead periods t >= horizon[b]: include/acn_qp.h)
+        if (ja >= 0 && tt < min(A.horizon[b], Tm)) yv = A.warm_y[((size_t)b * A.Mg + ja) * Tm + tt] / static_cast<const real*>(A.rowscale)[j];
       }
       Z2[i] = zt[r]; GX[i] = zt[r]; Y2[i] = yv;
     }

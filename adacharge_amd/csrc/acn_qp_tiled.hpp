@@ -567,13 +567,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void admm_tiled_kernel(const TiledArg
       vec4 gty = {0, 0, 0, 0};
       if (warm) {
         const real* RS = static_cast<const real*>(A.rowscale);
+        const int Th = min(A.horizon[b], Tm);   // warm_y reads as zero at the dead periods t >= horizon[b] (include/acn_qp.h)
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int j = 16 * m + M::rowof(g, r), tt = 16 * c + t;
             const int ja = A.rowabi[j];
-            const bool ok = ja >= 0 && tt < Tm;
+            const bool ok = ja >= 0 && tt < Th;
             y2[m][c][r] = ok ? (real)A.warm_y[((size_t)b * A.Mg + (ok ? ja : 0)) * Tm + (ok ? tt : 0)] / RS[j] : (real)0;
           }
 #pragma unroll

@@ -641,12 +641,13 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     for (int t = 0; t < TS; ++t) gty[t] = 0;
     if (warm) {
       const real* RS = static_cast<const real*>(A.rowscale);
+      const int Th = min(A.horizon[b], Tm);   // warm_y reads as zero at the dead periods t >= horizon[b] (include/acn_qp.h)
       vec4 yv[MT];
 #pragma unroll
       for (int r = 0; r < SR; ++r) {
         const int j = 16 * (r >> 2) + M::rowof(g, r & 3);
         const int ja = A.rowabi[j];
-        const bool ok = ja >= 0 && tc < TS && tb + tc < Tm;
+        const bool ok = ja >= 0 && tc < TS && tb + tc < Th;
         y2[r] = ok ? A.warm_y[((size_t)b * A.Mg + (ok ? ja : 0)) * Tm + (ok ? tb + tc : 0)] / RS[j] : 0.0;
         yv[r >> 2][r & 3] = y2[r];
       }

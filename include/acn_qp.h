@@ -131,7 +131,9 @@ typedef struct {
    * z = Proj(warm_x), y2 = warm_y and the multipliers of the box / energy set that make the pair stationary,
    * y1 = -(P z + q + G' y2).  The optimum does not depend on it; the iteration count does.                       */
   const double* warm_x;    /* [B*N*Tm] or NULL                                                        */
-  const double* warm_y;    /* [B*n_rows*Tm] or NULL: multipliers of the rows of acnqp_site.G, per period */
+  const double* warm_y;    /* [B*n_rows*Tm] or NULL: multipliers of the rows of acnqp_site.G, per period.
+                              Read as zero at t >= horizon[b], whatever is stored there (a shifted y of a longer
+                              horizon may leave entries behind): y stays exactly zero at dead periods            */
 } acnqp_problems;
 
 typedef struct {

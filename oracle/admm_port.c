@@ -184,7 +184,7 @@ static int solve_one(const port_site* S, const port_opts* O, int horizon, const 
    * cost vector prefers, inside its bounds and energy row), with the multiplier that makes it stationary,
    * y1 = -(q + pd z1); site rows at z2 = G z1, y2 = 0.  Exact when no site row binds. */
   /* Warm start (optional; acn_qp_tiled.hpp): z1 = Proj_B(warm_x), y2 = warm_y (already in this solver's row scaling),
-   * y1 = -(q + pd z1 + G' y2) */
+   * y1 = -(q + pd z1 + G' y2).  warm_y reads as zero at the dead periods t >= horizon (include/acn_qp.h) */
   const int warm = warm_x != 0 && warm_y != 0;
   for (int k = 0; k < n; ++k) { zh[k] = warm ? warm_x[k] : -kStartGain * q[k]; z1[k] = clip(zh[k], lb[k], ub[k]); }
   for (int k = 0; k < K; ++k)
@@ -196,7 +196,9 @@ static int solve_one(const port_site* S, const port_opts* O, int horizon, const 
                        shi[k * N + i], &m0, z1 + i * T + o);
       }
     }
-  if (warm) memcpy(y2, warm_y, sizeof(double) * mt);
+  if (warm)
+    for (int j = 0; j < Mg; ++j)
+      for (int t = 0; t < T && t < horizon; ++t) y2[j * T + t] = warm_y[j * T + t];
   for (int i = 0; i < N; ++i)
     for (int t = 0; t < T; ++t) {
       const int k = i * T + t;

@@ -238,9 +238,10 @@ def _certifies_infeasibility(v1, v2, G, limits, peak_b, site, lb, ub, s_off, s_l
     return bool(ssum < -vtol)
 
 
-def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
+def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None, warm_x=None, warm_y=None):
     """Run the ADMM on problem ``b`` of a builder.ProblemBatch-like object.
-    Returns dict(x (N,Tm), status, iters, pri_res, dua_res, obj, rho)."""
+    ``warm_x`` (N, Tm) and ``warm_y`` (Mg, Tm; rows and units of ``site.G``): optional warm start (both or neither), as
+    include/acn_qp.h states it.  Returns dict(x (N,Tm), y (Mg,Tm), status, iters, pri_res, dua_res, obj, rho)."""
     site = batch.site
     N, Tm, T = site.N, batch.Tm, int(batch.T[b])
     if batch.presolve_status is not None and batch.presolve_status[b]:
@@ -267,9 +268,11 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
     G, Gh, lam, Q, limits = site.G, site.Ghat, site.lam, site.Q, site.limits
     peak_b = batch.peak[b] if batch.peak is not None else None
     lf_b = float(batch.lf[b])
+    row_scale = np.ones(np.shape(G)[0])   # multipliers: caller's units = row_scale * this solver's units
     if opts.equilibrate:
         from .admm_port import equilibrated
         G, Gh, Q, lam, limits, pk_s, fl_s, _ = equilibrated(site)
+        row_scale = equilibrated.last_scale
         peak_b = None if peak_b is None else peak_b * pk_s
         lf_b /= fl_s * fl_s
     Mg = G.shape[0]
@@ -277,11 +280,21 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
     rho = opts.rho
     # start: the schedule that ignores the site rows, z1 = Proj_B(-START_GAIN q), with the multiplier that
     # makes it stationary, y1 = -(q + pdiag z1); site rows at z2 = G z1, y2 = 0 (exact when no site row binds)
-    z1 = _project_B(-START_GAIN * q, lb, ub, batch.s_off[b], batch.s_len[b], batch.s_cap[b], eq)
+    if (warm_x is None) != (warm_y is None):
+        raise ValueError("warm_x and warm_y go together (both or neither)")
+    if warm_x is None:
+        z1 = _project_B(-START_GAIN * q, lb, ub, batch.s_off[b], batch.s_len[b], batch.s_cap[b], eq)
+        y2 = np.zeros((Mg, Tm))
+        y1 = -(q + pdiag * z1)
+    else:
+        # include/acn_qp.h, acnqp_problems: "starts from z = Proj(warm_x), y2 = warm_y and the multipliers of the box /
+        # energy set that make the pair stationary, y1 = -(P z + q + G' y2)"; warm_y reads as zero at t >= horizon[b]
+        z1 = _project_B(np.array(warm_x, dtype=float), lb, ub, batch.s_off[b], batch.s_len[b], batch.s_cap[b], eq)
+        y2 = np.array(warm_y, dtype=float).reshape(Mg, Tm) / row_scale[:, None]
+        y2[:, T:] = 0.0
+        y1 = -(pdiag * z1 + q + G.T @ y2)
     x = z1.copy()
-    y1 = -(q + pdiag * z1)
     z2 = G @ z1
-    y2 = np.zeros((Mg, Tm))
     Gx = z2.copy()
     status = ST_MAX_ITER
     pri = dua = np.inf
@@ -291,7 +304,7 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
     y_prev = None   # (y1, y2) at the previous check: the infeasibility certificate tests their difference
     aa = _Anderson(opts.accel_mem, N * Tm + Mg * Tm) if opts.accel_mem > 0 else None
     if aa is not None:
-        aa.uprev = np.concatenate([(z1 + y1 / rho).ravel(), z2.ravel()])
+        aa.uprev = np.concatenate([(z1 + y1 / rho).ravel(), (z2 + y2 / rho).ravel()])
     for it in range(1, opts.max_iter + 1):
         a = sig + pdiag + rho
         r0 = sig * x - q + rho * z1 - y1
@@ -355,4 +368,4 @@ def solve_one(batch, b, opts: AdmmOptions = AdmmOptions(), trace=None):
     # the feasible iterate is z1 (it satisfies bounds and energy rows exactly)
     xs = z1
     obj = 0.5 * pdiag * (xs * xs).sum() + (q * xs).sum()
-    return dict(x=xs, xraw=x, status=status, iters=it, pri_res=pri, dua_res=dua, obj=obj, rho=rho)
+    return dict(x=xs, xraw=x, y=y2 * row_scale[:, None], status=status, iters=it, pri_res=pri, dua_res=dua, obj=obj, rho=rho)

@@ -334,11 +334,13 @@ def device_outputs(dev):
     return {k: getattr(dev, k).cpu().numpy() for k in ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")}
 
 
-def launch_poisoned(h, batch, options=None):
-    """one launch through the device entry with every output poisoned (NaN, iters -1); returns host arrays"""
+def launch_poisoned(h, batch, options=None, warm=None):
+    """one launch through the device entry with every output poisoned (NaN, iters -1); returns host arrays.
+    ``warm = (x0, y0)``: host arrays (B, N, Tm) and (B, Mg, Tm) of a warm start, uploaded as device tensors"""
     import torch
 
     dev = poisoned_device_batch(batch)
-    h.solve_device(dev, options, stream=torch.cuda.current_stream().cuda_stream)
+    wx, wy = (None, None) if warm is None else (torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to("cuda:0") for a in warm)
+    h.solve_device(dev, options, stream=torch.cuda.current_stream().cuda_stream, warm_x=wx, warm_y=wy)
     torch.cuda.synchronize()
     return device_outputs(dev)
