@@ -260,7 +260,8 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
                 out[k] = {sid: rj[i] for i, sid in enumerate(ids)}
         return out
 
-    def simulate_batch(self, fleets, steps, start_time=0, warm_start=False, return_schedules=False, observer=None, session_order=None):
+    def simulate_batch(self, fleets, steps, start_time=0, warm_start=False, return_schedules=False, observer=None, session_order=None,
+                       prices=None):
         """Closed-loop extension: ``steps`` control periods of B scenarios of this site (``fleets``: one list of EV records
         per scenario, or a ``rollout.FleetTable``) with the whole state resident in HBM.  On one stream, per period:
         ``solve_device -> pilots_device (first period) -> advance_device``, with no host synchronisation inside the loop; an
@@ -272,12 +273,17 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         ``session_order="fleet"`` (a session stands where its record stands in its fleet) or ``"arrival"`` (plug-in order).
         Then ``uninterrupted_charging`` and ``reallocate`` are served (``acnqp_prepare_device`` between the advance and the
         solve; the result carries ``visits`` and ``prepare_flags``); ``estimate_max_rate`` is refused either way.
+        One objective that reads the clock is served: ``tou_energy_cost`` (at most one component; keep it LAST in the list and
+        every problem of the loop is the builder's bit for bit, ``rollout.FleetTable``).  The advance prices each new problem
+        from ``interface.get_prices(steps + t_max, start_time)``, or from ``prices`` -- ``(P,)`` or ``(B, P)``, entry 0 the price
+        of period ``start_time``, one tariff per scenario (with a ``FleetTable`` the table's own ``prices`` hold) -- and the result
+        carries ``energy_cost (B,)``.  Every other objective that reads the clock raises ``ValueError``.
         ``warm_start``: every solve but the first starts from the previous
         period's schedule and multipliers, shifted on the device.  ``observer(step, state, pilots)``: diagnostic hook called
         after each period's solve has been enqueued (it may synchronise and read the ``DeviceBatch``)."""
         from .rollout import simulate
 
-        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer, session_order)
+        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer, session_order, prices)
 
 
 class AdaptiveChargingAlgorithmOffline(BaseAlgorithm):

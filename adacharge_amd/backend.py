@@ -129,6 +129,12 @@ class _AdvancePlan(C.Structure):
                                   "a_rate_seg", "a_min", "a_max")]
 
 
+class ClockCost(C.Structure):
+    """Mirror of ``acnqp_clock_cost`` (include/acn_qp.h): the clock cost of the advance's rule 6b."""
+
+    _fields_ = [("n_evse", C.c_int32), ("series_len", C.c_int32), ("coef", C.c_double), ("weight", C.c_void_p), ("series", C.c_void_p)]
+
+
 class _Next(C.Structure):
     """Mirror of ``acnqp_next`` (include/acn_qp.h)."""
 
@@ -206,6 +212,8 @@ EXPORTED_SYMBOLS = (
     "acnqp_pilots_host",
     "acnqp_advance_device",
     "acnqp_advance_host",
+    "acnqp_advance_priced_device",
+    "acnqp_advance_priced_host",
     "acnqp_prepare_device",
     "acnqp_prepare_host",
 )
@@ -297,6 +305,12 @@ def load_library():
     lib.acnqp_advance_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(_AdvancePlan), C.POINTER(_Next), C.c_void_p]
     lib.acnqp_advance_host.restype = C.c_int
+    lib.acnqp_advance_priced_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(_AdvancePlan), C.POINTER(ClockCost), C.POINTER(_Next), C.c_void_p, C.c_void_p]
+    lib.acnqp_advance_priced_device.restype = C.c_int
+    lib.acnqp_advance_priced_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(_AdvancePlan), C.POINTER(ClockCost), C.POINTER(_Next), C.c_void_p]
+    lib.acnqp_advance_priced_host.restype = C.c_int
     lib.acnqp_prepare_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(_PreparePlan), C.c_void_p, C.c_void_p,
                                          C.POINTER(_PrepareView), C.c_void_p, C.c_void_p]
     lib.acnqp_prepare_device.restype = C.c_int
@@ -407,7 +421,9 @@ class PilotPlan:
 class AdvancePlan:
     """The arrays of ``acnqp_advance_plan`` (include/acn_qp.h): numpy arrays for ``SiteHandle.advance``, torch tensors on the
     handle's GPU (``to_device``) for ``SiteHandle.advance_device``.  ``a_seg`` may hold one row of B + 1 entries per step
-    (``(steps, B + 1)``, absolute record indices): ``seg_row`` picks the step's.  ``rollout.FleetTable`` builds one."""
+    (``(steps, B + 1)``, absolute record indices): ``seg_row`` picks the step's.  ``rollout.FleetTable`` builds one.
+    ``c_coef, c_weight, c_series``: the clock cost of rule 6b (``acnqp_clock_cost``); all None is the plain advance, all
+    given goes through ``acnqp_advance_priced_device / _host``."""
     q_table: object                       # (H, N, Tm)
     h_scal: object                        # (H, 3) pdiag, lf, dc
     h_row: object                         # (Tm + 1,) int32
@@ -423,7 +439,11 @@ class AdvancePlan:
     a_min: Optional[object] = None        # (R,)
     a_max: Optional[object] = None
     warm_arrival_gain: float = 0.0        # rule 9: != 0 starts an admitted session at -gain * q' instead of the shifted x
+    c_coef: Optional[float] = None        # rule 6b: q' += c_coef * (c_weight[i] * c_series[b][step + 1 + t])
+    c_weight: Optional[object] = None     # (N,)
+    c_series: Optional[object] = None     # (B, P)
 
+    _COST = ("c_weight", "c_series")
     _ARRAYS = ("q_table", "h_scal", "h_row", "peak_series", "a_seg", "a_evse", "a_slot", "a_len", "a_cap", "a_rate_seg", "a_min", "a_max")
     _INT = ("h_row", "a_seg", "a_evse", "a_slot", "a_len", "a_rate_seg")
 
@@ -434,7 +454,10 @@ class AdvancePlan:
         for k in self._ARRAYS:
             a = getattr(self, k)
             moved[k] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int32 if k in self._INT else np.float64)).to(device)
-        return AdvancePlan(done_tol=self.done_tol, kw_per_amp=self.kw_per_amp, warm_arrival_gain=self.warm_arrival_gain, **moved)
+        for k in self._COST:
+            a = getattr(self, k)
+            moved[k] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(device)
+        return AdvancePlan(done_tol=self.done_tol, kw_per_amp=self.kw_per_amp, warm_arrival_gain=self.warm_arrival_gain, c_coef=self.c_coef, **moved)
 
     def _struct(self, N: int, Mg: int, step: int, seg_row: int = 0, keep=None) -> "_AdvancePlan":
         def ptr(k, row=None):
@@ -457,6 +480,29 @@ class AdvancePlan:
                             float(self.warm_arrival_gain),
                             ptr("q_table"), ptr("h_scal"), ptr("h_row"), ptr("peak_series"), ptr("a_seg", seg_row) if A else None,
                             ptr("a_evse"), ptr("a_slot"), ptr("a_len"), ptr("a_cap"), ptr("a_rate_seg"), ptr("a_min"), ptr("a_max"))
+
+    def _cost_struct(self, N: int, keep=None) -> Optional["ClockCost"]:
+        """the ``acnqp_clock_cost`` of the plan, or None (the plain advance) when no c_ field is set"""
+        given = [self.c_coef is not None, self.c_weight is not None, self.c_series is not None]
+        if not any(given):
+            return None
+        if not all(given):
+            raise ValueError("a clock cost needs c_coef, c_weight and c_series")
+        if self.c_series.ndim != 2:
+            raise ValueError("c_series must have shape (B, P)")
+        ptrs = []
+        for k in self._COST:
+            a = getattr(self, k)
+            if hasattr(a, "data_ptr"):
+                if a.element_size() != 8 or not a.is_contiguous():
+                    raise ValueError(f"{k} must be a contiguous float64 tensor")
+                ptrs.append(C.c_void_p(a.data_ptr()) if a.numel() else None)
+            else:
+                a = np.ascontiguousarray(a, np.float64)
+                if keep is not None:
+                    keep.append(a)
+                ptrs.append(_ptr(a) if a.size else None)
+        return ClockCost(int(N), int(self.c_series.shape[1]), float(self.c_coef), *ptrs)
 
 
 @dataclass
@@ -880,8 +926,15 @@ class SiteHandle:
         keep = []
         pl = plan._struct(N, Mg, step, seg_row, keep)
         nx = _Next(*[_ptr(out[k]) for k in self._NEXT + ("warm_x", "warm_y")])
-        _check(self._lib.acnqp_advance_host(self._h, C.byref(p), _ptr(app), _ptr(stat), _ptr(xs), _ptr(ys), C.byref(pl), C.byref(nx),
-                                            _ptr(flags)), "acnqp_advance_host")
+        cost = plan._cost_struct(N, keep)
+        if cost is not None and plan.c_series.shape[0] != B:
+            raise ValueError(f"c_series has {plan.c_series.shape[0]} rows, the batch has {B} problems")
+        if cost is None:
+            _check(self._lib.acnqp_advance_host(self._h, C.byref(p), _ptr(app), _ptr(stat), _ptr(xs), _ptr(ys), C.byref(pl), C.byref(nx),
+                                                _ptr(flags)), "acnqp_advance_host")
+        else:
+            _check(self._lib.acnqp_advance_priced_host(self._h, C.byref(p), _ptr(app), _ptr(stat), _ptr(xs), _ptr(ys), C.byref(pl),
+                                                       C.byref(cost), C.byref(nx), _ptr(flags)), "acnqp_advance_priced_host")
         del keep
         out["flags"] = flags
         return {k: v for k, v in out.items() if v is not None}
@@ -905,9 +958,16 @@ class SiteHandle:
                       _dptr(cur.s_len), _dptr(cur.s_cap), _dptr(cur.s_eq), _dptr(cur.peak), _dptr(cur.lf), _dptr(cur.dc), _dptr(cur.dfloor), None, None)
         pl = plan._struct(cur.N, self.site.Mg, step, seg_row)
         nx = _Next(*[_dptr(getattr(nxt, k)) for k in self._NEXT], _dptr(warm_x), _dptr(warm_y))
-        _check(self._lib.acnqp_advance_device(self._h, C.byref(p), _dptr(applied), _dptr(cur.status) if use_status else None,
-                                              _dptr(cur.x) if warm_x is not None else None, _dptr(cur.y) if warm_y is not None else None,
-                                              C.byref(pl), C.byref(nx), _dptr(flags), C.c_void_p(stream)), "acnqp_advance_device")
+        cost = plan._cost_struct(cur.N)
+        if cost is not None and plan.c_series.shape[0] != cur.B:
+            raise ValueError(f"c_series has {plan.c_series.shape[0]} rows, the batch has {cur.B} problems")
+        head = (self._h, C.byref(p), _dptr(applied), _dptr(cur.status) if use_status else None,
+                _dptr(cur.x) if warm_x is not None else None, _dptr(cur.y) if warm_y is not None else None, C.byref(pl))
+        if cost is None:
+            _check(self._lib.acnqp_advance_device(*head, C.byref(nx), _dptr(flags), C.c_void_p(stream)), "acnqp_advance_device")
+        else:
+            _check(self._lib.acnqp_advance_priced_device(*head, C.byref(cost), C.byref(nx), _dptr(flags), C.c_void_p(stream)),
+                   "acnqp_advance_priced_device")
 
     # -- before the solve (acn_qp_prepare.hpp) ---------------------------------------------------------------------------
     def prepare_host(self, cur: dict, plan: PreparePlan, want_view: bool = True, min_rates: bool = True, key_row=None) -> dict:

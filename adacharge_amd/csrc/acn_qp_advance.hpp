@@ -21,6 +21,10 @@
 // Every index that comes from caller data is range-checked before use; a bad record raises a flag and is skipped.  No
 // atomics; every output element is written whatever the input; a problem gives the same bits alone and at any position of
 // any batch.
+//
+// With a clock cost (acnqp_advance_priced_device / _host, rule 6b; spec tests/advance_priced_spec.py) the CLOCK
+// instantiations add coef * (weight[i] * series[b][step + 1 + t]) to q' inside the new horizon: two products and one sum
+// per entry, each rounded once -- the builder's q of an objective whose last component is coef * tou_energy_cost.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,6 +67,11 @@ struct AdvanceArgs {
   double* n_peak;                          // [B][Tm] or nullptr
   double *n_wx, *n_wy;                     // or nullptr
   int32_t* flags;                          // [B]
+  // the clock cost (rule 6b), read by the CLOCK instantiations only
+  int c_P = 0;                             // series length
+  double c_coef = 0.0;
+  const double* c_weight = nullptr;        // [N]
+  const double* c_series = nullptr;        // [B][c_P]
 };
 
 inline int advance_threads(int N) { return N <= 64 ? 64 : 256; }
@@ -70,7 +79,9 @@ inline size_t advance_lds(int N) { return ((size_t)N * 12 + 15) & ~(size_t)15; }
 
 constexpr double kAdvanceInf = __builtin_huge_val();
 
-template <int THREADS>
+// CLOCK: the variant with rule 6b, q' = q_table[row] + c_coef * (c_weight[i] * c_series[b][step + 1 + t]) for t < horizon'
+// (three operations, each rounded once), and rule 9 on that q'.  The plain variant reads none of the c_ fields.
+template <int THREADS, bool CLOCK = false>
 __global__ __launch_bounds__(THREADS) void advance_kernel(const AdvanceArgs A) {
 #pragma clang fp contract(off)   // every operation of this kernel is rounded once (tests/advance_spec.py)
   extern __shared__ __attribute__((aligned(16))) char advance_lds_raw[];
@@ -205,21 +216,39 @@ __global__ __launch_bounds__(THREADS) void advance_kernel(const AdvanceArgs A) {
   flag = red_or[0];
   int row = A.h_row[hz];
   if (row < 0 || row >= A.H) { row = -1; flag |= kAdvanceNoRow; }
-  {
-    double* nq = A.n_q + pb;
-    if (row >= 0) {
-      const double* q = A.q_table + (size_t)row * n;
-      for (int k = gt; k < n; k += THREADS) nq[k] = q[k];
-    } else {
-      for (int k = gt; k < n; k += THREADS) nq[k] = 0.0;
-    }
-  }
-  if (A.n_wx && A.warm_gain != 0.0) {   // rule 9: a session admitted now starts where a cold solve would start it
+  if constexpr (CLOCK) {   // rules 6, 6b and 9: one thread writes q'[k] and, for a session admitted now, warm_x'[k] from it
     const double* q = row >= 0 ? A.q_table + (size_t)row * n : nullptr;
-    double* wx = A.n_wx + pb;
+    const double* cs = A.c_series + (size_t)b * A.c_P + (A.step + 1);   // (t < hz <= Tm: inside the entry's series_len check)
+    const bool start = A.n_wx && A.warm_gain != 0.0;
     const double g = -A.warm_gain;
-    for (int k = gt; k < n; k += THREADS)
-      if (k % Tm < fresh[k / Tm]) wx[k] = g * (q ? q[k] : 0.0);
+    double* nq = A.n_q + pb;
+    for (int k = gt; k < n; k += THREADS) {
+      const int i = k / Tm, t = k % Tm;
+      double v = 0.0;
+      if (q) {
+        v = q[k];
+        if (t < hz) v = v + A.c_coef * (A.c_weight[i] * cs[t]);
+      }
+      nq[k] = v;
+      if (start && t < fresh[i]) A.n_wx[pb + k] = g * v;
+    }
+  } else {
+    {
+      double* nq = A.n_q + pb;
+      if (row >= 0) {
+        const double* q = A.q_table + (size_t)row * n;
+        for (int k = gt; k < n; k += THREADS) nq[k] = q[k];
+      } else {
+        for (int k = gt; k < n; k += THREADS) nq[k] = 0.0;
+      }
+    }
+    if (A.n_wx && A.warm_gain != 0.0) {   // rule 9: a session admitted now starts where a cold solve would start it
+      const double* q = row >= 0 ? A.q_table + (size_t)row * n : nullptr;
+      double* wx = A.n_wx + pb;
+      const double g = -A.warm_gain;
+      for (int k = gt; k < n; k += THREADS)
+        if (k % Tm < fresh[k / Tm]) wx[k] = g * (q ? q[k] : 0.0);
+    }
   }
   if (A.n_peak) {
     const double* ps = A.peak_series ? A.peak_series + (size_t)b * A.P + (A.step + 1) : nullptr;
@@ -241,6 +270,6 @@ __global__ __launch_bounds__(THREADS) void advance_kernel(const AdvanceArgs A) {
   }
 }
 
-hipError_t launch_advance(const AdvanceArgs& a, hipStream_t st);
+hipError_t launch_advance(const AdvanceArgs& a, hipStream_t st);   // the CLOCK variant iff a.c_series is given
 
 }  // namespace acnqp

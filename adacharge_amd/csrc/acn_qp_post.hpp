@@ -241,14 +241,22 @@ int acnqp_pilots_host(acnqp_handle* h, const acnqp_pilot_plan* pl, const double*
 
 // ---- time passes (acn_qp_advance.hpp) ---------------------------------------------------------------------------------
 static int check_advance_args(const acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
-                              const double* y, const acnqp_advance_plan* pl, const acnqp_next* nx, const int32_t* flags,
-                              const char* who) {
+                              const double* y, const acnqp_advance_plan* pl, const acnqp_clock_cost* cost, const acnqp_next* nx,
+                              const int32_t* flags, const char* who) {
   const std::string w(who);
   if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
   if (!c || !pl || !nx) return fail(ACNQP_ERR_INVALID, w + ": null argument");
   if (pl->n_evse != h->shape.N || pl->n_rows != h->shape.Mg)
     return fail(ACNQP_ERR_INVALID, w + ": the plan is for " + std::to_string(pl->n_evse) + " EVSEs and " + std::to_string(pl->n_rows) +
                                        " site rows, the handle's site has " + std::to_string(h->shape.N) + " and " + std::to_string(h->shape.Mg));
+  if (cost) {   // rule 6b
+    if (cost->n_evse != h->shape.N)
+      return fail(ACNQP_ERR_INVALID, w + ": the clock cost is for " + std::to_string(cost->n_evse) + " EVSEs, the handle's site has " + std::to_string(h->shape.N));
+    if (!cost->weight || !cost->series) return fail(ACNQP_ERR_INVALID, w + ": null weight or series of the clock cost");
+    uint64_t u;   // by its bits: this file is compiled with -fno-honor-nans, which may fold a floating-point test away
+    std::memcpy(&u, &cost->coef, sizeof u);
+    if ((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull) return fail(ACNQP_ERR_INVALID, w + ": the clock cost's coef is not finite");
+  }
   if (c->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
   if (c->batch == 0) return ACNQP_OK;
   if (c->t_max < 1 || c->t_max > 4096) return fail(ACNQP_ERR_INVALID, w + ": t_max must be in [1, 4096]");
@@ -274,13 +282,18 @@ static int check_advance_args(const acnqp_handle* h, const acnqp_problems* c, co
   if (pl->peak_series && h->shape.has_peak && (long long)pl->peak_len < (long long)pl->step + 1 + c->t_max)
     return fail(ACNQP_ERR_INVALID, w + ": peak_len is " + std::to_string(pl->peak_len) + ", rule 7 reads step + 1 + t_max = " +
                                        std::to_string((long long)pl->step + 1 + c->t_max) + " entries");
+  if (cost && (long long)cost->series_len < (long long)pl->step + 1 + c->t_max)
+    return fail(ACNQP_ERR_INVALID, w + ": series_len is " + std::to_string(cost->series_len) + ", rule 6b reads step + 1 + t_max = " +
+                                       std::to_string((long long)pl->step + 1 + c->t_max) + " entries");
   // nothing written may overlap anything read or anything else written: the kernel reads period t + 1 of an array while
   // other threads write period t, and its phases overwrite one another's output
   struct Span { const void* p; size_t n; const char* name; };
   const size_t nb = B * N * Tm * 8, ns4 = B * K * N * 4, ns8 = B * K * N * 8, ny = B * Mg * Tm * 8;
   const Span in[] = {{c->lb, nb, "lb"}, {c->ub, nb, "ub"}, {c->s_off, ns4, "s_off"}, {c->s_len, ns4, "s_len"}, {c->s_cap, ns8, "s_cap"},
                      {h->shape.has_max ? c->dfloor : nullptr, B * 8, "dfloor"}, {applied, B * N * 8, "applied"}, {status, B * 4, "status"},
-                     {nx->warm_x ? x : nullptr, nb, "x"}, {nx->warm_y ? y : nullptr, ny, "y"}};
+                     {nx->warm_x ? x : nullptr, nb, "x"}, {nx->warm_y ? y : nullptr, ny, "y"},
+                     {cost ? cost->weight : nullptr, N * 8, "cost->weight"},
+                     {cost ? cost->series : nullptr, cost ? B * (size_t)cost->series_len * 8 : 0, "cost->series"}};
   const Span out[] = {{nx->horizon, B * 4, "horizon"}, {nx->lb, nb, "lb"}, {nx->ub, nb, "ub"}, {nx->q, nb, "q"}, {nx->pdiag, B * 8, "pdiag"},
                       {nx->s_off, ns4, "s_off"}, {nx->s_len, ns4, "s_len"}, {nx->s_cap, ns8, "s_cap"},
                       {h->shape.has_peak ? nx->peak : nullptr, B * Tm * 8, "peak"}, {h->shape.has_flat ? nx->lf : nullptr, B * 8, "lf"},
@@ -298,9 +311,10 @@ static int check_advance_args(const acnqp_handle* h, const acnqp_problems* c, co
   return ACNQP_OK;
 }
 
-int acnqp_advance_device(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
-                         const double* y, const acnqp_advance_plan* pl, acnqp_next* nx, int32_t* flags, void* hip_stream) {
-  const int rc = check_advance_args(h, c, applied, status, x, y, pl, nx, flags, "acnqp_advance_device");
+int acnqp_advance_priced_device(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
+                                const double* y, const acnqp_advance_plan* pl, const acnqp_clock_cost* cost, acnqp_next* nx, int32_t* flags,
+                                void* hip_stream) {
+  const int rc = check_advance_args(h, c, applied, status, x, y, pl, cost, nx, flags, cost ? "acnqp_advance_priced_device" : "acnqp_advance_device");
   if (rc != ACNQP_OK || c->batch == 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   acnqp::AdvanceArgs a;
@@ -324,29 +338,38 @@ int acnqp_advance_device(acnqp_handle* h, const acnqp_problems* c, const double*
   a.n_wx = nx->warm_x;
   a.n_wy = h->shape.Mg > 0 ? nx->warm_y : nullptr;
   a.flags = flags;
+  if (cost) { a.c_P = cost->series_len; a.c_coef = cost->coef; a.c_weight = cost->weight; a.c_series = cost->series; }
   (void)hipGetLastError();
   const hipError_t e = acnqp::launch_advance(a, reinterpret_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("advance kernel launch: ") + hipGetErrorString(e));
   return ACNQP_OK;
 }
 
-int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
-                       const double* y, const acnqp_advance_plan* pl, acnqp_next* nx, int32_t* flags) {
-  const int rc = check_advance_args(h, c, applied, status, x, y, pl, nx, flags, "acnqp_advance_host");
+int acnqp_advance_device(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
+                         const double* y, const acnqp_advance_plan* pl, acnqp_next* nx, int32_t* flags, void* hip_stream) {
+  return acnqp_advance_priced_device(h, c, applied, status, x, y, pl, nullptr, nx, flags, hip_stream);
+}
+
+int acnqp_advance_priced_host(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
+                              const double* y, const acnqp_advance_plan* pl, const acnqp_clock_cost* cost, acnqp_next* nx, int32_t* flags) {
+  const int rc = check_advance_args(h, c, applied, status, x, y, pl, cost, nx, flags, cost ? "acnqp_advance_priced_host" : "acnqp_advance_host");
   if (rc != ACNQP_OK || c->batch == 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, K = (size_t)c->k_sessions, Mg = (size_t)h->shape.Mg;
   const size_t H = (size_t)pl->n_horizons, A = (size_t)pl->n_arrivals, R = (size_t)pl->n_rates, nv = N * Tm * 8, ns = K * N;
   const bool pk = h->shape.has_peak, fl = h->shape.has_flat, mx = h->shape.has_max, wy = nx->warm_y != nullptr && Mg > 0;
   const size_t P = pk && pl->peak_series ? (size_t)pl->peak_len : 0, nwx = nx->warm_x ? nv : 0, nwy = wy ? Mg * Tm * 8 : 0;
-  enum { QT, HS, HR, SEG, AEV, ASL, ALN, ACP, ARS, AMN, AMX, LB, UB, SOFF, SLEN, SCAP, DFL, APP, STAT, X, Y, PKS,
+  const size_t CP = cost ? (size_t)cost->series_len : 0;   // (without a cost its two rows take no room: the plan is the plain entry's)
+  enum { QT, HS, HR, SEG, AEV, ASL, ALN, ACP, ARS, AMN, AMX, CW, LB, UB, SOFF, SLEN, SCAP, DFL, APP, STAT, X, Y, PKS, CS,
          OHOR, OLB, OUB, OQ, OPD, OOFF, OLEN, OCAP, OPK, OLF, ODC, ODFL, OWX, OWY, OFLG, NARR };
   const S arr[NARR] = {
       S::plan(pl->q_table, H * nv), S::plan(pl->h_scal, H * 24), S::plan(pl->h_row, (Tm + 1) * 4), S::plan(pl->a_seg, A ? (B + 1) * 4 : 0),
       S::plan(pl->a_evse, A * 4), S::plan(pl->a_slot, A * 4), S::plan(pl->a_len, A * 4), S::plan(pl->a_cap, A * 8),
       S::plan(pl->a_rate_seg, A ? (A + 1) * 4 : 0), S::plan(pl->a_min, R * 8), S::plan(pl->a_max, R * 8),
+      S::plan(cost ? cost->weight : nullptr, cost ? N * 8 : 0),
       S::in(c->lb, nv), S::in(c->ub, nv), S::in(c->s_off, ns * 4), S::in(c->s_len, ns * 4), S::in(c->s_cap, ns * 8), S::in(c->dfloor, mx ? 8 : 0),
       S::in(applied, N * 8), S::in(status, status ? 4 : 0), S::in(x, nwx), S::in(y, nwy), S::in(pl->peak_series, P * 8),
+      S::in(cost ? cost->series : nullptr, CP * 8),
       S::out(nx->horizon, 4), S::out(nx->lb, nv), S::out(nx->ub, nv), S::out(nx->q, nv), S::out(nx->pdiag, 8), S::out(nx->s_off, ns * 4),
       S::out(nx->s_len, ns * 4), S::out(nx->s_cap, ns * 8), S::out(nx->peak, pk ? Tm * 8 : 0), S::out(nx->lf, fl ? 8 : 0), S::out(nx->dc, mx ? 8 : 0),
       S::out(nx->dfloor, mx ? 8 : 0), S::out(nx->warm_x, nwx), S::out(nx->warm_y, nwy), S::out(flags, 4)};
@@ -361,8 +384,15 @@ int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* c, const double* a
     pc.a_min = dev(AMN); pc.a_max = dev(AMX);
     acnqp_next nc{dev(OHOR), dev(OLB), dev(OUB), dev(OQ), dev(OPD), dev(OOFF), dev(OLEN), dev(OCAP), dev(OPK), dev(OLF), dev(ODC), dev(ODFL),
                   dev(OWX), dev(OWY)};
-    return acnqp_advance_device(h, &cc, dev(APP), dev(STAT), dev(X), dev(Y), &pc, &nc, dev(OFLG), h->slot[0].st);
+    acnqp_clock_cost kc{};
+    if (cost) { kc = *cost; kc.weight = dev(CW); kc.series = dev(CS); }
+    return acnqp_advance_priced_device(h, &cc, dev(APP), dev(STAT), dev(X), dev(Y), &pc, cost ? &kc : nullptr, &nc, dev(OFLG), h->slot[0].st);
   });
+}
+
+int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
+                       const double* y, const acnqp_advance_plan* pl, acnqp_next* nx, int32_t* flags) {
+  return acnqp_advance_priced_host(h, c, applied, status, x, y, pl, nullptr, nx, flags);
 }
 
 // ---- before the solve (acn_qp_prepare.hpp) ------------------------------------------------------------------------------

@@ -36,6 +36,7 @@ class RolloutResult:
     x: Optional[np.ndarray] = None   # (steps, B, N, Tm) the solved schedules, when asked for
     visits: Optional[np.ndarray] = None          # (steps, B) int32 visits of the reallocation's round robin (reallocate=True)
     prepare_flags: Optional[np.ndarray] = None   # (steps, B) int32 flags of acnqp_prepare_device (a session_order was stated)
+    energy_cost: Optional[np.ndarray] = None     # (B,) sum over s, i of pilots[s, b, i] * weight[i] * series[b][s]; None without a clock cost
 
 
 class FleetTable:
@@ -46,8 +47,18 @@ class FleetTable:
     (one linear cost per horizon serves the whole run).  That is checked by evaluating the cost one period later on an
     interface that keeps its clock in ``interface.data["current_time"]`` (this package's ``Interface``; the entry is put
     back); behind any other interface only this package's clock-free components (quick_charge, equal_share, total_energy,
-    load_flattening, peak, demand_charge) are accepted.  Either way a cost that reads the clock (``tou_energy_cost``) is
-    refused.  An ``external_signal`` of ``load_flattening`` is the caller's fixed array: it is read from its first entry
+    load_flattening, peak, demand_charge) are accepted.  Either way any other cost that reads the clock is refused.
+    The one clock-dependent cost the loop carries is ``tou_energy_cost``: the components whose function ``is
+    tou_energy_cost`` are taken out of the list before the table is built and become the plan's CLOCK COST (rule 6b of
+    include/acn_qp.h) -- ``coef`` the component's coefficient, ``weight[i] = voltages[i] / 1e3 * (period / 60)`` as
+    ``tou_energy_cost`` computes it, ``series = interface.get_prices(steps + Tm, start_time)`` for every scenario, or the
+    caller's ``prices``: a ``(P,)`` or ``(B, P)`` array whose entry 0 is the price of period ``start_time``, so that one batch
+    sweeps tariffs over its scenarios.  At most one such component with a non-zero coefficient is accepted.  The advance
+    then builds ``q' = q_table[row] + coef * (weight * price)``, three roundings.  The builder folds ``coefficient *
+    term.lin`` in list order and negates the sum, and negation is exact, so with ``tou_energy_cost`` as the LAST component
+    of the list the device's q' is the builder's q bit for bit; anywhere else in the list the builder's sum is folded in
+    another order and the two may differ in the last places.  The caller's list is never reordered.
+    An ``external_signal`` of ``load_flattening`` is the caller's fixed array: it is read from its first entry
     at every step, as ``schedule`` reads it.
     ``session_order`` states the order of the session lists a plant would hand to ``schedule`` -- what the reference's
     minimum-rate walk and reallocation read, and the slot state does not carry: ``"fleet"`` (a session stands where its record
@@ -58,7 +69,8 @@ class FleetTable:
     ORDERS = ("fleet", "arrival")
 
     def __init__(self, fleets: Sequence[Sequence[dict]], infrastructure, interface, objective, steps: int, start_time: int = 0,
-                 peak_limit=None, done_kwh: float = 1e-9, t_max: Optional[int] = None, session_order: Optional[str] = None):
+                 peak_limit=None, done_kwh: float = 1e-9, t_max: Optional[int] = None, session_order: Optional[str] = None,
+                 prices=None):
         if session_order is not None and session_order not in self.ORDERS:
             raise ValueError(f'session_order must be "fleet", "arrival" or None, not {session_order!r}')
         self.session_order = session_order
@@ -129,14 +141,31 @@ class FleetTable:
         # ---- the objective, once per horizon (aco.py:200-218 depends on a problem only through T, aco.py:243-245) ----------
         self.prev_peak = interface.get_prev_peak()
         Tm, N = self.Tm, self.N
+        rest, clock = self._split_clock_cost(objective)
         q_table, h_scal = np.zeros((Tm, N, Tm)), np.zeros((Tm, 3))
         dfloor = 0.0
         for T in range(1, Tm + 1):
-            q, pd, lf, _, dc, dfl = objective_terms(objective, infrastructure, interface, N, T, self.prev_peak)
+            q, pd, lf, _, dc, dfl = objective_terms(rest, infrastructure, interface, N, T, self.prev_peak)
             q_table[T - 1, :, :T] = q
             h_scal[T - 1] = pd, lf, dc
             dfloor = dfl
-        self._refuse_clock_dependence(objective, infrastructure, interface, q_table[Tm - 1])
+        self._refuse_clock_dependence(rest, infrastructure, interface, q_table[Tm - 1])
+        # ---- the clock cost (rule 6b): the tariff over the run, one row per scenario ---------------------------------------
+        self.c_coef = self.c_weight = self.c_series = None
+        if clock is None and prices is not None:
+            raise ValueError("prices= is given but the objective has no tou_energy_cost component with a non-zero coefficient")
+        if clock is not None:
+            need = self.steps + Tm
+            one = np.asarray(interface.get_prices(need, self.start) if prices is None else prices, float)
+            if one.ndim not in (1, 2) or (one.ndim == 2 and one.shape[0] != self.B):
+                raise ValueError(f"prices must have shape (P,) or ({self.B}, P)")
+            if one.shape[-1] < need:
+                raise ValueError(f"the price series holds {one.shape[-1]} periods from start_time; the rollout needs steps + t_max = {need}")
+            if not np.all(np.isfinite(one[..., :need])):
+                raise ValueError("the price series must be finite")
+            self.c_coef = float(clock.coefficient)
+            self.c_weight = np.asarray(infrastructure.voltages, float) / 1e3 * (interface.period / 60)   # as tou_energy_cost computes it
+            self.c_series = np.array(np.broadcast_to(one[..., :need], (self.B, need)), dtype=np.float64, order="C")   # (a copy: writable)
         self.dfloor0 = float(dfloor)
         self.need_flat, self.need_max = _objective_needs_flat(objective), _objective_needs_max(objective)
         h_row = np.r_[-1, np.arange(Tm)].astype(np.int32)
@@ -155,7 +184,29 @@ class FleetTable:
         self.plan = backend.AdvancePlan(
             q_table=q_table, h_scal=h_scal, h_row=h_row, done_tol=self.done_tol, kw_per_amp=self.kw_per_amp, peak_series=series,
             a_seg=a_seg, a_evse=np.array([r[2] for r in recs], np.int32), a_slot=np.zeros(A, np.int32), a_len=lens,
-            a_cap=np.array([r[4] for r in recs], np.float64), a_rate_seg=rate_seg, a_min=cat(5), a_max=cat(6))
+            a_cap=np.array([r[4] for r in recs], np.float64), a_rate_seg=rate_seg, a_min=cat(5), a_max=cat(6),
+            c_coef=self.c_coef, c_weight=self.c_weight, c_series=self.c_series)
+
+    @staticmethod
+    def _split_clock_cost(objective):
+        """(the components that build q_table / h_scal, the one tou_energy_cost component or None)"""
+        from .adaptive_charging_optimization import tou_energy_cost
+
+        rest = [c for c in objective if c.function is not tou_energy_cost]
+        clock = [c for c in objective if c.function is tou_energy_cost and c.coefficient != 0]
+        if len(clock) > 1:
+            raise ValueError(f"the objective holds {len(clock)} tou_energy_cost components with a non-zero coefficient: the rollout "
+                             "carries one clock cost (one coefficient, one price series); add their coefficients up")
+        if clock and not np.isfinite(clock[0].coefficient):
+            raise ValueError("the coefficient of tou_energy_cost must be finite")
+        return rest, (clock[0] if clock else None)
+
+    def energy_cost(self, pilots: np.ndarray) -> Optional[np.ndarray]:
+        """(B,) what the applied ``pilots`` (steps, B, N) cost under the clock cost's series: sum over s, i of
+        pilots[s, b, i] * weight[i] * series[b][s] (kWh times price); None without a clock cost."""
+        if self.c_series is None:
+            return None
+        return np.einsum("sbi,i,bs->b", pilots, self.c_weight, self.c_series[:, : pilots.shape[0]])
 
     def keys_for(self, session_order: str) -> np.ndarray:
         """(steps, B, N) int32: at step s, the list position under ``session_order`` of the record staying on EVSE i of
@@ -209,7 +260,7 @@ class FleetTable:
 
 
 def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = False, return_schedules: bool = False,
-             observer=None, session_order: Optional[str] = None) -> RolloutResult:
+             observer=None, session_order: Optional[str] = None, prices=None) -> RolloutResult:
     """``AdaptiveSchedulingAlgorithm.simulate_batch``: see there."""
     import torch
 
@@ -229,8 +280,10 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
         _bad_constraint_type(alg.constraint_type)
     interface = alg.interface
     infra = interface.infrastructure_info()
+    if isinstance(fleets, FleetTable) and prices is not None:
+        raise ValueError("prices= goes to the FleetTable: the table given was built with its own")
     table = fleets if isinstance(fleets, FleetTable) else FleetTable(fleets, infra, interface, alg.objective, steps, start_time, alg.peak_limit,
-                                                                            session_order=session_order)
+                                                                            session_order=session_order, prices=prices)
     if (table.steps, table.start) != (int(steps), int(start_time)):
         raise ValueError("the FleetTable was built for another run (steps, start_time)")
     if table.session_order != session_order:
@@ -320,4 +373,5 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             raise ValueError(f"step {s_bad}, scenario {b_bad}: allowable pilots end below a session's cap; the reallocation of the "
                              "rounding loss would never end")
         return RolloutResult(p, st, iters.cpu().numpy(), flags.cpu().numpy(), table.delivered(p),
-                             None if xs is None else xs.cpu().numpy(), vis, None if pflags is None else pflags.cpu().numpy())
+                             None if xs is None else xs.cpu().numpy(), vis, None if pflags is None else pflags.cpu().numpy(),
+                             table.energy_cost(p))

@@ -481,13 +481,19 @@ int acnqp_pilots_host(acnqp_handle* h, const acnqp_pilot_plan* plan, const doubl
  *    5  horizon' = max(1, max over the live slots of off' + len').
  *    6  q'[b] = q_table[h_row[horizon']] and pdiag', lf', dc' = h_scal[h_row[horizon']]; a row outside [0, n_horizons)
  *       sets flag bit 2 and writes q' and the three scalars as zeros.
+ *   6b  with a clock cost (acnqp_advance_priced_device / _host), where the horizon has a row:
+ *       q'[i][t] = q_table[row][i][t] + coef * (weight[i] * series[b][step + 1 + t]) for t < horizon' -- a product, a
+ *       product and a sum, each rounded once, in this order; for t >= horizon' q' stays the table's entry (its zero
+ *       padding), and without a row (flag bit 2) q' stays all zeros.  This is the builder's q of an objective whose LAST
+ *       component is coef * tou_energy_cost, bit for bit: -(S + coef * ((-w) * price)) = -S + coef * (w * price).
  *    7  peak'[t] = peak_series[b][step + 1 + t] for t < horizon' and +inf beyond (the builder's padding); all +inf when
  *       peak_series is NULL.
  *    8  dfloor' = max(dfloor, kw_per_amp * sum_i a_i): the sum in increasing i, every operation rounded once.
  *    9  when wanted, warm_x'[i][t] = x[i][t + 1] and warm_y'[j][t] = y[j][t + 1] for t + 1 < t_max, 0 at the last period.
  *       With warm_arrival_gain g != 0, warm_x' of a session admitted in rule 4 is (-g) * q'[i][t] on its window [0, a_len)
- *       instead (one product): the point a cold solve starts that session from, before its projection on the bounds and
- *       the energy row (the solver kernels use g = 1e5).  0 leaves the shifted x, which is 0 for an EVSE that was idle.
+ *       instead (one product; q' is the final one, after rule 6b): the point a cold solve starts that session from,
+ *       before its projection on the bounds and the energy row (the solver kernels use g = 1e5).  0 leaves the shifted
+ *       x, which is 0 for an EVSE that was idle.
  *   10  flags[b] is written for every problem, 0 when nothing was refused.
  * s_eq does not change with time and is not written.  Copies, comparisons, one subtraction per served slot and one
  * ordered sum per problem: tests/advance_spec.py states the rules in plain loops and the library returns its bits.  No
@@ -556,6 +562,29 @@ int acnqp_advance_device(acnqp_handle* h, const acnqp_problems* cur, const doubl
 int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* cur, const double* applied, const int32_t* status,
                        const double* x, const double* y, const acnqp_advance_plan* plan, acnqp_next* next,
                        int32_t* flags);
+
+/* The clock cost of rule 6b (additive to ABI v10: new symbols only): a linear cost that follows the clock, such as a
+ * time-of-use tariff -- coef * weight[i] * series[b][absolute period] per ampere of EVSE i.                           */
+typedef struct {
+  int32_t n_evse;        /* N: must be the handle's                                                                   */
+  int32_t series_len;    /* P >= step + 1 + t_max                                                                     */
+  double coef;           /* finite                                                                                    */
+  const double* weight;  /* [N]                                                                                       */
+  const double* series;  /* [B*P] series[b][p]: period p counted from the run's first period (step + 1 = 0)          */
+} acnqp_clock_cost;
+
+/* acnqp_advance_priced_device / _host -- acnqp_advance_device / _host with rule 6b.  cost == NULL is exactly the plain
+ * entry (which is this call with NULL).  With a cost, additionally refused with ACNQP_ERR_INVALID and acnqp_last_error
+ * set, before any device work: n_evse other than the handle's, a null weight or series, a coef that is not finite,
+ * series_len < step + 1 + t_max, a weight or series span that meets an output of `next` or `flags`.  The host entry
+ * stages `series` per problem (as peak_series) and `weight` once per call; same bits as the device entry, at any
+ * chunking.                                                                                                          */
+int acnqp_advance_priced_device(acnqp_handle* h, const acnqp_problems* cur, const double* applied, const int32_t* status,
+                                const double* x, const double* y, const acnqp_advance_plan* plan,
+                                const acnqp_clock_cost* cost, acnqp_next* next, int32_t* flags, void* hip_stream);
+int acnqp_advance_priced_host(acnqp_handle* h, const acnqp_problems* cur, const double* applied, const int32_t* status,
+                              const double* x, const double* y, const acnqp_advance_plan* plan,
+                              const acnqp_clock_cost* cost, acnqp_next* next, int32_t* flags);
 
 /* ---- before the solve (additive to ABI v10: new symbols only) --------------------------------------------------------
  * The link between the slot state an advance writes and the two steps of the reference that read the SESSION LIST:
