@@ -1058,6 +1058,16 @@ class SiteHandle:
         out["phase_us"] = [int(v) // 100 for v in buf[8:16]]   # summed over the polish workgroups
         return out
 
+    def polish_alongside(self) -> int:
+        """Problems that polish launches running ALONGSIDE a solver launch have taken since the previous call
+        (acnqp_debug_polish_alongside: introspection, not part of the ABI; synchronises)."""
+        fn = self._lib.acnqp_debug_polish_alongside
+        fn.restype, fn.argtypes = C.c_int64, [C.c_void_p]
+        n = int(fn(self._h))
+        if n < 0:
+            raise RuntimeError("acnqp_debug_polish_alongside failed")
+        return n
+
     def wave_rank(self) -> dict:
         """The site's live eigenpairs, the MFMA k-steps that hold them once compacted, and the eigen extent (k-steps) of
         the wave kernel's instantiation this handle runs (acnqp_debug_wave_rank: introspection, not part of the ABI)."""

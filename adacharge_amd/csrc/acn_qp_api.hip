@@ -100,7 +100,16 @@ struct acnqp_handle {
   // per launch stream: the kernel workspace (long-horizon, large-site, general-shape kernels) and the launch's small
   // scheduling buffer (queue counter, then sort keys and queue order).  Launches on different streams never share (or
   // regrow) each other's state, and a stream's own launches are ordered by the stream.
-  struct Work { hipStream_t st; DevBuf buf; DevBuf ord; DevBuf pol; long long used; hipEvent_t last; DevBuf dua; };   // pol: the polish's list and multiplier buffer; dua: g of a dual report without z
+  struct Work {
+    hipStream_t st; DevBuf buf; DevBuf ord; DevBuf pol; long long used; hipEvent_t last; DevBuf dua;   // pol: the polish's list and multiplier buffer; dua: g of a dual report without z
+    hipEvent_t fork = nullptr, join = nullptr;   // the polish alongside a solver launch: where it may start, where it has ended (created on first use)
+    void release_events() {
+      if (last) (void)hipEventDestroy(last);
+      if (fork) (void)hipEventDestroy(fork);
+      if (join) (void)hipEventDestroy(join);
+      last = fork = join = nullptr;
+    }
+  };
   std::vector<Work> work;
   long long work_clock = 0;
   // streams of the CALLER (acnqp_solve_batch_device) beyond the handle's own kSlots: a caller that round-robins one
@@ -132,7 +141,8 @@ struct acnqp_handle {
         if (lru == work.size() || work[k].used < work[lru].used) lru = k;
       }
       if (callers >= max_caller_workspaces()) {
-        if (work[lru].last) { (void)hipEventSynchronize(work[lru].last); (void)hipEventDestroy(work[lru].last); }
+        if (work[lru].last) (void)hipEventSynchronize(work[lru].last);   // (behind the launch's join with the auxiliary stream)
+        work[lru].release_events();
         work[lru].buf.release();
         work[lru].ord.release();
         work[lru].pol.release();
@@ -142,12 +152,12 @@ struct acnqp_handle {
     }
     hipEvent_t ev = nullptr;
     (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    work.push_back(Work{st, DevBuf(), DevBuf(), DevBuf(), ++work_clock, ev});
+    work.push_back(Work{st, DevBuf(), DevBuf(), DevBuf(), ++work_clock, ev, DevBuf()});
     return &work.back();
   }
   void release_work() {
     for (auto& w : work) {
-      if (w.last) (void)hipEventDestroy(w.last);
+      w.release_events();
       w.buf.release();
       w.ord.release();
       w.pol.release();
@@ -156,7 +166,9 @@ struct acnqp_handle {
     work.clear();
   }
   int cus = 0;   // compute units of the device (the work-queue launches size their grid from it)
-  int32_t* pol_stats = nullptr;   // device counters of the polish kernel, summed over the handle's life (acnqp_polish_stats)
+  int32_t* pol_stats = nullptr;   // device counters of the polish kernel, summed over the handle's life (acnqp_polish_stats);
+                                  // [16]: problems taken by the launches alongside the solver (acnqp_debug_polish_alongside)
+  hipStream_t aux = nullptr;      // the polish launches that run alongside a solver launch (launch_with_polish)
   // the post-solve host entries' device staging (acn_qp_post.hpp: the whole-call arrays and one chunk).  ONE buffer for
   // the three: each runs on slot[0].st, synchronises it before reserve() and returns synchronised
   DevBuf post_stage;
@@ -212,6 +224,9 @@ int polish_block_doubles(const acnqp_handle* h, const acnqp::Route& rt) {
   //  launches it adds its rounds to the launch's end, DESIGN.md 2.3 has the price)
   return blk < 2 * nrow_site * (2 * nrow_site + 1) / 2 ? -1 : blk;   // not even one full block
 }
+
+// acnqp_solve_batch_device with the pipeline's knowledge of what comes after the launch (nothing_follows: launch_with_polish)
+int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows);
 
 }  // namespace
 
@@ -306,9 +321,10 @@ int acnqp_create(const acnqp_site* site, int32_t device_id, acnqp_handle** out) 
   std::string err;
   const int rc = acnqp::build_site_dev(&h->shape, h->G, h->limits, &h->site, &err);
   if (rc != ACNQP_OK) { acnqp_destroy(h); return fail(rc, err); }
-  if (hipMalloc((void**)&h->pol_stats, 16 * sizeof(int32_t)) != hipSuccess || hipMemset(h->pol_stats, 0, 16 * sizeof(int32_t)) != hipSuccess) {
+  if (hipMalloc((void**)&h->pol_stats, 32 * sizeof(int32_t)) != hipSuccess || hipMemset(h->pol_stats, 0, 32 * sizeof(int32_t)) != hipSuccess ||
+      hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking) != hipSuccess) {
     acnqp_destroy(h);
-    return fail(ACNQP_ERR_HIP, "acnqp_create: polish counters");
+    return fail(ACNQP_ERR_HIP, "acnqp_create: polish counters and stream");
   }
   *out = h;
   return ACNQP_OK;
@@ -328,6 +344,7 @@ void acnqp_destroy(acnqp_handle* h) {
     sl.out.release();
     sl.tin.release();
   }
+  if (h->aux) { (void)hipStreamSynchronize(h->aux); (void)hipStreamDestroy(h->aux); }
   h->small_in.release();
   h->small_out.release();
   for (auto& ev : h->h2d_done) if (ev) (void)hipEventDestroy(ev);
@@ -413,7 +430,7 @@ acnqp::TiledArgs tiled_args(const acnqp_handle* h, const acnqp_problems* p, cons
   bool own = false;
   for (auto& sl : h->slot) own = own || sl.st == st;
   a.grid_oversub = own ? 4 : 1;
-  a.polish_iters = 0; a.polish_stall = 0; a.resume = 0; a.y_for_polish_only = 0; a.pol_rows = 0; a.pol_list = nullptr; a.pol_count = nullptr; a.count_dev = nullptr;
+  a.polish_iters = 0; a.polish_stall = 0; a.resume = 0; a.y_for_polish_only = 0; a.pol_rows = 0; a.pol_list = nullptr; a.pol_count = nullptr; a.pol_retired = nullptr; a.count_dev = nullptr;
   return a;
 }
 
@@ -513,8 +530,35 @@ hipError_t launch_solver(const acnqp_handle* h, const acnqp::Route& rt, const ac
 // the list -> solver kernel again over the list for what the polish gave up on (from scratch, with the retry passes:
 // the answer it had before there was a polish).  Three launches on the stream, the last two nearly empty as a rule.
 // pol_blk: polish_block_doubles of the shape.
+//
+// The problems that are handed over are the launch's longest-running ones, and the chip thins out for milliseconds before
+// its last straggler ends: where NOTHING FOLLOWS the launch (a caller's stream; the last chunk of a pipelined call) a
+// second polish launch runs ALONGSIDE the solver, on the handle's auxiliary stream, and takes the hand-overs as they are
+// published (acn_qp_polclaim.hpp) on the CUs the solver's retired workgroups leave.  The serial launches stay as they
+// are: they find the list drained, or finish what the launch alongside left.  Wave kernel with a work queue only (its
+// hand-over publishes inside the launch and it counts its finished problems: TiledArgs::pol_retired).  Intermediate chunks
+// of a pipelined call do without: their serial polish already runs under the next chunk's solver, and spinning workgroups
+// would hold CUs that chunk wants.  ACNQP_NO_POLISH_ALONGSIDE=1 (diagnostic, once per process): never.
 int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route& rt, const acnqp::TiledArgs& a, const Workspace& ws,
-                       int pol_blk, const acnqp_problems* p, const acnqp_options* o, const acnqp_results* r, hipStream_t st, hipError_t* e) {
+                       int pol_blk, const acnqp_problems* p, const acnqp_options* o, const acnqp_results* r, hipStream_t st, bool nothing_follows,
+                       hipError_t* e) {
+  static const bool no_alongside = std::getenv("ACNQP_NO_POLISH_ALONGSIDE") != nullptr;
+  // looks at the list a workgroup alongside makes per claim (an empty one costs about a microsecond: the default outlasts
+  // every launch the project times by seconds); 0: every one of them leaves at once, without a look
+  static const long long along_polls = [] {
+    const char* v = std::getenv("ACNQP_POLISH_ALONGSIDE_SPINS");
+    const long long n = v ? std::atoll(v) : (1ll << 21);
+    return n < 0 ? 0ll : n;
+  }();
+  static const int along_grid = [] {   // diagnostic: workgroups of the launch alongside
+    const char* v = std::getenv("ACNQP_POLISH_ALONGSIDE_GRID");
+    const int n = v ? std::atoi(v) : 0;
+    return n > 0 && n <= 256 ? n : 16;
+  }();
+  // (not the two-row-tile route of horizons <= 12, ACNQP_ROUTE_WAVE3: measured a LOSS there -- configs[3] site 3, 1,024
+  //  problems: 7.20-7.36 ms without, 8.02-8.18 ms with; two rounds of problems on 512 slots hand half their stragglers over in
+  //  mid-launch, and 16 workgroups then work through a list that the serial launch spreads over the chip)
+  const bool alongside = nothing_follows && !no_alongside && rt.wv > 0 && rt.wv != 3 && a.queue != nullptr;
   const acnqp::SiteShape& s = h->shape;
   const acnqp::SiteDev* d = &h->site;
   const int nrow_site = s.M + s.has_peak;
@@ -530,7 +574,13 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   int32_t* ctr = static_cast<int32_t*>(wk->pol.p);
   int32_t* list = ctr + 64;
   double* ybuf = r->y ? r->y : reinterpret_cast<double*>(static_cast<char*>(wk->pol.p) + 256 + lbytes);
-  HIP_TRY(hipMemsetAsync(ctr, 0, 256, st));
+  HIP_TRY(hipMemsetAsync(ctr, 0, 256, st));   // ([3]: the solver launch's finished problems, for the polish alongside it)
+  if (alongside) {
+    HIP_TRY(hipMemsetAsync(list, 0xff, lbytes, st));   // -1: not published
+    if (!wk->fork) HIP_TRY(hipEventCreateWithFlags(&wk->fork, hipEventDisableTiming));
+    if (!wk->join) HIP_TRY(hipEventCreateWithFlags(&wk->join, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(wk->fork, st));   // counters and list are set: from here on the launch alongside may run
+  }
   acnqp::TiledArgs a1 = a;
   a1.polish_iters = o->polish_iters - o->polish_iters % std::max(1, o->check_every);   // the exit is taken at a residual check
   if (a1.polish_iters < o->check_every) a1.polish_iters = o->check_every;
@@ -541,6 +591,7 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   static const int early = std::getenv("ACNQP_EARLY_HANDOVER") ? std::atoi(std::getenv("ACNQP_EARLY_HANDOVER")) : 0;   // diagnostic: the window (1: polish_iters / 4)
   a1.polish_stall = early > 1 ? early : (early == 1 ? std::max(o->check_every, a1.polish_iters / 4) : o->polish_stall);
   a1.y_for_polish_only = r->y ? 0 : 1;
+  a1.pol_retired = alongside ? ctr + 3 : nullptr;
   *e = launch_solver(h, rt, a1, ws, st);
   if (*e == hipSuccess) {
     acnqp::PolishArgs pa;
@@ -551,9 +602,26 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
     pa.s_off = p->s_off; pa.s_len = p->s_len; pa.s_cap = p->s_cap; pa.s_eq = p->s_eq; pa.peak = s.has_peak ? p->peak : nullptr;
     pa.x = r->x; pa.y = ybuf; pa.status = r->status; pa.iters = r->iters; pa.pri = r->pri_res; pa.dua = r->dua_res; pa.obj = r->obj;
     pa.list = list; pa.count = ctr + 2; pa.queue = ctr + 0; pa.stats = h->pol_stats; pa.reg_rel = o->reg_rel;
+    // (expected: the problems the FIRST launch serves -- its queue_length is the batch, count_dev being null there; only the
+    //  resume launch runs over a shorter list.  A first launch over fewer problems would leave the launch alongside polling
+    //  until its bound)
+    pa.alongside = 0; pa.expected = p->batch; pa.retired = ctr + 3; pa.max_polls = along_polls; pa.taken = h->pol_stats + 16;
+    if (alongside) {
+      // no host synchronisation; nothing the launch alongside waits for is queued behind it: the solver counts its own
+      // finished problems, and every poll is bounded
+      acnqp::PolishArgs pc = pa;
+      pc.alongside = 1;
+      // (error paths: a failed launch alongside is reported through *e like any launch, after the join below -- the two
+      //  streams are joined whether it ran or not; a HIP_TRY that returns here fails the call with the solver launch
+      //  already on `st` and at most the fork wait on `aux`: nothing on either stream waits for something that never comes)
+      HIP_TRY(hipStreamWaitEvent(h->aux, wk->fork, 0));
+      *e = acnqp::launch_polish(pc, along_grid, h->aux);
+      HIP_TRY(hipEventRecord(wk->join, h->aux));
+      HIP_TRY(hipStreamWaitEvent(st, wk->join, 0));
+    }
     // (pipelined chunks hand a handful of problems over: few workgroups, so that the launch does not queue for 256 slots
     //  behind the neighbouring streams' solver launches)
-    *e = acnqp::launch_polish(pa, pol_grid, st);
+    if (*e == hipSuccess) *e = acnqp::launch_polish(pa, pol_grid, st);
   }
   if (*e == hipSuccess) {
     acnqp::TiledArgs a3 = a;
@@ -569,15 +637,11 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   return ACNQP_OK;
 }
 
-}  // namespace
-
-int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r,
-                             void* hip_stream) {
+int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows) {
   int rc = check_problem_shapes(h, p, o, r);
   if (rc != ACNQP_OK) return rc;
   if (p->batch == 0) return ACNQP_OK;
   HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   acnqp::TiledArgs a = tiled_args(h, p, o, r, st);
   (void)hipGetLastError();   // drop any stale error so the checks below report this launch only
   // a problem whose workgroup never ran must not look solved (or carry the previous call's status)
@@ -595,7 +659,7 @@ int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acn
   const int pol_blk = (o->polish_iters > 0 && o->polish_iters < o->max_iter && !a.warm_x) ? polish_block_doubles(h, rt) : -1;
   hipError_t e = hipSuccess;
   if (pol_blk >= 0) {
-    if ((rc = launch_with_polish(h, wk, rt, a, ws, pol_blk, p, o, r, st, &e)) != ACNQP_OK) return rc;
+    if ((rc = launch_with_polish(h, wk, rt, a, ws, pol_blk, p, o, r, st, nothing_follows, &e)) != ACNQP_OK) return rc;
   } else {
     e = launch_solver(h, rt, a, ws, st);
   }
@@ -604,6 +668,14 @@ int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acn
   if (wk->last) HIP_TRY(hipEventRecord(wk->last, st));   // what an eviction of this stream's buffers waits for
   ++h->launches;
   return ACNQP_OK;
+}
+
+}  // namespace
+
+// (a launch on a caller's stream: nothing of this handle's follows it)
+int acnqp_solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r,
+                             void* hip_stream) {
+  return solve_batch_device(h, p, o, r, reinterpret_cast<hipStream_t>(hip_stream), true);
 }
 
 int32_t acnqp_accel_columns(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t precision, int32_t requested) {
@@ -632,6 +704,16 @@ int acnqp_polish_stats(acnqp_handle* h, int64_t* out, int32_t capacity) {
   HIP_TRY(hipMemcpy(v, h->pol_stats, sizeof(v), hipMemcpyDeviceToHost));
   for (int k = 0; k < capacity && k < 16; ++k) out[k] = v[k];
   return ACNQP_OK;
+}
+
+// Introspection outside include/acn_qp.h (every build): the problems that polish launches ALONGSIDE a solver launch
+// (launch_with_polish) have taken since the last call; -1 without a handle or on a HIP error.  Synchronises the device.
+extern "C" int64_t acnqp_debug_polish_alongside(acnqp_handle* h) {
+  if (!h || hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+  int32_t v = 0;
+  if (hipMemcpy(&v, h->pol_stats + 16, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemset(h->pol_stats + 16, 0, sizeof v) != hipSuccess) return -1;
+  return v;
 }
 
 // Introspection outside include/acn_qp.h (every build): out[0] = live eigenpairs of the site's G G', out[1] = the MFMA

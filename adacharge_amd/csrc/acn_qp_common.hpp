@@ -78,6 +78,8 @@ struct TiledArgs {
   int pol_rows;               // rows of the polish kernel's Schur system for this shape: a problem whose iterate has more tight site
                               // rows than that is not handed over (it would come straight back) and the ADMM goes on
   int32_t *pol_list, *pol_count;
+  int32_t* pol_retired;       // null, or (wave kernel, work-queue launches): the problems of this launch that are finished and, where
+                              // handed over, published -- what a polish launch running ALONGSIDE this one waits for
   const int32_t* count_dev;   // number of queue positions, on the device (null: B)
   int ws_by_slot;  // 1: a streaming kernel's workspace belongs to the workgroup slot (work-queue launches), 0: to the problem
   int grid_oversub; // host side only: workgroups of a work-queue launch per resident slot (1: fully persistent; the pipelined

@@ -454,7 +454,7 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
     acnqp_problems dp;
     acnqp_results dr;
     device_views(L, di, dq, s, cn, b, &dp, &dr);
-    rc = acnqp_solve_batch_device(h, &dp, o, &dr, S.st);
+    rc = solve_batch_device(h, &dp, o, &dr, S.st, c + 1 == chunks.size());   // (the last chunk: nothing follows its launch)
     if (rc != ACNQP_OK) return rc;
     if (staged) HIP_TRY(hipMemcpyAsync(ho + L.st, dq + L.st, L.y - L.st, hipMemcpyDeviceToHost, S.st));
     for (const Piece& pc : pcs) {

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "acn_qp_common.hpp"
+#include "acn_qp_polclaim.hpp"
 
 namespace acnqp {
 
@@ -55,6 +56,13 @@ struct PolishArgs {
   int32_t* queue;                  // launch counter of the work queue
   int32_t* stats;                  // [0] attempted, [1] succeeded, [2] gave up: rows, [3] pivot, [4] rounds, [5] verification
   double reg_rel;
+  // -- a launch ALONGSIDE the solver launch that fills `list` (acn_qp_polclaim.hpp): entries are claimed as
+  //    they are published, until the solver's `retired` count reaches `expected` problems or max_polls polls have passed
+  int alongside;                   // 0: the serial launch behind the solver (the list is complete: `count` entries)
+  int expected;
+  const int32_t* retired;
+  long long max_polls;
+  int32_t* taken;                  // problems the launches alongside took (acnqp_debug_polish_alongside)
 };
 
 constexpr int kPolMaxSess = 128;      // tight sessions with free variables (columns of V) at most (PolishArgs.max_sess <= this)
@@ -209,12 +217,25 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
   auto row_is_disc = [&](int r) { return soc && r < M; };
 
   for (int q_round = 0;; ++q_round) {
-    const int nlist = *A.count;
-    const int pos = queue_next(A.queue, nlist < A.B ? nlist : A.B, q_round, &q_slot);
-    if (pos < 0) break;
-    const int b = A.list[pos];
+    int pos, b;
+    if (A.alongside) {   // (block-uniform) thread 0 claims a PUBLISHED entry, or learns that there is nothing more to wait for
+      if (tid == 0) q_slot = pol_claim(A.list, A.queue, A.retired, A.expected, A.B, A.max_polls, [] { __builtin_amdgcn_s_sleep(32); });
+      __syncthreads();
+      pos = __builtin_amdgcn_readfirstlane(q_slot);
+      __syncthreads();
+      if (pos < 0) break;
+      // every thread acquires the entry itself: the solver's x / y / status / iters stores behind it are visible to all of them
+      b = __builtin_amdgcn_readfirstlane(__hip_atomic_load(A.list + pos, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT));
+      if (b < 0 || b >= A.B) continue;   // (never expected: a claimed entry is a published problem)
+    } else {
+      const int nlist = *A.count;
+      pos = queue_next(A.queue, nlist < A.B ? nlist : A.B, q_round, &q_slot);
+      if (pos < 0) break;
+      b = A.list[pos];
+    }
     if (A.status[b] != kStatusPolish) continue;   // (block-uniform)
     if (tid == 0) atomicAdd(A.stats + 0, 1);
+    if (tid == 0 && A.alongside) atomicAdd(A.taken, 1);
     const bool eq = A.s_eq[b] != 0;
     const double pd_user = A.pdiag[b];
 

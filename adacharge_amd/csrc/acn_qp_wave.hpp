@@ -260,7 +260,8 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     }
   };
 
-  for (int q_round = 0;; ++q_round) {   // work queue: this WAVE's (pair's) next problem
+  int q_round = 0;                      // problems this wave (group) has taken and finished
+  for (;; ++q_round) {   // work queue: this WAVE's (pair's) next problem
   int q_pos;
   if constexpr (NPW >= 2) {   // the group's first wave fetches; the position travels through the mailbox
     int mine = 0;
@@ -1161,6 +1162,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     STAMP(7);   // residual check (amortised)
   }
   it_total += it;
+  if (lane == 0 && half == 0) A.iters[b] = it_total;   // (ahead of the hand-over's publication: the polish adds its rounds)
   // ---- results of this pass: the feasible iterate z1 is the schedule (kept if it beats the earlier passes) ---------------
   if (pass == 0 || status_rank(status) > status_rank(best_status)) {   // wave-uniform
     best_status = status;
@@ -1183,6 +1185,10 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
         if (ja >= 0 && t_o < TS && tb + t_o < Tm) A.y_out[((size_t)b * A.Mg + ja) * Tm + tb + t_o] = y2[r] * RS[j];
       }
     }
+    // A hand-over may be consumed while this launch still runs (the polish launched alongside): every lane
+    // of every part makes its x / y_out stores visible to the whole device (the XCDs' L2s) BEFORE the group's last mailbox
+    // exchange, and part 0 publishes the problem after it.  Wave-uniform, and the same in every part.
+    if (status == kStatusPolish) __threadfence();
     ol = wave_sum<real>(ol);
     { real o1[1] = {ol}; pu_sum(o1, 1); ol = o1[0]; }
     if (lane == 0 && half == 0) {
@@ -1192,10 +1198,12 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
       A.pri[b] = pri;
       A.dua[b] = dua;
       A.obj[b] = ol;
-      if (status == kStatusPolish) A.pol_list[atomicAdd(A.pol_count, 1)] = b;
+      if (status == kStatusPolish) {   // reserve the slot, then publish into it (the list is preset to -1): release, device scope
+        const int slot = atomicAdd(A.pol_count, 1);
+        __hip_atomic_store(A.pol_list + slot, b, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
   }
-  if (lane == 0 && half == 0) A.iters[b] = it_total;
 #ifdef ACNQP_STAMPS
   {
     unsigned long long st_rt1, st_t1;
@@ -1210,6 +1218,11 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
   if (!retry_wanted(pass, A.retry_passes, status, it, A.stall_iters, A.adapt_every)) break;
   }   // passes
   }   // work queue
+  // The completion signal of a launch with a polish alongside it: this wave's (group's) problems are finished and, where
+  // handed over, published.  Counted in PROBLEMS, once per wave when it leaves the queue: the total reaches the launch's
+  // batch however many of its workgroups ever became resident.
+  if (A_kernarg.pol_retired != nullptr && lane == 0 && half == 0 && q_round > 0)
+    __hip_atomic_fetch_add(A_kernarg.pol_retired, q_round, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 #undef BIGC
 #undef EKOF
 }
