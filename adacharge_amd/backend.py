@@ -4,10 +4,15 @@ There is exactly one compute path: the HIP library.  If it is missing or no GPU
 is visible, everything here raises -- there is no CPU fallback by design
 (the CPU implementations under oracle/ are test infrastructure and are never
 imported from this package).
+
+Each fact of the ABI is stated once: the arrays of a struct and their dtypes in one ``_*_ARRAYS``
+map, from which the ctypes mirror, the marshallers and the plan classes are made; the entry points in ``_ABI``;
+tests/test_abi.py holds every struct and constant to the header.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -34,193 +39,159 @@ STATUS_NAMES = {
     STATUS_EMPTY_SET: "infeasible",
     STATUS_SOLVED_INACCURATE: "optimal_inaccurate",
 }
+PILOTS_CONTINUOUS, PILOTS_DISCRETE, PILOTS_REALLOCATE = 0, 1, 2
+ADVANCE_REFUSED, ADVANCE_NO_ROW, ADVANCE_BAD_SLOT = 1, 2, 4
+PREPARE_FUTURE = 1
+# kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
+ROUTE_NAMES = {1: "wave1", 2: "wave2", 3: "wave3", 4: "wave4", 5: "wave5", 6: "tiled_ct1", 7: "tiled_ct2",
+               8: "long_lds", 9: "long_ws", 10: "stream", 11: "general"}
 
 
 class BackendUnavailable(RuntimeError):
     """The HIP library could not be loaded or no MI355X is visible."""
 
 
+# ---- the structs of include/acn_qp.h -----------------------------------------------------------------------------------
+# A struct's arrays, in the header's order, with the dtype the library reads or writes: the ctypes mirror, the host
+# marshallers, DeviceBatch and the plan classes below are all made from these maps.
+_I4, _F8, _U1 = np.int32, np.float64, np.uint8
+_PROBLEM_ARRAYS = dict(horizon=_I4, lb=_F8, ub=_F8, q=_F8, pdiag=_F8, s_off=_I4, s_len=_I4, s_cap=_F8, s_eq=_U1, peak=_F8, lf=_F8,
+                       dc=_F8, dfloor=_F8)
+_NEXT_ARRAYS = tuple(k for k in _PROBLEM_ARRAYS if k != "s_eq")   # acnqp_next: the same, writable; s_eq does not change with time
+_WARM = ("warm_x", "warm_y")
+_TABLE_ARRAYS = dict(horizon=_I4, q_index=_I4, q_table=_F8, pdiag=_F8, s_eq=_U1, peak=_F8, lf=_F8, dc=_F8, dfloor=_F8, sess_seg=_I4,
+                     s_evse=_I4, s_slot=_I4, s_off=_I4, s_len=_I4, s_cap=_F8, rate_seg=_I4, min_rates=_F8, max_rates=_F8)
+_RESULT_ARRAYS = dict(x=_F8, status=_I4, iters=_I4, pri_res=_F8, dua_res=_F8, obj=_F8)   # then y and x_dev, both optional
+_PILOT_ARRAYS = dict(cre=_F8, cim=_F8, limits=_F8, max_pilot=_F8, levels=_F8, sess_seg=_I4, s_evse=_I4, s_arrived=_U1, s_cap=_F8)
+_ADVANCE_ARRAYS = dict(q_table=_F8, h_scal=_F8, h_row=_I4, peak_series=_F8, a_seg=_I4, a_evse=_I4, a_slot=_I4, a_len=_I4, a_cap=_F8,
+                       a_rate_seg=_I4, a_min=_F8, a_max=_F8)
+_COST_ARRAYS = dict(c_weight=_F8, c_series=_F8)   # weight and series of acnqp_clock_cost, under AdvancePlan's names
+_PREPARE_ARRAYS = dict(key=_I4, cre=_F8, cim=_F8, limits=_F8, min_pilot=_F8)
+
+
+def _ints(*names):
+    return [(k, C.c_int32) for k in names]
+
+
+def _doubles(*names):
+    return [(k, C.c_double) for k in names]
+
+
+def _ptrs(*names):
+    return [(k, C.c_void_p) for k in names]
+
+
 class _Site(C.Structure):
-    _fields_ = [
-        ("n_evse", C.c_int32),
-        ("n_infra", C.c_int32),
-        ("n_rows", C.c_int32),
-        ("cone", C.c_int32),
-        ("has_peak", C.c_int32),
-        ("has_flat", C.c_int32),
-        ("has_max", C.c_int32),
-        ("G", C.c_void_p),
-        ("limits", C.c_void_p),
-    ]
+    _fields_ = _ints("n_evse", "n_infra", "n_rows", "cone", "has_peak", "has_flat", "has_max") + _ptrs("G", "limits")
 
 
 class _Problems(C.Structure):
-    _fields_ = [
-        ("batch", C.c_int32),
-        ("t_max", C.c_int32),
-        ("k_sessions", C.c_int32),
-        ("horizon", C.c_void_p),
-        ("lb", C.c_void_p),
-        ("ub", C.c_void_p),
-        ("q", C.c_void_p),
-        ("pdiag", C.c_void_p),
-        ("s_off", C.c_void_p),
-        ("s_len", C.c_void_p),
-        ("s_cap", C.c_void_p),
-        ("s_eq", C.c_void_p),
-        ("peak", C.c_void_p),
-        ("lf", C.c_void_p),
-        ("dc", C.c_void_p),
-        ("dfloor", C.c_void_p),
-        ("warm_x", C.c_void_p),
-        ("warm_y", C.c_void_p),
-    ]
+    """Mirror of ``acnqp_problems``: ``_Problems(B, Tm, K, s_off=..., s_len=...)`` leaves every array not named NULL."""
+
+    _fields_ = _ints("batch", "t_max", "k_sessions") + _ptrs(*_PROBLEM_ARRAYS, *_WARM)
 
 
 class _Table(C.Structure):
-    """Mirror of ``acnqp_table`` (include/acn_qp.h)."""
-
-    _fields_ = [(k, C.c_int32) for k in ("batch", "t_max", "k_sessions", "n_sessions", "n_horizons")] + [
-        (k, C.c_void_p) for k in ("horizon", "q_index", "q_table", "pdiag", "s_eq", "peak", "lf", "dc", "dfloor", "sess_seg",
-                                  "s_evse", "s_slot", "s_off", "s_len", "s_cap", "rate_seg", "min_rates", "max_rates")]
+    _fields_ = _ints("batch", "t_max", "k_sessions", "n_sessions", "n_horizons") + _ptrs(*_TABLE_ARRAYS)
 
 
 class _Results(C.Structure):
-    _fields_ = [
-        ("x", C.c_void_p),
-        ("status", C.c_void_p),
-        ("iters", C.c_void_p),
-        ("pri_res", C.c_void_p),
-        ("dua_res", C.c_void_p),
-        ("obj", C.c_void_p),
-        ("y", C.c_void_p),
-        ("x_dev", C.c_void_p),
-    ]
+    _fields_ = _ptrs(*_RESULT_ARRAYS, "y", "x_dev")
 
 
 class _Duals(C.Structure):
-    """Mirror of ``acnqp_duals`` (include/acn_qp.h)."""
-
-    _fields_ = [("mu", C.c_void_p), ("z", C.c_void_p), ("res", C.c_void_p)]
+    _fields_ = _ptrs("mu", "z", "res")
 
 
 class _PilotPlan(C.Structure):
-    """Mirror of ``acnqp_pilot_plan`` (include/acn_qp.h)."""
-
-    _fields_ = [(k, C.c_int32) for k in ("batch", "t_max", "n_evse", "n_infra", "n_levels", "n_sessions", "mode")] + [
-        (k, C.c_void_p) for k in ("cre", "cim", "limits", "max_pilot", "levels", "sess_seg", "s_evse", "s_arrived", "s_cap")]
+    _fields_ = _ints("batch", "t_max", "n_evse", "n_infra", "n_levels", "n_sessions", "mode") + _ptrs(*_PILOT_ARRAYS)
 
 
 class _Pilots(C.Structure):
-    """Mirror of ``acnqp_pilots`` (include/acn_qp.h)."""
-
-    _fields_ = [("pilots", C.c_void_p), ("first", C.c_void_p), ("visits", C.c_void_p)]
-
-
-PILOTS_CONTINUOUS, PILOTS_DISCRETE, PILOTS_REALLOCATE = 0, 1, 2
+    _fields_ = _ptrs("pilots", "first", "visits")
 
 
 class _AdvancePlan(C.Structure):
-    """Mirror of ``acnqp_advance_plan`` (include/acn_qp.h)."""
-
-    _fields_ = [(k, C.c_int32) for k in ("n_evse", "n_rows", "n_horizons", "step", "peak_len", "n_arrivals", "n_rates")] + [
-        ("done_tol", C.c_double), ("kw_per_amp", C.c_double), ("warm_arrival_gain", C.c_double)] + [
-        (k, C.c_void_p) for k in ("q_table", "h_scal", "h_row", "peak_series", "a_seg", "a_evse", "a_slot", "a_len", "a_cap",
-                                  "a_rate_seg", "a_min", "a_max")]
+    _fields_ = (_ints("n_evse", "n_rows", "n_horizons", "step", "peak_len", "n_arrivals", "n_rates")
+                + _doubles("done_tol", "kw_per_amp", "warm_arrival_gain") + _ptrs(*_ADVANCE_ARRAYS))
 
 
 class ClockCost(C.Structure):
-    """Mirror of ``acnqp_clock_cost`` (include/acn_qp.h): the clock cost of the advance's rule 6b."""
+    """Mirror of ``acnqp_clock_cost``: the clock cost of the advance's rule 6b."""
 
-    _fields_ = [("n_evse", C.c_int32), ("series_len", C.c_int32), ("coef", C.c_double), ("weight", C.c_void_p), ("series", C.c_void_p)]
+    _fields_ = _ints("n_evse", "series_len") + _doubles("coef") + _ptrs("weight", "series")
 
 
 class _Next(C.Structure):
-    """Mirror of ``acnqp_next`` (include/acn_qp.h)."""
-
-    _fields_ = [(k, C.c_void_p) for k in ("horizon", "lb", "ub", "q", "pdiag", "s_off", "s_len", "s_cap", "peak", "lf", "dc",
-                                          "dfloor", "warm_x", "warm_y")]
-
-
-ADVANCE_REFUSED, ADVANCE_NO_ROW, ADVANCE_BAD_SLOT = 1, 2, 4
+    _fields_ = _ptrs(*_NEXT_ARRAYS, *_WARM)
 
 
 class _PreparePlan(C.Structure):
-    """Mirror of ``acnqp_prepare_plan`` (include/acn_qp.h)."""
-
-    _fields_ = [("n_evse", C.c_int32), ("n_infra", C.c_int32)] + [(k, C.c_void_p) for k in ("key", "cre", "cim", "limits", "min_pilot")]
+    _fields_ = _ints("n_evse", "n_infra") + _ptrs(*_PREPARE_ARRAYS)
 
 
 class _PrepareView(C.Structure):
-    """Mirror of ``acnqp_prepare_view`` (include/acn_qp.h)."""
-
-    _fields_ = [("v_evse", C.c_void_p), ("v_arrived", C.c_void_p), ("v_cap", C.c_void_p)]
-
-
-PREPARE_FUTURE = 1
+    _fields_ = _ptrs("v_evse", "v_arrived", "v_cap")
 
 
 class Options(C.Structure):
     """Mirror of ``acnqp_options``; construct with ``default_options()``."""
 
-    _fields_ = [
-        ("eps_abs", C.c_double),
-        ("eps_rel", C.c_double),
-        ("max_iter", C.c_int32),
-        ("check_every", C.c_int32),
-        ("adapt_every", C.c_int32),
-        ("rho", C.c_double),
-        ("sigma", C.c_double),
-        ("alpha", C.c_double),
-        ("adapt_tol", C.c_double),
-        ("reg_rel", C.c_double),
-        ("precision", C.c_int32),
-        ("accel_mem", C.c_int32),
-        ("stall_iters", C.c_int32),
-        ("retry_passes", C.c_int32),
-        ("retry_max_iter", C.c_int32),
-        ("polish_iters", C.c_int32),
-        ("retry_rho", C.c_double),
-        ("inaccurate_floor", C.c_double),
-        ("polish_stall", C.c_int32),
+    _fields_ = (_doubles("eps_abs", "eps_rel") + _ints("max_iter", "check_every", "adapt_every")
+                + _doubles("rho", "sigma", "alpha", "adapt_tol", "reg_rel")
+                + _ints("precision", "accel_mem", "stall_iters", "retry_passes", "retry_max_iter", "polish_iters")
+                + _doubles("retry_rho", "inaccurate_floor") + _ints("polish_stall"))
+
+
+# ---- the entry points --------------------------------------------------------------------------------------------------
+def _abi():
+    """(name, restype, argtypes, declared): the prototype of every entry the binding calls.  ``declared``: the header
+    declares it, so every build exports it; the others are introspection that a build may lack."""
+    P, ptr, i32, i64, rc = C.POINTER, C.c_void_p, C.c_int32, C.c_int64, C.c_int
+    h = stream = ptr
+    solve = [h, P(_Problems), P(Options), P(_Results)]
+    advance = [h, P(_Problems), ptr, ptr, ptr, ptr, P(_AdvancePlan)]   # cur, applied, status, x, y, plan
+    rows = [
+        ("acnqp_create", rc, [P(_Site), i32, P(ptr)]),
+        ("acnqp_destroy", None, [h]),
+        ("acnqp_solve_batch", rc, solve),
+        ("acnqp_solve_batch_device", rc, solve + [stream]),
+        ("acnqp_solve_batches", rc, [h, i32, P(_Problems), P(Options), P(_Results)]),
+        ("acnqp_solve_table", rc, [h, P(_Table), P(Options), P(_Results)]),
+        ("acnqp_host_alloc", ptr, [C.c_size_t]),
+        ("acnqp_host_free", None, [ptr]),
+        ("acnqp_default_options", None, [P(Options)]),
+        ("acnqp_last_error", C.c_char_p, []),
+        ("acnqp_abi_version", i32, []),
+        ("acnqp_last_kernel_ms", C.c_float, [h]),
+        ("acnqp_kernel_times", i32, [h, P(C.c_float), i32]),
+        ("acnqp_launch_count", i64, [h]),
+        ("acnqp_ordered_launch_count", i64, [h]),
+        ("acnqp_polish_stats", rc, [h, P(i64), i32]),
+        ("acnqp_accel_columns", i32, [h, i32, i32, i32, i32]),
+        ("acnqp_route", i32, [h, i32, i32, i32, P(i32)]),
     ]
+    # acnqp_X_host takes these arguments, acnqp_X_device the same and the stream behind them
+    for stem, args in (
+        ("acnqp_duals", [h, P(_Problems), P(Options), ptr, ptr, ptr, P(_Duals)]),
+        ("acnqp_pilots", [h, P(_PilotPlan), ptr, P(_Pilots)]),
+        ("acnqp_advance", advance + [P(_Next), ptr]),
+        ("acnqp_advance_priced", advance + [P(ClockCost), P(_Next), ptr]),
+        ("acnqp_prepare", [h, P(_Problems), P(_PreparePlan), ptr, ptr, P(_PrepareView), ptr]),
+    ):
+        rows += [(stem + "_host", rc, args), (stem + "_device", rc, args + [stream])]
+    introspection = [
+        ("acnqp_debug_polish_alongside", i64, [h]),
+        ("acnqp_debug_wave_rank", rc, [h, P(i32)]),
+        ("acnqp_debug_wave_evse_extent", rc, [h, P(i32)]),
+        ("acnqp_debug_copy_workspace", i64, [h, ptr, i64]),   # builds with -DACNQP_DEBUG_WS only (tools/gpu_long_race.py)
+    ]
+    return tuple(r + (True,) for r in rows) + tuple(r + (False,) for r in introspection)
 
 
+_ABI = _abi()
 # every symbol include/acn_qp.h declares; tests check the library exports all of them
-EXPORTED_SYMBOLS = (
-    "acnqp_create",
-    "acnqp_solve_batch",
-    "acnqp_solve_batch_device",
-    "acnqp_destroy",
-    "acnqp_default_options",
-    "acnqp_last_error",
-    "acnqp_abi_version",
-    "acnqp_last_kernel_ms",
-    "acnqp_accel_columns",
-    "acnqp_kernel_times",
-    "acnqp_ordered_launch_count",
-    "acnqp_polish_stats",
-    "acnqp_solve_batches",
-    "acnqp_solve_table",
-    "acnqp_host_alloc",
-    "acnqp_host_free",
-    "acnqp_launch_count",
-    "acnqp_route",
-    "acnqp_duals_device",
-    "acnqp_duals_host",
-    "acnqp_pilots_device",
-    "acnqp_pilots_host",
-    "acnqp_advance_device",
-    "acnqp_advance_host",
-    "acnqp_advance_priced_device",
-    "acnqp_advance_priced_host",
-    "acnqp_prepare_device",
-    "acnqp_prepare_host",
-)
-
-# kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
-ROUTE_NAMES = {1: "wave1", 2: "wave2", 3: "wave3", 4: "wave4", 5: "wave5", 6: "tiled_ct1", 7: "tiled_ct2",
-               8: "long_lds", 9: "long_ws", 10: "stream", 11: "general"}
+EXPORTED_SYMBOLS = tuple(name for name, _, _, declared in _ABI if declared)
 
 _lib = None
 
@@ -251,72 +222,10 @@ def load_library():
         lib = C.CDLL(path)
     except OSError as exc:  # missing ROCm runtime etc.
         raise BackendUnavailable(f"cannot load {path}: {exc}") from exc
-    lib.acnqp_create.argtypes = [C.POINTER(_Site), C.c_int32, C.POINTER(C.c_void_p)]
-    lib.acnqp_create.restype = C.c_int
-    lib.acnqp_solve_batch.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(Options), C.POINTER(_Results)]
-    lib.acnqp_solve_batch.restype = C.c_int
-    lib.acnqp_solve_batch_device.argtypes = [
-        C.c_void_p, C.POINTER(_Problems), C.POINTER(Options), C.POINTER(_Results), C.c_void_p,
-    ]
-    lib.acnqp_solve_batch_device.restype = C.c_int
-    lib.acnqp_destroy.argtypes = [C.c_void_p]
-    lib.acnqp_destroy.restype = None
-    lib.acnqp_default_options.argtypes = [C.POINTER(Options)]
-    lib.acnqp_default_options.restype = None
-    lib.acnqp_last_error.argtypes = []
-    lib.acnqp_last_error.restype = C.c_char_p
-    lib.acnqp_abi_version.argtypes = []
-    lib.acnqp_abi_version.restype = C.c_int32
-    lib.acnqp_last_kernel_ms.argtypes = [C.c_void_p]
-    lib.acnqp_last_kernel_ms.restype = C.c_float
-    lib.acnqp_accel_columns.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    lib.acnqp_accel_columns.restype = C.c_int32
-    lib.acnqp_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int32]
-    lib.acnqp_kernel_times.restype = C.c_int32
-    lib.acnqp_solve_batches.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_Problems), C.POINTER(Options), C.POINTER(_Results)]
-    lib.acnqp_solve_batches.restype = C.c_int
-    lib.acnqp_solve_table.argtypes = [C.c_void_p, C.POINTER(_Table), C.POINTER(Options), C.POINTER(_Results)]
-    lib.acnqp_solve_table.restype = C.c_int
-    lib.acnqp_host_alloc.argtypes = [C.c_size_t]
-    lib.acnqp_host_alloc.restype = C.c_void_p
-    lib.acnqp_host_free.argtypes = [C.c_void_p]
-    lib.acnqp_host_free.restype = None
-    lib.acnqp_launch_count.argtypes = [C.c_void_p]
-    lib.acnqp_launch_count.restype = C.c_int64
-    lib.acnqp_ordered_launch_count.argtypes = [C.c_void_p]
-    lib.acnqp_ordered_launch_count.restype = C.c_int64
-    lib.acnqp_polish_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
-    lib.acnqp_polish_stats.restype = C.c_int
-    lib.acnqp_route.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    lib.acnqp_route.restype = C.c_int32
-    lib.acnqp_duals_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.POINTER(_Duals), C.c_void_p]
-    lib.acnqp_duals_device.restype = C.c_int
-    lib.acnqp_duals_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.POINTER(_Duals)]
-    lib.acnqp_duals_host.restype = C.c_int
-    lib.acnqp_pilots_device.argtypes = [C.c_void_p, C.POINTER(_PilotPlan), C.c_void_p, C.POINTER(_Pilots), C.c_void_p]
-    lib.acnqp_pilots_device.restype = C.c_int
-    lib.acnqp_pilots_host.argtypes = [C.c_void_p, C.POINTER(_PilotPlan), C.c_void_p, C.POINTER(_Pilots)]
-    lib.acnqp_pilots_host.restype = C.c_int
-    lib.acnqp_advance_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.POINTER(_AdvancePlan), C.POINTER(_Next), C.c_void_p, C.c_void_p]
-    lib.acnqp_advance_device.restype = C.c_int
-    lib.acnqp_advance_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.POINTER(_AdvancePlan), C.POINTER(_Next), C.c_void_p]
-    lib.acnqp_advance_host.restype = C.c_int
-    lib.acnqp_advance_priced_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.POINTER(_AdvancePlan), C.POINTER(ClockCost), C.POINTER(_Next), C.c_void_p, C.c_void_p]
-    lib.acnqp_advance_priced_device.restype = C.c_int
-    lib.acnqp_advance_priced_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                              C.POINTER(_AdvancePlan), C.POINTER(ClockCost), C.POINTER(_Next), C.c_void_p]
-    lib.acnqp_advance_priced_host.restype = C.c_int
-    lib.acnqp_prepare_device.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(_PreparePlan), C.c_void_p, C.c_void_p,
-                                         C.POINTER(_PrepareView), C.c_void_p, C.c_void_p]
-    lib.acnqp_prepare_device.restype = C.c_int
-    lib.acnqp_prepare_host.argtypes = [C.c_void_p, C.POINTER(_Problems), C.POINTER(_PreparePlan), C.c_void_p, C.c_void_p,
-                                       C.POINTER(_PrepareView), C.c_void_p]
-    lib.acnqp_prepare_host.restype = C.c_int
+    for name, restype, argtypes, declared in _ABI:
+        if declared or hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -341,13 +250,103 @@ def _check(rc: int, what: str):
         raise RuntimeError(f"{what} failed (rc={rc}): {msg}")
 
 
+# ---- arrays and tensors to pointers ------------------------------------------------------------------------------------
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _addr(a: Optional[np.ndarray]):
+    """the address of an array as an int (None stays None), for a struct field whose array the caller keeps alive: half the
+    cost of ``_ptr``, whose c_void_p also holds on to the array"""
+    return None if a is None else a.ctypes.data
 
 
 def _dptr(t):
     """the device address of a torch tensor (None stays None)"""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _f8(a):
+    return None if a is None else np.ascontiguousarray(a, np.float64)
+
+
+def _i4(a):
+    return None if a is None else np.ascontiguousarray(a, np.int32)
+
+
+def _torch_dtype(dtype):
+    import torch
+
+    return getattr(torch, np.dtype(dtype).name)
+
+
+def _want(t, name: str, dtype, shape=None, device=None) -> None:
+    """The one check of a tensor argument; None passes.  With ``device``: a contiguous torch tensor of ``dtype`` there (and
+    of ``shape``, when one is given).  Without: contiguity, shape and the ITEM SIZE of ``dtype`` only, on any device -- all
+    the entries older than ``pilots_device`` ever asked, kept so that they refuse nothing they took."""
+    if t is None:
+        return
+    if device is None:
+        ok = t.element_size() == np.dtype(dtype).itemsize
+    else:
+        import torch
+
+        ok = isinstance(t, torch.Tensor) and t.device == device and t.dtype == _torch_dtype(dtype)
+    if not ok or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous torch.{np.dtype(dtype).name} tensor" + ("" if device is None else f" on {device}")
+                         + ("" if shape is None else f" of shape {tuple(shape)}"))
+
+
+def _absent(site: SiteData, peak: bool = False) -> tuple:
+    """the optional arrays that are NULL for this site: those of a row it does not have (``peak``: the peak row's too)"""
+    return (() if site.has_flat else ("lf",)) + (() if site.has_max else ("dc", "dfloor")) + (("peak",) if peak and not site.has_peak else ())
+
+
+def _host_arrays(src, arrays: dict, absent) -> dict:
+    """{name: array or None} of a struct's ``arrays`` from the attributes of ``src`` (a ProblemBatch or TablePlan, which call the
+    horizons T): C-contiguous with the ABI's dtype -- the attribute itself when it already is (e.g. pinned arrays from
+    ``pinned_empty``), else a copy; None for a name in ``absent`` and for an attribute that is None."""
+    return {k: None if k in absent or (a := getattr(src, "T" if k == "horizon" else k)) is None else np.ascontiguousarray(a, dt)
+            for k, dt in arrays.items()}
+
+
+def _new_results(B: int, N: int, Tm: int, Mg: int, pinned: bool, want_y: bool, x_dev=None, out: Optional["BatchResult"] = None):
+    """(BatchResult, _Results pointing into it): ``out`` when its arrays have the shapes asked for, else new arrays (pinned
+    or not).  ``x_dev``: the device address for acnqp_results.x_dev, or None."""
+    if out is not None and out.x.shape == (B, N, Tm) and (not want_y or (out.y is not None and out.y.shape == (B, Mg, Tm))):
+        res = out
+    else:
+        new = pinned_empty if pinned else np.zeros
+        res = BatchResult(*[new((B, N, Tm) if k == "x" else B, dt) for k, dt in _RESULT_ARRAYS.items()])
+        if want_y:
+            res.y = new((B, Mg, Tm))
+    r = _Results(*[_addr(getattr(res, k)) for k in _RESULT_ARRAYS], _addr(res.y) if want_y else None,
+                 None if x_dev is None else C.c_void_p(int(x_dev)))
+    return res, r
+
+
+def _marshal_batch(site: SiteData, batch: ProblemBatch, pinned: bool, x_dev=None, warm=None, want_y=False):
+    """ctypes views of one batch of host arrays for ``site``: (_Problems, _Results, BatchResult, keep-alive).  lf, dc and
+    dfloor are NULL where the site has no such row: that skips a copy in the library."""
+    B, N, Tm = batch.B, batch.N, batch.Tm
+    arrs = _host_arrays(batch, _PROBLEM_ARRAYS, _absent(site))
+    wx = wy = None
+    if warm is not None:
+        wx, wy = _f8(warm[0]), _f8(warm[1])
+        if wx.shape != (B, N, Tm) or wy.shape != (B, site.Mg, Tm):
+            raise ValueError(f"warm start arrays must have shapes {(B, N, Tm)} and {(B, site.Mg, Tm)}")
+    p = _Problems(B, Tm, batch.K, *[_addr(a) for a in arrs.values()], _addr(wx), _addr(wy))
+    res, r = _new_results(B, N, Tm, site.Mg, pinned, want_y, x_dev)
+    return p, r, res, (arrs, wx, wy)
+
+
+def _device_problems(dev: "DeviceBatch", warm_x=None, warm_y=None) -> _Problems:
+    """The ``acnqp_problems`` of a ``DeviceBatch``: the address of every tensor it holds, NULL for a peak it does not have
+    and for a warm start that is not given.  lf, dc and dfloor are always passed, because a ``DeviceBatch`` always holds
+    them, also for a site without a flat or max row: the library reads them only under has_flat / has_max (``tiled_args``
+    in acn_qp_api.hip, ``check_problem_shapes`` and the duals entry in acn_qp_post.hpp) and refuses a NULL only where the row
+    exists, so the extra addresses are never looked at."""
+    return _Problems(dev.B, dev.Tm, dev.K, *[_dptr(getattr(dev, k)) for k in _PROBLEM_ARRAYS], _dptr(warm_x), _dptr(warm_y))
 
 
 @dataclass
@@ -377,8 +376,42 @@ class DualResult:
     comp: np.ndarray     # (B,) worst multiplier x slack over the site rows (oracle-free KKT check, scaled as documented)
 
 
+class _PlanArrays:
+    """What the three plan classes share.  ``_DTYPES``: {array field: the dtype the ABI reads}."""
+
+    _DTYPES = {}
+
+    def to_device(self, device):
+        """the same plan with every array a torch tensor of the ABI's dtype on ``device``"""
+        import torch
+
+        moved = {k: None if getattr(self, k) is None else torch.from_numpy(np.ascontiguousarray(getattr(self, k), dt)).to(device)
+                 for k, dt in self._DTYPES.items()}
+        return dataclasses.replace(self, **moved)
+
+    def _p(self, k: str, keep=None, row: int = 0, stacked: Optional[int] = None):
+        """The pointer of field ``k`` for the struct: NULL when it is None or empty; a tensor's ``data_ptr()``; for an
+        array, the address of a C-contiguous array of the field's dtype -- the array itself when it is one, else a copy --
+        which is appended to ``keep`` so that it outlives the call.  A field with ``stacked`` dimensions holds one block per
+        step: ``row`` picks the step's."""
+        a = getattr(self, k)
+        if a is None or (a.numel() if hasattr(a, "numel") else a.size) == 0:
+            return None
+        if a.ndim == stacked:
+            a = a[row]
+        if hasattr(a, "data_ptr"):
+            return C.c_void_p(a.data_ptr())
+        a = np.ascontiguousarray(a, self._DTYPES[k])
+        if keep is not None:
+            keep.append(a)
+        return _ptr(a)
+
+    def _len(self, k: str, axis: int = 0) -> int:
+        return 0 if getattr(self, k) is None else int(getattr(self, k).shape[axis])
+
+
 @dataclass
-class PilotPlan:
+class PilotPlan(_PlanArrays):
     """The arrays of ``acnqp_pilot_plan`` (include/acn_qp.h): numpy arrays for ``SiteHandle.pilots``, torch tensors on the
     handle's GPU (``to_device``) for ``SiteHandle.pilots_device``.  ``postprocessing.pilot_plan_arrays`` builds one."""
     mode: int
@@ -395,30 +428,16 @@ class PilotPlan:
     s_arrived: Optional[object] = None   # (S,) uint8
     s_cap: Optional[object] = None       # (S,)
 
-    _ARRAYS = ("cre", "cim", "limits", "max_pilot", "levels", "sess_seg", "s_evse", "s_arrived", "s_cap")
+    _DTYPES = _PILOT_ARRAYS
+    _ARRAYS = tuple(_PILOT_ARRAYS)
 
-    def to_device(self, device) -> "PilotPlan":
-        import torch
-
-        moved = {k: None if getattr(self, k) is None else torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
-                 for k in self._ARRAYS}
-        return PilotPlan(self.mode, self.B, self.Tm, self.N, **moved)
-
-    def _struct(self, batch=None, t_max=None) -> "_PilotPlan":
-        def ptr(a):
-            if a is None or (hasattr(a, "numel") and a.numel() == 0) or (isinstance(a, np.ndarray) and a.size == 0):
-                return None
-            return C.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else _ptr(a)
-
-        M = 0 if self.cre is None else int(self.cre.shape[0])
-        L = 0 if self.levels is None else int(self.levels.shape[1])
-        S = 0 if self.s_evse is None else int(self.s_evse.shape[0])
-        return _PilotPlan(int(self.B if batch is None else batch), int(self.Tm if t_max is None else t_max), self.N, M, L, S,
-                          self.mode, *[ptr(getattr(self, k)) for k in self._ARRAYS])
+    def _struct(self, batch=None, t_max=None, keep=None) -> "_PilotPlan":
+        return _PilotPlan(int(self.B if batch is None else batch), int(self.Tm if t_max is None else t_max), self.N, self._len("cre"),
+                          self._len("levels", 1), self._len("s_evse"), self.mode, *[self._p(k, keep) for k in _PILOT_ARRAYS])
 
 
 @dataclass
-class AdvancePlan:
+class AdvancePlan(_PlanArrays):
     """The arrays of ``acnqp_advance_plan`` (include/acn_qp.h): numpy arrays for ``SiteHandle.advance``, torch tensors on the
     handle's GPU (``to_device``) for ``SiteHandle.advance_device``.  ``a_seg`` may hold one row of B + 1 entries per step
     (``(steps, B + 1)``, absolute record indices): ``seg_row`` picks the step's.  ``rollout.FleetTable`` builds one.
@@ -443,43 +462,16 @@ class AdvancePlan:
     c_weight: Optional[object] = None     # (N,)
     c_series: Optional[object] = None     # (B, P)
 
-    _COST = ("c_weight", "c_series")
-    _ARRAYS = ("q_table", "h_scal", "h_row", "peak_series", "a_seg", "a_evse", "a_slot", "a_len", "a_cap", "a_rate_seg", "a_min", "a_max")
-    _INT = ("h_row", "a_seg", "a_evse", "a_slot", "a_len", "a_rate_seg")
-
-    def to_device(self, device) -> "AdvancePlan":
-        import torch
-
-        moved = {}
-        for k in self._ARRAYS:
-            a = getattr(self, k)
-            moved[k] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int32 if k in self._INT else np.float64)).to(device)
-        for k in self._COST:
-            a = getattr(self, k)
-            moved[k] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(device)
-        return AdvancePlan(done_tol=self.done_tol, kw_per_amp=self.kw_per_amp, warm_arrival_gain=self.warm_arrival_gain, c_coef=self.c_coef, **moved)
+    _DTYPES = {**_ADVANCE_ARRAYS, **_COST_ARRAYS}
+    _ARRAYS = tuple(_ADVANCE_ARRAYS)
 
     def _struct(self, N: int, Mg: int, step: int, seg_row: int = 0, keep=None) -> "_AdvancePlan":
-        def ptr(k, row=None):
-            a = getattr(self, k)
-            if a is None or (a.numel() if hasattr(a, "numel") else a.size) == 0:
-                return None
-            if row is not None and a.ndim == 2:
-                a = a[row]
-            if hasattr(a, "data_ptr"):
-                return C.c_void_p(a.data_ptr())
-            a = np.ascontiguousarray(a, np.int32 if k in self._INT else np.float64)
-            if keep is not None:
-                keep.append(a)
-            return _ptr(a)
-
-        A = 0 if self.a_evse is None else int(self.a_evse.shape[0])
-        R = 0 if self.a_min is None else int(self.a_min.shape[0])
-        P = 0 if self.peak_series is None else int(self.peak_series.shape[1])
-        return _AdvancePlan(int(N), int(Mg), int(self.q_table.shape[0]), int(step), P, A, R, float(self.done_tol), float(self.kw_per_amp),
-                            float(self.warm_arrival_gain),
-                            ptr("q_table"), ptr("h_scal"), ptr("h_row"), ptr("peak_series"), ptr("a_seg", seg_row) if A else None,
-                            ptr("a_evse"), ptr("a_slot"), ptr("a_len"), ptr("a_cap"), ptr("a_rate_seg"), ptr("a_min"), ptr("a_max"))
+        A = self._len("a_evse")
+        ptrs = [self._p(k, keep, seg_row, 2 if k == "a_seg" else None) for k in _ADVANCE_ARRAYS]
+        if not A:   # a_seg is NULL iff there is no arrival
+            ptrs[self._ARRAYS.index("a_seg")] = None
+        return _AdvancePlan(int(N), int(Mg), int(self.q_table.shape[0]), int(step), self._len("peak_series", 1), A, self._len("a_min"),
+                            float(self.done_tol), float(self.kw_per_amp), float(self.warm_arrival_gain), *ptrs)
 
     def _cost_struct(self, N: int, keep=None) -> Optional["ClockCost"]:
         """the ``acnqp_clock_cost`` of the plan, or None (the plain advance) when no c_ field is set"""
@@ -490,23 +482,14 @@ class AdvancePlan:
             raise ValueError("a clock cost needs c_coef, c_weight and c_series")
         if self.c_series.ndim != 2:
             raise ValueError("c_series must have shape (B, P)")
-        ptrs = []
-        for k in self._COST:
-            a = getattr(self, k)
-            if hasattr(a, "data_ptr"):
-                if a.element_size() != 8 or not a.is_contiguous():
-                    raise ValueError(f"{k} must be a contiguous float64 tensor")
-                ptrs.append(C.c_void_p(a.data_ptr()) if a.numel() else None)
-            else:
-                a = np.ascontiguousarray(a, np.float64)
-                if keep is not None:
-                    keep.append(a)
-                ptrs.append(_ptr(a) if a.size else None)
-        return ClockCost(int(N), int(self.c_series.shape[1]), float(self.c_coef), *ptrs)
+        for k, dt in _COST_ARRAYS.items():
+            if hasattr(getattr(self, k), "data_ptr"):
+                _want(getattr(self, k), k, dt)
+        return ClockCost(int(N), int(self.c_series.shape[1]), float(self.c_coef), *[self._p(k, keep) for k in _COST_ARRAYS])
 
 
 @dataclass
-class PreparePlan:
+class PreparePlan(_PlanArrays):
     """The arrays of ``acnqp_prepare_plan`` (include/acn_qp.h): numpy arrays for ``SiteHandle.prepare_host``, torch tensors on the
     handle's GPU (``to_device``) for ``SiteHandle.prepare_device``.  ``key`` may hold one (B, N) block per step
     (``(steps, B, N)``): ``key_row`` picks the step's.  ``min_pilot=None``: no minimum-rate step."""
@@ -516,33 +499,12 @@ class PreparePlan:
     limits: Optional[object] = None      # (M,)
     min_pilot: Optional[object] = None   # (N,)
 
-    _ARRAYS = ("key", "cre", "cim", "limits", "min_pilot")
-
-    def to_device(self, device) -> "PreparePlan":
-        import torch
-
-        moved = {}
-        for k in self._ARRAYS:
-            a = getattr(self, k)
-            moved[k] = None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int32 if k == "key" else np.float64)).to(device)
-        return PreparePlan(**moved)
+    _DTYPES = _PREPARE_ARRAYS
+    _ARRAYS = tuple(_PREPARE_ARRAYS)
 
     def _struct(self, N: int, key_row=None, min_rates: bool = True, keep=None) -> "_PreparePlan":
-        def ptr(k):
-            a = getattr(self, k)
-            if a is None or (a.numel() if hasattr(a, "numel") else a.size) == 0:
-                return None
-            if k == "key" and a.ndim == 3:
-                a = a[0 if key_row is None else key_row]
-            if hasattr(a, "data_ptr"):
-                return C.c_void_p(a.data_ptr())
-            a = np.ascontiguousarray(a, np.int32 if k == "key" else np.float64)
-            if keep is not None:
-                keep.append(a)
-            return _ptr(a)
-
-        M = 0 if self.cre is None else int(self.cre.shape[0])
-        return _PreparePlan(int(N), M, ptr("key"), ptr("cre"), ptr("cim"), ptr("limits"), ptr("min_pilot") if min_rates else None)
+        return _PreparePlan(int(N), self._len("cre"), self._p("key", keep, 0 if key_row is None else key_row, 3), self._p("cre", keep),
+                            self._p("cim", keep), self._p("limits", keep), self._p("min_pilot", keep) if min_rates else None)
 
 
 class _PinnedBlock:
@@ -617,42 +579,8 @@ class SiteHandle:
             raise ValueError("batch was built for a different site than this handle")
 
     def _marshal(self, batch: ProblemBatch, pinned: bool, x_dev=None, warm=None, want_y=False):
-        """ctypes views of one batch: (_Problems, _Results, BatchResult, keep-alive list).  Arrays that already
-        are C-contiguous with the ABI's dtype are passed as they are (e.g. pinned arrays from ``pinned_empty``)."""
-        B, N, Tm = batch.B, batch.N, batch.Tm
-        arrs = dict(
-            horizon=np.ascontiguousarray(batch.T, np.int32),
-            lb=np.ascontiguousarray(batch.lb, np.float64),
-            ub=np.ascontiguousarray(batch.ub, np.float64),
-            q=np.ascontiguousarray(batch.q, np.float64),
-            pdiag=np.ascontiguousarray(batch.pdiag, np.float64),
-            s_off=np.ascontiguousarray(batch.s_off, np.int32),
-            s_len=np.ascontiguousarray(batch.s_len, np.int32),
-            s_cap=np.ascontiguousarray(batch.s_cap, np.float64),
-            s_eq=np.ascontiguousarray(batch.s_eq, np.uint8),
-        )
-        peak = None if batch.peak is None else np.ascontiguousarray(batch.peak, np.float64)
-        lf = np.ascontiguousarray(batch.lf, np.float64) if self.site.has_flat else None
-        dc = np.ascontiguousarray(batch.dc, np.float64) if self.site.has_max else None
-        dfl = np.ascontiguousarray(batch.dfloor, np.float64) if self.site.has_max else None
-        wx = wy = None
-        if warm is not None:
-            wx = np.ascontiguousarray(warm[0], np.float64)
-            wy = np.ascontiguousarray(warm[1], np.float64)
-            if wx.shape != (B, N, Tm) or wy.shape != (B, self.site.Mg, Tm):
-                raise ValueError(f"warm start arrays must have shapes {(B, N, Tm)} and {(B, self.site.Mg, Tm)}")
-        p = _Problems(B, Tm, batch.K, *[_ptr(arrs[k]) for k in
-                                       ("horizon", "lb", "ub", "q", "pdiag", "s_off", "s_len", "s_cap", "s_eq")],
-                      _ptr(peak), _ptr(lf), _ptr(dc), _ptr(dfl), _ptr(wx), _ptr(wy))
-        new = pinned_empty if pinned else (lambda shape, dtype=np.float64: np.zeros(shape, dtype))
-        res = BatchResult(
-            new((B, N, Tm)), new(B, np.int32), new(B, np.int32), new(B), new(B), new(B),
-        )
-        if want_y:
-            res.y = new((B, self.site.Mg, Tm))
-        r = _Results(_ptr(res.x), _ptr(res.status), _ptr(res.iters), _ptr(res.pri_res), _ptr(res.dua_res), _ptr(res.obj),
-                     _ptr(res.y), None if x_dev is None else C.c_void_p(int(x_dev)))
-        return p, r, res, (arrs, peak, lf, dc, dfl, wx, wy)
+        """ctypes views of one batch: (_Problems, _Results, BatchResult, keep-alive) -- ``_marshal_batch`` for this site"""
+        return _marshal_batch(self.site, batch, pinned, x_dev, warm, want_y)
 
     def _finish(self, batch: ProblemBatch, res: "BatchResult"):
         if self.site.has_flat:   # the kernel's obj covers pdiag and q; add 1/2 lf sum_t (v' x_t)^2
@@ -695,29 +623,10 @@ class SiteHandle:
             raise ValueError("plan was built for another site")
         o = options if options is not None else default_options()
         B, N, Tm = plan.B, plan.N, plan.Tm
-        c = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)
-        keep = dict(
-            horizon=c(plan.T, np.int32), q_index=c(plan.q_index, np.int32), q_table=c(plan.q_table, np.float64),
-            pdiag=c(plan.pdiag, np.float64), s_eq=c(plan.s_eq, np.uint8), peak=c(plan.peak, np.float64) if self.site.has_peak else None,
-            lf=c(plan.lf, np.float64) if self.site.has_flat else None, dc=c(plan.dc, np.float64) if self.site.has_max else None,
-            dfloor=c(plan.dfloor, np.float64) if self.site.has_max else None, sess_seg=c(plan.sess_seg, np.int32),
-            s_evse=c(plan.s_evse, np.int32), s_slot=c(plan.s_slot, np.int32), s_off=c(plan.s_off, np.int32), s_len=c(plan.s_len, np.int32),
-            s_cap=c(plan.s_cap, np.float64), rate_seg=c(plan.rate_seg, np.int32), min_rates=c(plan.min_rates, np.float64),
-            max_rates=c(plan.max_rates, np.float64))
-        t = _Table(B, Tm, plan.K, plan.S, len(plan.q_table), *[_ptr(keep[k]) for k in (
-            "horizon", "q_index", "q_table", "pdiag", "s_eq", "peak", "lf", "dc", "dfloor", "sess_seg", "s_evse", "s_slot", "s_off",
-            "s_len", "s_cap", "rate_seg", "min_rates", "max_rates")])
-        new = pinned_empty if pinned_results else (lambda shape, dtype=np.float64: np.zeros(shape, dtype))
-        if out is not None and out.x.shape == (B, N, Tm) and (not want_y or (out.y is not None and out.y.shape == (B, self.site.Mg, Tm))):
-            res = out
-        else:
-            res = BatchResult(new((B, N, Tm)), new(B, np.int32), new(B, np.int32), new(B), new(B), new(B))
-            if want_y:
-                res.y = new((B, self.site.Mg, Tm))
-        r = _Results(_ptr(res.x), _ptr(res.status), _ptr(res.iters), _ptr(res.pri_res), _ptr(res.dua_res), _ptr(res.obj),
-                     _ptr(res.y) if want_y else None, None if x_dev is None else C.c_void_p(x_dev.data_ptr()))
-        if x_dev is not None and (tuple(x_dev.shape) != (B, N, Tm) or not x_dev.is_contiguous() or x_dev.element_size() != 8):
-            raise ValueError(f"x_dev must be a contiguous float64 tensor of shape {(B, N, Tm)}")
+        _want(x_dev, "x_dev", _F8, (B, N, Tm))
+        keep = _host_arrays(plan, _TABLE_ARRAYS, _absent(self.site, peak=True))
+        t = _Table(B, Tm, plan.K, plan.S, len(plan.q_table), *[_addr(a) for a in keep.values()])
+        res, r = _new_results(B, N, Tm, self.site.Mg, pinned_results, want_y, None if x_dev is None else x_dev.data_ptr(), out)
         res.x_dev = x_dev
         self.kernel_times()
         self._launches_seen = int(self._lib.acnqp_launch_count(self._h))
@@ -774,23 +683,10 @@ class SiteHandle:
         o = options if options is not None else default_options()
         if (warm_x is None) != (warm_y is None):
             raise ValueError("warm_x and warm_y go together (both or neither)")
-        if warm_x is not None and (tuple(warm_x.shape) != (dev.B, dev.N, dev.Tm) or tuple(warm_y.shape) != (dev.B, self.site.Mg, dev.Tm)
-                                   or not warm_x.is_contiguous() or not warm_y.is_contiguous()
-                                   or warm_x.element_size() != 8 or warm_y.element_size() != 8):
-            raise ValueError(f"warm start tensors must be contiguous float64 of shapes {(dev.B, dev.N, dev.Tm)} and {(dev.B, self.site.Mg, dev.Tm)}")
-        p = _Problems(
-            dev.B, dev.Tm, dev.K,
-            dev.horizon.data_ptr(), dev.lb.data_ptr(), dev.ub.data_ptr(), dev.q.data_ptr(), dev.pdiag.data_ptr(),
-            dev.s_off.data_ptr(), dev.s_len.data_ptr(), dev.s_cap.data_ptr(), dev.s_eq.data_ptr(),
-            None if dev.peak is None else dev.peak.data_ptr(),
-            dev.lf.data_ptr() if self.site.has_flat else None,
-            dev.dc.data_ptr() if self.site.has_max else None,
-            dev.dfloor.data_ptr() if self.site.has_max else None,
-            None if warm_x is None else warm_x.data_ptr(), None if warm_y is None else warm_y.data_ptr(),
-        )
-        r = _Results(dev.x.data_ptr(), dev.status.data_ptr(), dev.iters.data_ptr(),
-                     dev.pri_res.data_ptr(), dev.dua_res.data_ptr(), dev.obj.data_ptr(),
-                     None if dev.y is None else dev.y.data_ptr(), None)
+        _want(warm_x, "warm_x", _F8, (dev.B, dev.N, dev.Tm))
+        _want(warm_y, "warm_y", _F8, (dev.B, self.site.Mg, dev.Tm))
+        p = _device_problems(dev, warm_x, warm_y)
+        r = _Results(*[_dptr(getattr(dev, k)) for k in _RESULT_ARRAYS], _dptr(dev.y), None)
         _check(
             self._lib.acnqp_solve_batch_device(self._h, C.byref(p), C.byref(o), C.byref(r), C.c_void_p(stream)),
             "acnqp_solve_batch_device",
@@ -807,9 +703,7 @@ class SiteHandle:
             raise ValueError("duals need the site-row multipliers: solve with want_y=True")
         o = options if options is not None else default_options()
         p, _, _, keep = self._marshal(batch, False)
-        x = np.ascontiguousarray(res.x, np.float64)
-        y = None if res.y is None else np.ascontiguousarray(res.y, np.float64)
-        st = np.ascontiguousarray(res.status, np.int32)
+        x, y, st = _f8(res.x), _f8(res.y), _i4(res.status)
         if x.shape != (B, N, Tm) or st.shape != (B,) or (y is not None and y.shape != (B, self.site.Mg, Tm)):
             raise ValueError("result arrays do not match the batch")
         mu, z, r = np.zeros((B, K, N)), (np.zeros((B, N, Tm)) if want_z else None), np.zeros((B, 4))
@@ -826,21 +720,11 @@ class SiteHandle:
         o = options if options is not None else default_options()
         if self.site.Mg > 0 and dev.y is None:
             raise ValueError("duals need the site-row multipliers: DeviceBatch(..., want_y=True)")
-        p = _Problems(
-            dev.B, dev.Tm, dev.K,
-            dev.horizon.data_ptr(), dev.lb.data_ptr(), dev.ub.data_ptr(), dev.q.data_ptr(), dev.pdiag.data_ptr(),
-            dev.s_off.data_ptr(), dev.s_len.data_ptr(), dev.s_cap.data_ptr(), dev.s_eq.data_ptr(),
-            None if dev.peak is None else dev.peak.data_ptr(),
-            dev.lf.data_ptr() if self.site.has_flat else None,
-            dev.dc.data_ptr() if self.site.has_max else None,
-            dev.dfloor.data_ptr() if self.site.has_max else None,
-            None, None,
-        )
+        p = _device_problems(dev)
         d = _Duals(mu.data_ptr(), None if z is None else z.data_ptr(), res.data_ptr())
         _check(
-            self._lib.acnqp_duals_device(self._h, C.byref(p), C.byref(o), C.c_void_p(dev.x.data_ptr()),
-                                         None if dev.y is None else C.c_void_p(dev.y.data_ptr()),
-                                         C.c_void_p(dev.status.data_ptr()) if use_status else None, C.byref(d), C.c_void_p(stream)),
+            self._lib.acnqp_duals_device(self._h, C.byref(p), C.byref(o), _dptr(dev.x), _dptr(dev.y),
+                                         _dptr(dev.status) if use_status else None, C.byref(d), C.c_void_p(stream)),
             "acnqp_duals_device",
         )
 
@@ -855,9 +739,11 @@ class SiteHandle:
         pil = np.empty((B, N, Tm)) if want_pilots else None
         first = np.empty((B, N)) if want_first else None
         visits = np.empty(B, np.int32)
-        p = plan._struct(B, Tm)
+        keep = []
+        p = plan._struct(B, Tm, keep)
         out = _Pilots(_ptr(pil), _ptr(first), _ptr(visits))
         _check(self._lib.acnqp_pilots_host(self._h, C.byref(p), _ptr(x), C.byref(out)), "acnqp_pilots_host")
+        del keep
         return pil, first, visits
 
     def pilots_device(self, plan: PilotPlan, x, pilots=None, first=None, visits=None, stream: int = 0) -> None:
@@ -867,39 +753,23 @@ class SiteHandle:
         import torch
 
         here = torch.device("cuda", self.device)
-
-        def want(t, name, dtype, shape=None):
-            if t is None:
-                return
-            if not isinstance(t, torch.Tensor) or t.device != here or t.dtype != dtype or not t.is_contiguous() or (
-                    shape is not None and tuple(t.shape) != tuple(shape)):
-                raise ValueError(f"{name} must be a contiguous {dtype} tensor on {here}" + ("" if shape is None else f" of shape {tuple(shape)}"))
-
-        want(x, "x", torch.float64)
+        _want(x, "x", _F8, None, here)
         if x.dim() != 3 or x.shape[1] != plan.N:
             raise ValueError("x must have the shape (B, N, Tm) of the plan's site")
         B, N, Tm = x.shape
-        want(pilots, "pilots", torch.float64, (B, N, Tm))
-        want(first, "first", torch.float64, (B, N))
-        want(visits, "visits", torch.int32, (B,))
-        M = 0 if plan.cre is None else int(plan.cre.shape[0])
-        L = 0 if plan.levels is None else int(plan.levels.shape[1])
-        want(plan.max_pilot, "plan.max_pilot", torch.float64, (N,))
-        want(plan.levels, "plan.levels", torch.float64, (N, L))
-        want(plan.cre, "plan.cre", torch.float64, (M, N))
-        want(plan.cim, "plan.cim", torch.float64, (M, N))
-        want(plan.limits, "plan.limits", torch.float64, (M,))
-        want(plan.sess_seg, "plan.sess_seg", torch.int32, (B + 1,))
-        S = 0 if plan.s_evse is None else int(plan.s_evse.shape[0])
-        want(plan.s_evse, "plan.s_evse", torch.int32, (S,))
-        want(plan.s_arrived, "plan.s_arrived", torch.uint8, (S,))
-        want(plan.s_cap, "plan.s_cap", torch.float64, (S,))
+        M, L, S = plan._len("cre"), plan._len("levels", 1), plan._len("s_evse")
+        shapes = dict(max_pilot=(N,), levels=(N, L), cre=(M, N), cim=(M, N), limits=(M,), sess_seg=(B + 1,), s_evse=(S,), s_arrived=(S,),
+                      s_cap=(S,))
+        for t, name, dt, shape in ((pilots, "pilots", _F8, (B, N, Tm)), (first, "first", _F8, (B, N)), (visits, "visits", _I4, (B,))):
+            _want(t, name, dt, shape, here)
+        for k, shape in shapes.items():
+            _want(getattr(plan, k), "plan." + k, _PILOT_ARRAYS[k], shape, here)
         p = plan._struct(B, Tm)
         out = _Pilots(_dptr(pilots), _dptr(first), _dptr(visits))
         _check(self._lib.acnqp_pilots_device(self._h, C.byref(p), _dptr(x), C.byref(out), C.c_void_p(stream)), "acnqp_pilots_device")
 
     # -- time passes (acn_qp_advance.hpp) -------------------------------------------------------------------------------
-    _NEXT = ("horizon", "lb", "ub", "q", "pdiag", "s_off", "s_len", "s_cap", "peak", "lf", "dc", "dfloor")
+    _NEXT = _NEXT_ARRAYS
 
     def advance(self, cur: dict, applied, plan: AdvancePlan, step: int, status=None, x=None, y=None, want_warm: bool = False,
                 seg_row: int = 0) -> dict:
@@ -907,34 +777,31 @@ class SiteHandle:
         ``s_off, s_len, s_cap`` (B, K, N) and, on a site with a max row, ``dfloor`` (B,) -- after the pilots ``applied`` (B, N)
         of period ``step``, under ``plan`` (numpy arrays).  Returns a dict of the same layout with ``horizon, q, pdiag, lf, dc,
         peak, flags`` added and, with ``want_warm``, ``warm_x`` / ``warm_y`` shifted from ``x`` (B, N, Tm) / ``y`` (B, Mg, Tm)."""
-        f8 = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
-        i4 = lambda a: None if a is None else np.ascontiguousarray(a, np.int32)
-        lb, ub, off, ln, cap = f8(cur["lb"]), f8(cur["ub"]), i4(cur["s_off"]), i4(cur["s_len"]), f8(cur["s_cap"])
+        lb, ub, off, ln, cap = _f8(cur["lb"]), _f8(cur["ub"]), _i4(cur["s_off"]), _i4(cur["s_len"]), _f8(cur["s_cap"])
         if lb.ndim != 3 or lb.shape[1] != self.site.N or ub.shape != lb.shape or off.ndim != 3 or off.shape != ln.shape or off.shape != cap.shape:
             raise ValueError("cur needs lb, ub of shape (B, N, Tm) and s_off, s_len, s_cap of shape (B, K, N) for the handle's site")
         B, N, Tm = lb.shape
         K, Mg = off.shape[1], self.site.Mg
-        dfl = f8(cur.get("dfloor")) if self.site.has_max else None
-        app, stat, xs, ys = f8(applied), i4(status), f8(x) if want_warm else None, f8(y) if want_warm and Mg else None
+        dfl = _f8(cur.get("dfloor")) if self.site.has_max else None
+        app, stat, xs, ys = _f8(applied), _i4(status), _f8(x) if want_warm else None, _f8(y) if want_warm and Mg else None
         out = dict(horizon=np.empty(B, np.int32), lb=np.empty((B, N, Tm)), ub=np.empty((B, N, Tm)), q=np.empty((B, N, Tm)),
                    pdiag=np.empty(B), s_off=np.empty((B, K, N), np.int32), s_len=np.empty((B, K, N), np.int32), s_cap=np.empty((B, K, N)),
                    peak=np.empty((B, Tm)) if self.site.has_peak else None, lf=np.empty(B) if self.site.has_flat else None,
                    dc=np.empty(B) if self.site.has_max else None, dfloor=np.empty(B) if self.site.has_max else None,
                    warm_x=np.empty((B, N, Tm)) if xs is not None else None, warm_y=np.empty((B, Mg, Tm)) if ys is not None else None)
         flags = np.empty(B, np.int32)
-        p = _Problems(B, Tm, K, None, _ptr(lb), _ptr(ub), None, None, _ptr(off), _ptr(ln), _ptr(cap), None, None, None, None, _ptr(dfl), None, None)
+        p = _Problems(B, Tm, K, lb=_ptr(lb), ub=_ptr(ub), s_off=_ptr(off), s_len=_ptr(ln), s_cap=_ptr(cap), dfloor=_ptr(dfl))
         keep = []
         pl = plan._struct(N, Mg, step, seg_row, keep)
-        nx = _Next(*[_ptr(out[k]) for k in self._NEXT + ("warm_x", "warm_y")])
+        nx = _Next(*[_ptr(out[k]) for k in _NEXT_ARRAYS + _WARM])
         cost = plan._cost_struct(N, keep)
         if cost is not None and plan.c_series.shape[0] != B:
             raise ValueError(f"c_series has {plan.c_series.shape[0]} rows, the batch has {B} problems")
+        head = (self._h, C.byref(p), _ptr(app), _ptr(stat), _ptr(xs), _ptr(ys), C.byref(pl))
         if cost is None:
-            _check(self._lib.acnqp_advance_host(self._h, C.byref(p), _ptr(app), _ptr(stat), _ptr(xs), _ptr(ys), C.byref(pl), C.byref(nx),
-                                                _ptr(flags)), "acnqp_advance_host")
+            _check(self._lib.acnqp_advance_host(*head, C.byref(nx), _ptr(flags)), "acnqp_advance_host")
         else:
-            _check(self._lib.acnqp_advance_priced_host(self._h, C.byref(p), _ptr(app), _ptr(stat), _ptr(xs), _ptr(ys), C.byref(pl),
-                                                       C.byref(cost), C.byref(nx), _ptr(flags)), "acnqp_advance_priced_host")
+            _check(self._lib.acnqp_advance_priced_host(*head, C.byref(cost), C.byref(nx), _ptr(flags)), "acnqp_advance_priced_host")
         del keep
         out["flags"] = flags
         return {k: v for k, v in out.items() if v is not None}
@@ -950,14 +817,11 @@ class SiteHandle:
             raise ValueError("cur and nxt must have the same shape (B, N, Tm, K)")
         if warm_y is not None and cur.y is None:
             raise ValueError("warm_y needs the site-row multipliers: DeviceBatch(..., want_y=True)")
-        if tuple(applied.shape) != (cur.B, cur.N) or applied.element_size() != 8 or not applied.is_contiguous():
-            raise ValueError(f"applied must be a contiguous float64 tensor of shape {(cur.B, cur.N)}")
-        if tuple(flags.shape) != (cur.B,) or flags.element_size() != 4 or not flags.is_contiguous():
-            raise ValueError(f"flags must be a contiguous int32 tensor of shape {(cur.B,)}")
-        p = _Problems(cur.B, cur.Tm, cur.K, _dptr(cur.horizon), _dptr(cur.lb), _dptr(cur.ub), _dptr(cur.q), _dptr(cur.pdiag), _dptr(cur.s_off),
-                      _dptr(cur.s_len), _dptr(cur.s_cap), _dptr(cur.s_eq), _dptr(cur.peak), _dptr(cur.lf), _dptr(cur.dc), _dptr(cur.dfloor), None, None)
+        _want(applied, "applied", _F8, (cur.B, cur.N))
+        _want(flags, "flags", _I4, (cur.B,))
+        p = _device_problems(cur)
         pl = plan._struct(cur.N, self.site.Mg, step, seg_row)
-        nx = _Next(*[_dptr(getattr(nxt, k)) for k in self._NEXT], _dptr(warm_x), _dptr(warm_y))
+        nx = _Next(*[_dptr(getattr(nxt, k)) for k in _NEXT_ARRAYS], _dptr(warm_x), _dptr(warm_y))
         cost = plan._cost_struct(cur.N)
         if cost is not None and plan.c_series.shape[0] != cur.B:
             raise ValueError(f"c_series has {plan.c_series.shape[0]} rows, the batch has {cur.B} problems")
@@ -974,9 +838,8 @@ class SiteHandle:
         """acnqp_prepare_host: the state ``cur`` -- numpy arrays ``lb, ub`` (B, N, Tm) and ``s_off, s_len, s_cap`` (B, 1, N) or
         (B, N) -- under ``plan`` (numpy arrays).  Returns ``lb, ub`` (copies, period 0 changed when the plan has ``min_pilot``
         and ``min_rates``), ``flags`` (B,) and, with ``want_view``, ``v_evse, v_arrived, v_cap`` (B, N)."""
-        f8 = lambda a: np.array(a, np.float64, order="C")
-        i4 = lambda a: np.ascontiguousarray(a, np.int32)
-        lb, ub, off, ln, cap = f8(cur["lb"]), f8(cur["ub"]), i4(cur["s_off"]), i4(cur["s_len"]), np.ascontiguousarray(cur["s_cap"], np.float64)
+        lb, ub = np.array(cur["lb"], np.float64, order="C"), np.array(cur["ub"], np.float64, order="C")   # copies: the entry writes them
+        off, ln, cap = _i4(cur["s_off"]), _i4(cur["s_len"]), _f8(cur["s_cap"])
         if lb.ndim != 3 or lb.shape[1] != self.site.N or ub.shape != lb.shape:
             raise ValueError("cur needs lb, ub of shape (B, N, Tm) for the handle's site")
         B, N, Tm = lb.shape
@@ -985,7 +848,7 @@ class SiteHandle:
             raise ValueError("cur needs s_off, s_len, s_cap of shape (B, K, N)")
         view = dict(v_evse=np.empty((B, N), np.int32), v_arrived=np.empty((B, N), np.uint8), v_cap=np.empty((B, N))) if want_view else {}
         flags = np.empty(B, np.int32)
-        p = _Problems(B, Tm, K, None, None, None, None, None, _ptr(off), _ptr(ln), _ptr(cap), None, None, None, None, None, None, None)
+        p = _Problems(B, Tm, K, s_off=_ptr(off), s_len=_ptr(ln), s_cap=_ptr(cap))
         keep = []
         pl = plan._struct(N, key_row, min_rates, keep)
         v = _PrepareView(*[_ptr(view.get(k)) for k in ("v_evse", "v_arrived", "v_cap")])
@@ -1002,37 +865,23 @@ class SiteHandle:
         import torch
 
         here = torch.device("cuda", self.device)
-
-        def want(t, name, dtype, shape):
-            if t is None:
-                return
-            if not isinstance(t, torch.Tensor) or t.device != here or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-                raise ValueError(f"{name} must be a contiguous {dtype} tensor on {here} of shape {tuple(shape)}")
-
-        B, N, Tm = cur.B, cur.N, cur.Tm
-        M = 0 if plan.cre is None else int(plan.cre.shape[0])
+        B, N, Tm, K = cur.B, cur.N, cur.Tm, cur.K
+        M = plan._len("cre")
         if plan.key is None or not hasattr(plan.key, "dim"):
             raise ValueError("plan.key must be a tensor on the handle's GPU (PreparePlan.to_device)")
-        want(plan.key, "plan.key", torch.int32, (B, N) if plan.key.dim() == 2 else (plan.key.shape[0], B, N))
+        _want(plan.key, "plan.key", _I4, (B, N) if plan.key.dim() == 2 else (plan.key.shape[0], B, N), here)
         if plan.key.dim() == 3 and not 0 <= (0 if key_row is None else int(key_row)) < plan.key.shape[0]:
             raise ValueError("key_row is outside plan.key")
-        want(plan.cre, "plan.cre", torch.float64, (M, N))
-        want(plan.cim, "plan.cim", torch.float64, (M, N))
-        want(plan.limits, "plan.limits", torch.float64, (M,))
-        want(plan.min_pilot, "plan.min_pilot", torch.float64, (N,))
-        want(cur.lb, "cur.lb", torch.float64, (B, N, Tm))
-        want(cur.ub, "cur.ub", torch.float64, (B, N, Tm))
-        want(cur.s_off, "cur.s_off", torch.int32, (B, cur.K, N))
-        want(cur.s_len, "cur.s_len", torch.int32, (B, cur.K, N))
-        want(cur.s_cap, "cur.s_cap", torch.float64, (B, cur.K, N))
-        want(flags, "flags", torch.int32, (B,))
+        for k, shape in dict(cre=(M, N), cim=(M, N), limits=(M,), min_pilot=(N,)).items():
+            _want(getattr(plan, k), "plan." + k, _PREPARE_ARRAYS[k], shape, here)
+        for k, shape in dict(lb=(B, N, Tm), ub=(B, N, Tm), s_off=(B, K, N), s_len=(B, K, N), s_cap=(B, K, N)).items():
+            _want(getattr(cur, k), "cur." + k, _PROBLEM_ARRAYS[k], shape, here)
+        _want(flags, "flags", _I4, (B,), here)
         if flags is None:
             raise ValueError("flags is required")
-        want(v_evse, "v_evse", torch.int32, (B, N))
-        want(v_arrived, "v_arrived", torch.uint8, (B, N))
-        want(v_cap, "v_cap", torch.float64, (B, N))
-        p = _Problems(B, Tm, cur.K, None, None, None, None, None, _dptr(cur.s_off), _dptr(cur.s_len), _dptr(cur.s_cap), None, None, None, None,
-                      None, None, None)
+        for t, name, dt in ((v_evse, "v_evse", _I4), (v_arrived, "v_arrived", _U1), (v_cap, "v_cap", _F8)):
+            _want(t, name, dt, (B, N), here)
+        p = _Problems(B, Tm, K, s_off=_dptr(cur.s_off), s_len=_dptr(cur.s_len), s_cap=_dptr(cur.s_cap))
         pl = plan._struct(N, key_row, min_rates)
         v = _PrepareView(_dptr(v_evse), _dptr(v_arrived), _dptr(v_cap))
         _check(self._lib.acnqp_prepare_device(self._h, C.byref(p), C.byref(pl), _dptr(cur.lb), _dptr(cur.ub), C.byref(v), _dptr(flags),
@@ -1061,9 +910,7 @@ class SiteHandle:
     def polish_alongside(self) -> int:
         """Problems that polish launches running ALONGSIDE a solver launch have taken since the previous call
         (acnqp_debug_polish_alongside: introspection, not part of the ABI; synchronises)."""
-        fn = self._lib.acnqp_debug_polish_alongside
-        fn.restype, fn.argtypes = C.c_int64, [C.c_void_p]
-        n = int(fn(self._h))
+        n = int(self._lib.acnqp_debug_polish_alongside(self._h))
         if n < 0:
             raise RuntimeError("acnqp_debug_polish_alongside failed")
         return n
@@ -1072,9 +919,7 @@ class SiteHandle:
         """The site's live eigenpairs, the MFMA k-steps that hold them once compacted, and the eigen extent (k-steps) of
         the wave kernel's instantiation this handle runs (acnqp_debug_wave_rank: introspection, not part of the ABI)."""
         buf = (C.c_int32 * 3)()
-        fn = self._lib.acnqp_debug_wave_rank
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
-        if fn(self._h, buf) != 0:
+        if self._lib.acnqp_debug_wave_rank(self._h, buf) != 0:
             raise RuntimeError("acnqp_debug_wave_rank failed")
         return dict(rank=int(buf[0]), eig_ksteps=int(buf[1]), extent=int(buf[2]))
 
@@ -1082,9 +927,7 @@ class SiteHandle:
         """The site's EVSEs, the MFMA k-steps of P = Ghat r0 that hold one, and the EVSE k-steps the wave kernel's
         instantiation this handle runs sums over (acnqp_debug_wave_evse_extent: introspection, not part of the ABI)."""
         buf = (C.c_int32 * 3)()
-        fn = self._lib.acnqp_debug_wave_evse_extent
-        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]
-        if fn(self._h, buf) != 0:
+        if self._lib.acnqp_debug_wave_evse_extent(self._h, buf) != 0:
             raise RuntimeError("acnqp_debug_wave_evse_extent failed")
         return dict(n_evse=int(buf[0]), evse_ksteps=int(buf[1]), extent=int(buf[2]))
 
@@ -1126,28 +969,21 @@ class DeviceBatch:
 
         dev = torch.device(device)
         self.B, self.N, self.Tm, self.K = batch.B, batch.N, batch.Tm, batch.K
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
-        self.horizon = t(batch.T, np.int32)
-        self.lb = t(batch.lb, np.float64)
-        self.ub = t(batch.ub, np.float64)
-        self.q = t(batch.q, np.float64)
-        self.pdiag = t(batch.pdiag, np.float64)
-        self.s_off = t(batch.s_off, np.int32)
-        self.s_len = t(batch.s_len, np.int32)
-        self.s_cap = t(batch.s_cap, np.float64)
-        self.s_eq = t(batch.s_eq, np.uint8)
-        self.peak = None if batch.peak is None else t(batch.peak, np.float64)
-        self.lf = t(batch.lf, np.float64)
-        self.dc = t(batch.dc if batch.dc is not None else np.zeros(batch.B), np.float64)
-        self.dfloor = t(batch.dfloor if batch.dfloor is not None else np.zeros(batch.B), np.float64)
-        self.x = torch.zeros((self.B, self.N, self.Tm), dtype=torch.float64, device=dev)
-        self.status = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self.iters = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self.pri_res = torch.zeros(self.B, dtype=torch.float64, device=dev)
-        self.dua_res = torch.zeros(self.B, dtype=torch.float64, device=dev)
-        self.obj = torch.zeros(self.B, dtype=torch.float64, device=dev)
-        # site-row multipliers (B, Mg, Tm) when wanted (acnqp_results.y), else None
-        self.y = torch.zeros((self.B, batch.site.Mg, self.Tm), dtype=torch.float64, device=dev) if want_y else None
+        for k, dt in _PROBLEM_ARRAYS.items():
+            a = getattr(batch, "T" if k == "horizon" else k)
+            if a is None and k in ("lf", "dc", "dfloor"):   # a batch without the term: the tensor is there all the same
+                a = np.zeros(batch.B)
+            setattr(self, k, None if a is None else torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev))
+        self._alloc_results(batch.site.Mg, want_y, dev)
+
+    def _alloc_results(self, Mg: int, want_y: bool, dev) -> None:
+        """zeroed result tensors: those of ``_RESULT_ARRAYS`` and, when wanted, the site-row multipliers y (B, Mg, Tm)
+        (acnqp_results.y), else None"""
+        import torch
+
+        for k, dt in _RESULT_ARRAYS.items():
+            setattr(self, k, torch.zeros((self.B, self.N, self.Tm) if k == "x" else self.B, dtype=_torch_dtype(dt), device=dev))
+        self.y = torch.zeros((self.B, Mg, self.Tm), dtype=torch.float64, device=dev) if want_y else None
 
     @classmethod
     def empty(cls, site: SiteData, B: int, Tm: int, K: int, device, want_y: bool = False, s_eq: int = 0, dfloor: float = 0.0,
@@ -1159,17 +995,12 @@ class DeviceBatch:
         dev = torch.device(device)
         self = cls.__new__(cls)
         self.B, self.N, self.Tm, self.K = int(B), site.N, int(Tm), int(K)
-        z = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)
-        self.horizon = torch.ones(self.B, dtype=torch.int32, device=dev)
-        self.lb, self.ub, self.q = z((self.B, self.N, self.Tm)), z((self.B, self.N, self.Tm)), z((self.B, self.N, self.Tm))
-        self.pdiag, self.lf, self.dc = z(self.B), z(self.B), z(self.B)
-        self.dfloor = torch.full((self.B,), float(dfloor), dtype=torch.float64, device=dev)
-        self.s_off, self.s_len = z((self.B, self.K, self.N), torch.int32), z((self.B, self.K, self.N), torch.int32)
-        self.s_cap = z((self.B, self.K, self.N))
-        self.s_eq = torch.full((self.B,), int(s_eq), dtype=torch.uint8, device=dev)
-        self.peak = torch.full((self.B, self.Tm), float("inf"), dtype=torch.float64, device=dev) if (site.has_peak if with_peak is None else with_peak) else None
-        self.x = z((self.B, self.N, self.Tm))
-        self.status, self.iters = z(self.B, torch.int32), z(self.B, torch.int32)
-        self.pri_res, self.dua_res, self.obj = z(self.B), z(self.B), z(self.B)
-        self.y = z((self.B, site.Mg, self.Tm)) if want_y else None
+        shapes = dict(lb=(self.B, self.N, self.Tm), ub=(self.B, self.N, self.Tm), q=(self.B, self.N, self.Tm), s_off=(self.B, self.K, self.N),
+                      s_len=(self.B, self.K, self.N), s_cap=(self.B, self.K, self.N), peak=(self.B, self.Tm))
+        fill = dict(horizon=1, dfloor=float(dfloor), s_eq=int(s_eq), peak=float("inf"))
+        no_peak = not (site.has_peak if with_peak is None else with_peak)
+        for k, dt in _PROBLEM_ARRAYS.items():
+            setattr(self, k, None if k == "peak" and no_peak else
+                    torch.full(shapes.get(k, (self.B,)), fill.get(k, 0), dtype=_torch_dtype(dt), device=dev))
+        self._alloc_results(site.Mg, want_y, dev)
         return self

@@ -3,6 +3,7 @@ rejects misuse with return codes -- no compute calls (no GPU here)."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -36,19 +37,68 @@ def test_abi_v10_version_and_defaults(hip_library):
     o2 = backend.default_options(eps_abs=1e-9, max_iter=5)
     assert o2.eps_abs == 1e-9 and o2.max_iter == 5
     assert backend.default_options(polish_stall=100).polish_stall == 100      # ABI v9: the last field of the structure
-    # the header's own layout (compiled here with gcc): the new field sits behind inaccurate_floor, where the binding has it
-    import subprocess, tempfile
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, "o.c")
-        with open(src, "w") as f:
-            f.write('#include <stdio.h>\n#include <stddef.h>\n#include "acn_qp.h"\nint main(){printf("%zu %zu %zu", sizeof(acnqp_options), '
-                    'offsetof(acnqp_options, polish_stall), offsetof(acnqp_options, inaccurate_floor));return 0;}')
-        exe = os.path.join(tmp, "o")
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-        size, off_stall, off_floor = map(int, subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split())
-    assert size == C.sizeof(backend.Options) and off_stall == backend.Options.polish_stall.offset and off_floor == backend.Options.inaccurate_floor.offset
+    # (the header's own layout, polish_stall behind inaccurate_floor included: test_every_struct_and_constant_matches_the_header)
     with pytest.raises(TypeError):
         backend.default_options(nonsense=1)
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "acn_qp.h")).read(), flags=re.S)
+
+
+STRUCTS = {
+    "acnqp_site": backend._Site, "acnqp_problems": backend._Problems, "acnqp_results": backend._Results, "acnqp_options": backend.Options,
+    "acnqp_table": backend._Table, "acnqp_duals": backend._Duals, "acnqp_pilot_plan": backend._PilotPlan, "acnqp_pilots": backend._Pilots,
+    "acnqp_advance_plan": backend._AdvancePlan, "acnqp_next": backend._Next, "acnqp_clock_cost": backend.ClockCost,
+    "acnqp_prepare_plan": backend._PreparePlan, "acnqp_prepare_view": backend._PrepareView,
+}
+
+
+def test_every_struct_and_constant_matches_the_header(tmp_path):
+    """The header, laid out by gcc, against the binding: size of every struct, offset and size of every field, the value of
+    every constant.  The program is generated from the binding's own ``_fields_``, so a field the header does not have
+    fails the compile; a struct the header has and ``STRUCTS`` lacks fails the count."""
+    text = _header()
+    assert sorted(re.findall(r"typedef\s+struct\s*\{[^}]*\}\s*(acnqp_\w+)\s*;", text)) == sorted(STRUCTS)
+    consts = re.findall(r"#define\s+(ACNQP_(?:(?:STATUS|ROUTE|PILOTS|ADVANCE)_\w+|PREPARE_FUTURE|ABI_VERSION))\b", text)
+    lines = []
+    for name, cls in STRUCTS.items():
+        lines.append(f'printf("%zu\\n", sizeof({name}));')
+        lines += [f'printf("%zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, _ in cls._fields_]
+    lines += [f'printf("%d\\n", {c});' for c in consts]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "acn_qp.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0;\n}\n")
+    cc = subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    got = iter(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n"))
+    checked = 0
+    for name, cls in STRUCTS.items():
+        assert int(next(got)) == C.sizeof(cls), name
+        for f, ctype in cls._fields_:
+            assert next(got).split() == [str(getattr(cls, f).offset), str(C.sizeof(ctype))], (name, f)
+            checked += 1
+    assert checked == sum(len(cls._fields_) for cls in STRUCTS.values()) >= 150
+    assert C.sizeof(backend.Options) == 120 and backend.Options.polish_stall.offset == backend.Options.inaccurate_floor.offset + 8 == 112
+    value ={c: int(next(got)) for c in consts}
+    assert value.pop("ACNQP_ABI_VERSION") == 10
+    assert {v: c[len("ACNQP_ROUTE_"):].lower() for c, v in value.items() if c.startswith("ACNQP_ROUTE_")} == backend.ROUTE_NAMES
+    rest = {c[len("ACNQP_"):]: v for c, v in value.items() if not c.startswith("ACNQP_ROUTE_")}
+    assert len(rest) == 6 + 3 + 3 + 1   # statuses, pilot modes, advance flags, the prepare flag
+    assert rest == {k: getattr(backend, k) for k in rest}
+
+
+def test_every_entry_has_its_prototype(hip_library):
+    """After ``load_library`` every declared entry has the header's parameter count in ``argtypes``, and the introspection
+    entries have theirs without any method having set it."""
+    decl = dict(re.findall(r"\b(acnqp_[a-z_]+)\s*\(([^()]*)\)\s*;", _header()))
+    assert set(decl) == set(backend.EXPORTED_SYMBOLS) == set(declared_symbols())
+    for name, params in decl.items():
+        n = 0 if params.strip() in ("", "void") else len(params.split(","))
+        assert getattr(hip_library, name).argtypes is not None and len(getattr(hip_library, name).argtypes) == n, name
+    for name, n in (("acnqp_debug_polish_alongside", 1), ("acnqp_debug_wave_rank", 2), ("acnqp_debug_wave_evse_extent", 2)):
+        assert name not in backend.EXPORTED_SYMBOLS and len(getattr(hip_library, name).argtypes) == n, name
+    assert hip_library.acnqp_debug_polish_alongside.restype is C.c_int64 and hip_library.acnqp_launch_count.restype is C.c_int64
+    assert hip_library.acnqp_host_alloc.restype is C.c_void_p and hip_library.acnqp_last_error.restype is C.c_char_p
 
 
 def test_create_rejects_bad_arguments(hip_library):

@@ -1,17 +1,13 @@
 """tests/pilots_spec.py -- the contract of the pilot-signal kernel -- equals the host post-processing
 (postprocessing.project_into_*_batch, diff_based_reallocation_batch) exactly where no decision sits on a rounding, and
-the C header, the binding and the symbol list agree about the new entries.  No GPU."""
+the library exports the new entries (their layout against the C header: tests/test_abi.py).  No GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from adacharge_amd import backend, postprocessing as pp
 from tests import pilots_cases as cases, pilots_spec as spec
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _spec_all(infra, iface, table, rates):
@@ -84,23 +80,6 @@ def test_endless_input_stops_at_the_bound():
     assert len(counted) == plan.N * plan.levels.shape[1]
     _, v2, _ = spec.reallocate(rates, plan.levels, plan.cre, plan.cim, plan.limits, plan.sess_seg, plan.s_evse, plan.s_arrived, np.array([32.0]))
     assert v2[0] == 1
-
-
-def test_header_binding_and_symbols_agree(tmp_path):
-    assert {"acnqp_pilots_device", "acnqp_pilots_host"} <= set(backend.EXPORTED_SYMBOLS)
-    P, O = backend._PilotPlan, backend._Pilots
-    fields = [f for f, _ in P._fields_]
-    src = tmp_path / "p.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "acn_qp.h"\nint main(){printf("%zu %zu %d %d %d %d ", sizeof(acnqp_pilot_plan), '
-                   'sizeof(acnqp_pilots), ACNQP_PILOTS_CONTINUOUS, ACNQP_PILOTS_DISCRETE, ACNQP_PILOTS_REALLOCATE, ACNQP_ABI_VERSION);'
-                   + "".join(f'printf("%zu ", offsetof(acnqp_pilot_plan, {f}));' for f in fields)
-                   + 'printf("%zu %zu %zu", offsetof(acnqp_pilots, pilots), offsetof(acnqp_pilots, first), offsetof(acnqp_pilots, visits));return 0;}')
-    exe = tmp_path / "p"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()))
-    assert got[:6] == [C.sizeof(P), C.sizeof(O), backend.PILOTS_CONTINUOUS, backend.PILOTS_DISCRETE, backend.PILOTS_REALLOCATE, 10]
-    assert got[6:6 + len(fields)] == [getattr(P, f).offset for f in fields]
-    assert got[6 + len(fields):] == [O.pilots.offset, O.first.offset, O.visits.offset]
 
 
 def test_library_exports_the_entries_and_refuses_a_null_handle(hip_library):

@@ -31,9 +31,7 @@ obj = [ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-12)]
 snaps = sites.snapshot_batch(infra, T, nb, seed=100 + T, demand_range=(5.0, 60.0))
 batch = build_batch(snaps + snaps, infra, iface, obj, "SOC")
 B = batch.B
-lib = load_library()
-lib.acnqp_debug_copy_workspace.restype = C.c_int64
-lib.acnqp_debug_copy_workspace.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+lib = load_library()   # gives acnqp_debug_copy_workspace its prototype when the build has it
 NP = 64
 CTL = {96: 6, 144: 9}.get(T, (T + 15) // 16)
 NE = NP // 16

@@ -19,8 +19,8 @@ def med(f, n=40):
     return 1e3 * float(np.median(t))
 print("solve(pinned_results=True)  %.2f ms" % med(lambda: h.solve(batch, o, pinned_results=True)))
 print("solve(pinned_results=False) %.2f ms" % med(lambda: h.solve(batch, o, pinned_results=False)))
-print("_marshal(pinned) alone      %.2f ms" % med(lambda: h._marshal(batch, True)))
-print("_marshal(plain) alone       %.2f ms" % med(lambda: h._marshal(batch, False)))
+print("_marshal(pinned) alone      %.3f ms" % med(lambda: h._marshal(batch, True)))
+print("_marshal(plain) alone       %.3f ms" % med(lambda: h._marshal(batch, False)))
 p, r, res, keep = h._marshal(batch, True)
 print("C call alone (pinned results, marshalled once) %.2f ms" % med(lambda: _check(h._lib.acnqp_solve_batch(h._h, C.byref(p), C.byref(o), C.byref(r)), "x")))
 print("kernel %.2f ms" % h.last_kernel_ms())
