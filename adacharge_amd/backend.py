@@ -184,6 +184,7 @@ def _abi():
         ("acnqp_debug_polish_alongside", i64, [h]),
         ("acnqp_debug_wave_rank", rc, [h, P(i32)]),
         ("acnqp_debug_wave_evse_extent", rc, [h, P(i32)]),
+        ("acnqp_debug_order_keys", rc, [h, P(_Problems), P(i32)]),
         ("acnqp_debug_copy_workspace", i64, [h, ptr, i64]),   # builds with -DACNQP_DEBUG_WS only (tools/gpu_long_race.py)
     ]
     return tuple(r + (True,) for r in rows) + tuple(r + (False,) for r in introspection)
@@ -931,8 +932,17 @@ class SiteHandle:
             raise RuntimeError("acnqp_debug_wave_evse_extent failed")
         return dict(n_evse=int(buf[0]), evse_ksteps=int(buf[1]), extent=int(buf[2]))
 
+    def order_keys(self, dev: "DeviceBatch") -> np.ndarray:
+        """The launch-order keys (B,) int32 of a ``DeviceBatch`` of any size: what a launch of 768 problems or more is
+        sorted by, largest first (acnqp_debug_order_keys: introspection, not part of the ABI; synchronises)."""
+        keys = np.empty(dev.B, np.int32)
+        p = _device_problems(dev)
+        if self._lib.acnqp_debug_order_keys(self._h, C.byref(p), keys.ctypes.data_as(C.POINTER(C.c_int32))) != 0:
+            raise RuntimeError("acnqp_debug_order_keys failed")
+        return keys
+
     def ordered_launches(self) -> int:
-        """Launches of this handle whose queue order was sorted by session count (acnqp_ordered_launch_count)."""
+        """Launches of this handle whose queue order was sorted by a key (acnqp_ordered_launch_count)."""
         return int(self._lib.acnqp_ordered_launch_count(self._h))
 
     def last_kernel_ms(self) -> float:

@@ -87,7 +87,7 @@ struct acnqp_handle {
   static constexpr int kEvRing = 64;               // event pairs of the most recent launches
   hipEvent_t ev_start[kEvRing] = {}, ev_stop[kEvRing] = {};
   long long launches = 0, reported = 0;           // launches recorded / already handed out by acnqp_kernel_times
-  long long ordered_launches = 0;                 // launches whose queue order was sorted by session count (acnqp_ordered_launch_count)
+  long long ordered_launches = 0;                 // launches whose queue order was sorted by launch_order_keys' key (acnqp_ordered_launch_count)
   // host-buffer entry points: kSlots pipeline slots, each with its own stream and device staging, so that the
   // H2D copies, the kernel and the D2H copies of successive chunks of a call overlap
   static constexpr int kSlots = 4;
@@ -441,13 +441,42 @@ acnqp::TiledArgs tiled_args(const acnqp_handle* h, const acnqp_problems* p, cons
 // across the whole chip: a slot that ends early leaves its bandwidth to the others, and the static schedule measured
 // the same or better (configs[4] leg 432 vs 434-438 ms, 54 x 144 x 2,048 237-243 vs 247-248 ms; gpurun_out/r4c):
 // they keep one workgroup per problem.
+// The launch-order keys of the device-resident problems p (which route rt serves) into keys[p->batch], on st: the
+// congestion key of order_keys_kernel, or the session count.  The session count is the key
+//  * of a shape beyond that kernel's LDS budget (order_key_waves),
+//  * of the four-wave route (two row tiles x horizon 13-24), the one ordered leg that measured a LOSS under the
+//    congestion key (jpl52 x 24 x 4,096, five runs each: 43.52-43.69 ms by sessions, 43.77-43.99 ms by congestion;
+//    profiles/order_key_ab.json),
+//  * under ACNQP_ORDER_KEY=sessions (diagnostic, read once per process; `overload` names the default).
+// By shape and route, never by batch.
+hipError_t launch_order_keys(acnqp_handle* h, const acnqp::Route& rt, const acnqp_problems* p, hipStream_t st, int32_t* keys) {
+  static const bool by_sessions = [] { const char* e = std::getenv("ACNQP_ORDER_KEY"); return e && std::strcmp(e, "sessions") == 0; }();
+  const acnqp::SiteShape& s = h->shape;
+  const int g_rows = s.cone == ACNQP_CONE_SOC ? 2 * s.M : s.M;
+  const int waves = by_sessions || rt.family == ACNQP_ROUTE_WAVE4 ? 0 : order_key_waves((size_t)s.N, (size_t)p->t_max, (size_t)g_rows);
+  if (waves == 0) {
+    hipLaunchKernelGGL(session_keys_kernel, dim3((p->batch + 3) / 4), dim3(256), 0, st, p->s_len, p->k_sessions * s.N, p->batch, keys);
+    return hipGetLastError();
+  }
+  OrderKeyArgs ka;
+  ka.B = p->batch; ka.N = s.N; ka.Tm = p->t_max; ka.K = p->k_sessions; ka.M = s.M; ka.soc = s.cone == ACNQP_CONE_SOC; ka.has_peak = s.has_peak;
+  ka.lb = p->lb; ka.ub = p->ub; ka.s_cap = p->s_cap; ka.peak = p->peak; ka.G = h->site.Gabi; ka.limits = h->site.limabi;
+  ka.s_off = p->s_off; ka.s_len = p->s_len; ka.horizon = p->horizon; ka.keys = keys;
+  const size_t lds = ((size_t)g_rows * s.N + (size_t)waves * s.N * p->t_max) * sizeof(double);
+  const hipError_t e = acnqp::ensure_dynamic_lds(reinterpret_cast<const void*>(order_keys_kernel), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(order_keys_kernel, dim3((p->batch + waves - 1) / waves), dim3(64 * waves), lds, st, ka);
+  return hipGetLastError();
+}
+
 int schedule_launch(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route& rt, const acnqp_problems* p, hipStream_t st, acnqp::TiledArgs* a) {
   static const bool no_order = std::getenv("ACNQP_NO_ORDER") != nullptr;   // diagnostic: queue position b = problem b
   static const bool no_queue_env = std::getenv("ACNQP_NO_QUEUE") != nullptr;   // diagnostic: the static schedule (workgroup w = position w)
   static const bool queue_all = std::getenv("ACNQP_QUEUE_ALL") != nullptr;     // diagnostic: the queue for the streaming kernels too
   const bool no_queue = no_queue_env || !(rt.on_chip || queue_all);
-  // (the order by sessions only for separable objectives: with a load-flattening or demand-charge row the coupling, not
-  //  the number of sessions, sets the iteration count -- on the configs[4] leg it was 10 % SLOWER than the natural one)
+  // (an order only for separable objectives: with a load-flattening or demand-charge row the coupling, which neither the
+  //  session count nor the overloaded cells of the greedy schedule see, sets the iteration count -- by sessions the
+  //  configs[4] leg was 10 % SLOWER than in the natural order)
   const bool want_order = p->batch >= kOrderMinBatch && !no_order && !h->shape.has_flat && !h->shape.has_max;
   if (!no_queue || want_order) {
     // scheduling buffer of this stream: [0] the queue counter (its own 256-byte line), then keys[B], order[B]
@@ -461,7 +490,7 @@ int schedule_launch(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route&
     if (want_order) {
       int32_t* keys = static_cast<int32_t*>(wk->ord.p) + 64;
       int32_t* order = keys + p->batch;
-      hipLaunchKernelGGL(order_keys_kernel, dim3((p->batch + 3) / 4), dim3(256), 0, st, p->s_len, p->k_sessions * h->shape.N, p->batch, keys);
+      HIP_TRY(launch_order_keys(h, rt, p, st, keys));
       hipLaunchKernelGGL(order_sort_kernel, dim3(1), dim3(kOrderKeys), 0, st, keys, p->batch, order);
       a->order = order;
       h->ordered_launches++;
@@ -724,6 +753,22 @@ extern "C" int acnqp_debug_wave_rank(acnqp_handle* h, int32_t* out) {
   const int ext = wave_extent_of(h);
   out[0] = h->site.rank; out[1] = h->site.eig_ksteps; out[2] = ext > 0 ? ext : h->shape.MR / 4;
   return 0;
+}
+
+// Introspection outside include/acn_qp.h (every build): the launch-order keys (launch_order_keys: what a launch of at
+// least kOrderMinBatch problems is sorted by) of the DEVICE-resident problems p, of any batch size, copied to the host
+// array keys_out[p->batch].  Synchronises.  Returns 0, -1 on a null argument or a HIP error.
+extern "C" int acnqp_debug_order_keys(acnqp_handle* h, const acnqp_problems* p, int32_t* keys_out) {
+  if (!h || !p || !keys_out || p->batch < 0 || p->t_max < 1 || p->k_sessions < 1) return -1;
+  if (p->batch == 0) return 0;
+  if (!p->lb || !p->ub || !p->s_off || !p->s_len || !p->s_cap || !p->horizon) return -1;
+  if (hipSetDevice(h->device) != hipSuccess) return -1;
+  int32_t* keys = nullptr;
+  if (hipMalloc((void**)&keys, (size_t)p->batch * sizeof(int32_t)) != hipSuccess) return -1;
+  hipError_t e = launch_order_keys(h, route_of(h, p->t_max, p->k_sessions, p->batch), p, nullptr, keys);
+  if (e == hipSuccess) e = hipMemcpy(keys_out, keys, (size_t)p->batch * sizeof(int32_t), hipMemcpyDeviceToHost);
+  (void)hipFree(keys);
+  return e == hipSuccess ? 0 : -1;
 }
 
 // Introspection outside include/acn_qp.h (every build): out[0] = the site's EVSEs, out[1] = the MFMA k-steps of P = Ghat r0

@@ -122,25 +122,38 @@ using acnqp::ChunkLayout;
 // ---- launch order: longest expected problem first -------------------------------------------------------------------
 // A launch of B problems on S resident workgroup slots ends with its slowest slot; the hardware hands workgroups out in
 // index order, so the tail is up to one whole problem long (bench workload, 32 problems per slot: natural order 7.0 %
-// above the mean slot, `longest first` by the TRUE iteration counts 0.2 %).  The number of sessions of a problem
-// predicts its iteration count well enough (rank correlation 0.81 on that workload: the list schedule by it ends 1.8 %
-// above the mean): two tiny kernels sort the problems by it, descending, and every solver kernel maps workgroup ->
+// above the mean slot, `longest first` by the TRUE iteration counts 0.2 %).  Two tiny kernels give every problem a key
+// that predicts its iteration count and sort the problems by it, descending; every solver kernel maps workgroup ->
 // problem through the result.  Results do not depend on the order (a workgroup only touches its own problem).
 //
-// That 1.8 % was measured at 32 problems per slot on 64 slots.  The wave kernel's headline launch has 16 problems per
-// slot on 1,024 wave slots, and there no key levels the tail.  A SIMULATION (tools/sim_launch_tail.py: the CPU twin's
-// iteration counts of the bench's 16,384 problems, capped at the polish hand-over, list-scheduled on 1,024 wave slots at
-// 3.67 us per iteration; nothing of it measured on a GPU): the work spread evenly 11.4 ms; one launch in session order
-// 13.6 ms (+19 %), by sum of s_len / sum of ub 13.0, by deliverable energy 13.5, natural order 13.2, a second seed set
-// 13.4-13.8; the chunk plan 2,048 / 4,096 / 8,192 / 2,048 with four-wave workgroups 14.2 ms for each of the four sorted
-// keys (second seed set 14.8-14.9), natural order 14.8 (15.3).  Only the TRUE iteration counts as the key reach the even
-// spread (11.45 ms lone, 12.9 pipelined), and no key known before the solve predicts them: a handful of problems with
-// few sessions run 400 ... 808 iterations (22 of the last 6,384 in session order), a serial chain that starts late ends
-// late whatever the order, and a CU passes to the next launch only when the slowest of its four waves is done.  What is
-// left as a lever is the latency of one wave-iteration.
+// Which key.  Measures of DEMAND (sessions, sum of s_len, sum of ub, deliverable energy) do not level the wave kernel's
+// headline launch (16 problems per slot on 1,024 wave slots): a handful of problems with few sessions run 400 ... 808
+// iterations, start late under such a key and end late.  What sets the iteration count is CONGESTION: how much of the
+// schedule that ignores the site rows the site rows reject.  The key is computed from the GREEDY schedule x0 (every
+// session charges at its upper bound from its first period until its energy cap is used up): C = the (site row, period)
+// cells whose load under x0 exceeds the limit, key = 8 min(C, 127) + min(7, sessions / 8).  A problem with C = 0
+// converges at the first residual check (20 iterations; exactly so on the 49,152 problems of three bench seed sets, 36 %
+// of them), so every queue ends with fine-grained work.  tests/order_key_spec.py is the definition in numpy,
+// tools/sim_launch_tail.py the SIMULATION that chose the key on the CPU twin's iteration counts (wave-iterations, mean of
+// three seed sets, lone launch / chunk plan: even spread 3,113; sessions 3,656 / 3,936; this key 3,436 / 3,816; the
+// true iteration counts 3,120 / 3,515; profiles/order_key_sim.json), DESIGN.md section 3.7 what it measured.
+// ACNQP_ORDER_KEY=sessions / overload (diagnostic, read once per process) selects the key in the same binary.
 constexpr int kOrderKeys = 1024;
 constexpr int kOrderMinBatch = 768;   // fewer problems than ~1.5 x the resident slots: nothing to level
-__global__ __launch_bounds__(256) void order_keys_kernel(const int32_t* s_len, int KN, int B, int32_t* keys) {
+// LDS budget of order_keys_kernel: the greedy schedule of ONE problem (N x Tm doubles) may take 64 KB (54 x 144 fits), and
+// a workgroup -- the site's infrastructure rows of G, then the schedules of its waves -- the CU's 160 KB.  A shape beyond
+// either gets the session-count key; a shape whose four schedules do not fit one workgroup gets fewer waves per workgroup.
+// Decided by shape (order_key_waves), never by batch.
+constexpr size_t kOrderLdsPerProblem = (size_t)64 << 10;
+constexpr size_t kOrderLdsPerGroup = (size_t)160 << 10;
+inline int order_key_waves(size_t N, size_t Tm, size_t g_rows) {   // waves (= problems) per workgroup; 0: session-count key
+  const size_t sched = N * Tm * sizeof(double), g = g_rows * N * sizeof(double);
+  if (sched == 0 || sched > kOrderLdsPerProblem || g + sched > kOrderLdsPerGroup) return 0;
+  return (int)std::min<size_t>(4, (kOrderLdsPerGroup - g) / sched);
+}
+
+// the session-count key: ACNQP_ORDER_KEY=sessions, and every shape beyond the LDS budget of order_keys_kernel
+__global__ __launch_bounds__(256) void session_keys_kernel(const int32_t* s_len, int KN, int B, int32_t* keys) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + wave;
   if (b >= B) return;
@@ -148,6 +161,75 @@ __global__ __launch_bounds__(256) void order_keys_kernel(const int32_t* s_len, i
   for (int k = lane; k < KN; k += 64) c += s_len[(size_t)b * KN + k] > 0 ? 1 : 0;
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
   if (lane == 0) keys[b] = c < kOrderKeys ? c : kOrderKeys - 1;
+}
+
+struct OrderKeyArgs {
+  int B, N, Tm, K, M, soc, has_peak;   // M infrastructure constraints: G rows [0, M) and, for SOC, their partners [M, 2M)
+  const double *lb, *ub, *s_cap, *peak, *G, *limits;   // G, limits: acnqp_site's, in the caller's row order and units
+  const int32_t *s_off, *s_len, *horizon;
+  int32_t* keys;
+};
+
+// The congestion key (above; tests/order_key_spec.py).  One wave per problem, blockDim.x / 64 problems per workgroup.
+// LDS: the infrastructure rows of G (staged once per workgroup), then one schedule x0[N][Tm] per wave.  Phase 1, a lane
+// per (session slot, EVSE): the greedy schedule over the slot's window (windows of one EVSE are disjoint: no two lanes
+// write one entry).  Phase 2, a lane per (row, period) cell: the row's load under x0 against its limit.
+__global__ __launch_bounds__(256) void order_keys_kernel(const OrderKeyArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char order_lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int N = a.N, Tm = a.Tm, M = a.M;
+  const int g_rows = a.soc ? 2 * M : M;
+  double* Gs = reinterpret_cast<double*>(order_lds);
+  double* x0 = Gs + (size_t)g_rows * N + (size_t)wave * N * Tm;
+  const int b = blockIdx.x * (int)(blockDim.x >> 6) + wave;
+  const bool live = b < a.B;   // (a wave without a problem still takes part in the barriers)
+  for (int k = threadIdx.x; k < g_rows * N; k += blockDim.x) Gs[k] = a.G[k];
+  if (live)
+    for (int k = lane; k < N * Tm; k += 64) x0[k] = 0.0;
+  __syncthreads();
+  int sessions = 0;
+  if (live) {
+    const int hz = min(a.horizon[b], Tm);
+    const size_t sb = (size_t)b * a.K * N, vb = (size_t)b * N * Tm;
+    for (int k = lane; k < a.K * N; k += 64) {
+      const int len = a.s_len[sb + k];
+      if (len <= 0) continue;
+      ++sessions;
+      const int i = k % N, off = a.s_off[sb + k];
+      const int t0 = max(off, 0), t1 = (int)min((long long)off + len, (long long)hz);   // (inside [0, Tm) whatever the arrays hold)
+      double rem = a.s_cap[sb + k];
+      for (int t = t0; t < t1; ++t) {
+        const double d = fmax(a.lb[vb + (size_t)i * Tm + t], fmin(a.ub[vb + (size_t)i * Tm + t], fmax(rem, 0.0)));
+        x0[i * Tm + t] = d;
+        rem -= d;
+      }
+    }
+  }
+  __syncthreads();
+  int over = 0;
+  if (live) {
+    const int cells = (M + (a.has_peak && a.peak ? 1 : 0)) * Tm;
+    for (int c = lane; c < cells; c += 64) {
+      const int j = c / Tm, t = c - j * Tm;
+      double load, limit;
+      if (j < M) {
+        double re = 0.0, im = 0.0;
+        for (int i = 0; i < N; ++i) re += Gs[j * N + i] * x0[i * Tm + t];
+        if (a.soc)
+          for (int i = 0; i < N; ++i) im += Gs[(j + M) * N + i] * x0[i * Tm + t];
+        load = a.soc ? hypot(re, im) : re;
+        limit = a.limits[j];
+      } else {
+        load = 0.0;
+        for (int i = 0; i < N; ++i) load += x0[i * Tm + t];
+        limit = a.peak[(size_t)b * Tm + t];   // (+inf: never overloaded)
+      }
+      // load / limit > 1 + 1e-9 without the division (no NaN of 0 / 0: this unit is compiled with -fno-honor-nans)
+      over += (limit > 0.0 ? load > (1.0 + 1e-9) * limit : limit == 0.0 && load > 0.0) ? 1 : 0;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { over += __shfl_xor(over, o); sessions += __shfl_xor(sessions, o); }
+  if (live && lane == 0) a.keys[b] = min(kOrderKeys - 1, 8 * min(over, 127) + min(7, sessions / 8));
 }
 __global__ __launch_bounds__(kOrderKeys) void order_sort_kernel(const int32_t* keys, int B, int32_t* order) {
   __shared__ int hist[kOrderKeys], scan[kOrderKeys];

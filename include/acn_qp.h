@@ -335,7 +335,8 @@ int32_t acnqp_kernel_times(acnqp_handle* h, float* out_ms, int32_t capacity);
  * durations: a caller that sums them can tell from this count whether any were dropped).                    */
 int64_t acnqp_launch_count(acnqp_handle* h);
 
-/* Of those, the launches whose QUEUE ORDER was sorted (longest expected problem first, by session count: launches of
+/* Of those, the launches whose QUEUE ORDER was sorted (longest expected problem first, by how much of the greedy
+ * schedule the site rows reject -- ACNQP_ORDER_KEY=sessions in the environment: by session count; launches of
  * >= 768 problems on sites without a load-flattening / demand-charge row).  Test plumbing: lets a test assert that the
  * ordered path really ran.  Every launch hands its problems to the resident workgroups through a work queue (one
  * atomic counter per launch); ACNQP_NO_QUEUE=1 / ACNQP_NO_ORDER=1 in the environment select the static schedule / the

@@ -1,6 +1,6 @@
 """How long the headline step's launches must take, from the CPU twin's iteration counts alone (no GPU): a SIMULATION.
 
-    python tools/sim_launch_tail.py [--rank R] [--us-per-iteration 3.67] [--threads 8] [--cap-iterations 808]
+    python tools/sim_launch_tail.py [--rank R] [--site K] [--us-per-iteration 3.67] [--threads 8] [--cap-iterations 808]
 
 The bench's 16,384 problems (caltech54, horizon 12, SOC, the seeds of bench.py for rank R) are solved by the twin
 (oracle/admm_port.c; its iteration counts are the wave kernel's), and the counts are list-scheduled on the chip's 1,024
@@ -12,8 +12,16 @@ per wave-iteration (default 3.67 us: 2,202 quad-cycles per problem-iteration, pr
   pipelined  the chunk plan of a uniform wave call (plan_chunk_caps, acn_qp_pipeline.hpp: 2,048 / 4,096 / 8,192 / 2,048),
              each chunk a launch of its own in call order; a CU passes to the next launch when the slowest of its four
              waves is done (copies, the polish and the launch gaps are not modelled)
-Keys: the session count (what order_keys_kernel sorts by), sum of s_len, sum of ub, deliverable energy (sum of s_cap),
-natural order, and -- as the bound for any key -- the true iteration counts."""
+Keys, five measures of DEMAND: the session count (order_keys_kernel's key under ACNQP_ORDER_KEY=sessions), sum of s_len,
+sum of ub, deliverable energy (sum of s_cap), natural order; four measures of CONGESTION, all of the greedy schedule of
+tests/order_key_spec.py (every session at its upper bound until its cap is used up) set against the site rows:
+  overload_cells                    C, the (row, period) cells whose load exceeds the limit
+  overload_key                      8 min(C, 127) + min(7, sessions / 8): what order_keys_kernel computes
+  max_ratio_q128                    the largest load / limit of any cell, in steps of 1 / 128
+  overload_periods_x64_plus_sessions  periods with an overloaded cell, times 64, plus the session count
+and -- as the bound for any key -- the true iteration counts.  Every key also reports its makespans in wave-iterations.
+--site K: instead of the headline workload, the 1,024 demand scenarios of site K of bench.py's configs[3] legs
+(cfg3_site in bench.py), one launch on 512 and on 1,024 slots; `lone_iterations_by_slots` per key."""
 import argparse
 import heapq
 import json
@@ -28,9 +36,9 @@ sys.path.insert(0, ROOT)
 WAVES, PER_WG = 1024, 4
 
 
-def lone(iters, order):
+def lone(iters, order, slots=WAVES):
     """makespan (iterations) of one launch: every wave slot takes the next position of the queue when it is free"""
-    free = [0] * WAVES
+    free = [0] * slots
     heapq.heapify(free)
     end = 0
     for b in order:
@@ -71,6 +79,7 @@ def plan(total):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rank", type=int, default=0)
+    ap.add_argument("--site", type=int, default=None, help="site K of bench.py's configs[3] legs instead of the headline workload")
     ap.add_argument("--us-per-iteration", type=float, default=2202 * 4 / 2.4e3)
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--batches", type=int, default=64)
@@ -83,21 +92,62 @@ if __name__ == "__main__":
     from adacharge_amd.builder import build_batch, make_site
     from oracle import admm_port
 
+    from tests import order_key_spec as spec
+
+    DEMAND = ("sessions", "sum_s_len", "sum_ub", "energy")
+    CONGESTION = ("overload_cells", "overload_key", "max_ratio_q128", "overload_periods_x64_plus_sessions")
+
+    def keys_of(batch):
+        s_len = np.asarray(batch.s_len).reshape(batch.B, -1)
+        ratios, C, key = spec.describe(batch)
+        over = ratios > spec.OVERLOAD
+        finite = np.where(np.isfinite(ratios), ratios, 0.0).reshape(batch.B, -1)
+        worst = finite.max(axis=1) if finite.shape[1] else np.zeros(batch.B)
+        return {"sessions": (s_len > 0).sum(axis=1), "sum_s_len": s_len.sum(axis=1),
+                "sum_ub": np.asarray(batch.ub).reshape(batch.B, -1).sum(axis=1),
+                "energy": np.asarray(batch.s_cap).reshape(batch.B, -1).sum(axis=1),
+                "overload_cells": C, "overload_key": key.astype(np.int64),
+                "max_ratio_q128": np.minimum(1023, np.floor(worst * 128)).astype(np.int64),
+                "overload_periods_x64_plus_sessions": over.any(axis=1).sum(axis=1) * 64 + (s_len > 0).sum(axis=1)}
+
+    if args.site is not None:
+        # bench.py, cfg3_site(k): one snapshot of the site, 1,024 lognormal demand scenarios
+        from adacharge_amd.builder import scenario_batch
+
+        infra = sites.eight_sites()[args.site]
+        iface = Interface({"infrastructure_info": infra, "period": 5})
+        rng = np.random.default_rng(500 + args.site)
+        qc_es = [ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-3)]
+        base = build_batch([sites.random_sessions(infra, 12, rng)], infra, iface, qc_es, "SOC")
+        batch = scenario_batch(base, rng.lognormal(0.0, 0.25, size=(1024, base.K, base.N)))
+        iters = np.minimum(admm_port.solve_batch(batch, threads=args.threads, accel_mem=5)["iters"].astype(np.int64), args.cap_iterations)
+        keys = keys_of(batch)
+        keys["natural"] = np.zeros(iters.size)
+        keys["true_iterations"] = iters
+        out = {"simulation": "list schedule of the CPU twin's iteration counts; nothing here was measured on a GPU",
+               "site": args.site, "evse": int(batch.N), "site_rows": int(batch.site.Mg), "problems": int(iters.size),
+               "mean_iterations": float(iters.mean()), "max_iterations": int(iters.max()),
+               "no_overloaded_cell": int((keys["overload_cells"] == 0).sum()),
+               "even_iterations_by_slots": {str(s_): float(iters.sum() / s_) for s_ in (512, 1024)}, "keys": {}}
+        for name, key in keys.items():
+            order = np.argsort(-key, kind="stable")
+            out["keys"][name] = {"lone_iterations_by_slots": {str(s_): lone(iters, order, s_) for s_ in (512, 1024)}}
+        print(json.dumps(out, indent=1))
+        raise SystemExit(0)
+
     infra = sites.caltech54()
     iface = Interface({"infrastructure_info": infra, "period": 5})
     objective = [ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-12)]
     site = make_site(infra, "SOC")
-    iters, keys = [], {"sessions": [], "sum_s_len": [], "sum_ub": [], "energy": []}
+    iters, keys = [], {k: [] for k in DEMAND + CONGESTION}
     for g in range(args.batches):
         sn = sites.snapshot_batch(infra, 12, 256, seed=20240 + 7919 * args.rank + 104729 * g)
         batch = build_batch(sn, infra, iface, objective, "SOC", site=site)
         iters.append(admm_port.solve_batch(batch, threads=args.threads, accel_mem=5)["iters"])
-        s_len = np.asarray(batch.s_len).reshape(batch.B, -1)
-        keys["sessions"].append((s_len > 0).sum(axis=1))
-        keys["sum_s_len"].append(s_len.sum(axis=1))
-        keys["sum_ub"].append(np.asarray(batch.ub).reshape(batch.B, -1).sum(axis=1))
-        keys["energy"].append(np.asarray(batch.s_cap).reshape(batch.B, -1).sum(axis=1))
-    iters = np.minimum(np.concatenate(iters).astype(np.int64), args.cap_iterations)
+        for k, v in keys_of(batch).items():
+            keys[k].append(v)
+    raw_iters = np.concatenate(iters).astype(np.int64)
+    iters = np.minimum(raw_iters, args.cap_iterations)
     keys = {k: np.concatenate(v) for k, v in keys.items()}
     keys["natural"] = np.zeros(iters.size)
     keys["true_iterations"] = iters
@@ -112,11 +162,15 @@ if __name__ == "__main__":
            "even_ms": float(iters.sum() / WAVES * ms),
            "at_least_400_iterations": int((iters >= 400).sum()),
            "at_least_400_in_last_6384_of_session_order": int((iters[by_sessions[-6384:]] >= 400).sum()),
+           "no_overloaded_cell": int((keys["overload_cells"] == 0).sum()),
+           "first_check_20_iterations": int((raw_iters == 20).sum()),
+           "no_overloaded_cell_xor_20_iterations": int(((keys["overload_cells"] == 0) != (raw_iters == 20)).sum()),
            "keys": {}}
     for name, key in keys.items():
         order = np.argsort(-key, kind="stable")
         chunks = [lo + np.argsort(-key[lo:hi], kind="stable") for lo, hi in zip(bounds[:-1], bounds[1:])]
-        l, p = lone(iters, order) * ms, pipelined(iters, chunks) * ms
+        li, pi = lone(iters, order), pipelined(iters, chunks)
+        l, p = li * ms, pi * ms
         out["keys"][name] = {"lone_ms": round(l, 2), "pipelined_ms": round(p, 2), "lone_over_even": round(l / out["even_ms"] - 1, 3),
-                             "pipelined_over_even": round(p / out["even_ms"] - 1, 3)}
+                             "pipelined_over_even": round(p / out["even_ms"] - 1, 3), "lone_iterations": li, "pipelined_iterations": pi}
     print(json.dumps(out, indent=1))
