@@ -182,6 +182,7 @@ def _abi():
         rows += [(stem + "_host", rc, args), (stem + "_device", rc, args + [stream])]
     introspection = [
         ("acnqp_debug_polish_alongside", i64, [h]),
+        ("acnqp_debug_direct_x", i64, [h]),
         ("acnqp_debug_wave_rank", rc, [h, P(i32)]),
         ("acnqp_debug_wave_evse_extent", rc, [h, P(i32)]),
         ("acnqp_debug_order_keys", rc, [h, P(_Problems), P(i32)]),
@@ -657,16 +658,21 @@ class SiteHandle:
         del keep
         return [self._finish(b, r) for b, r in zip(batches, results)]
 
-    def prepare_many(self, batches, pinned_results: bool = True, x_dev_ptrs=None):
+    def prepare_many(self, batches, pinned_results=True, x_dev_ptrs=None, warm=None):
         """Marshal once, solve repeatedly (bench.py): returns a callable ``run(options)`` that re-submits the same
-        host buffers through acnqp_solve_batches and the list of BatchResults it fills.  ``x_dev_ptrs[g]``: optional
-        device address that also receives batch g's schedules (acnqp_results.x_dev)."""
+        host buffers through acnqp_solve_batches and the list of BatchResults it fills.  ``pinned_results``: one choice
+        for all batches, or one per batch.  ``x_dev_ptrs[g]``: optional device address that also receives batch g's
+        schedules (acnqp_results.x_dev).  ``warm[g]``: optional warm start of batch g, as ``solve`` takes it."""
         n = len(batches)
+        warm = [None] * n if warm is None else list(warm)
+        pinned = [bool(pinned_results)] * n if isinstance(pinned_results, (bool, np.bool_)) else [bool(v) for v in pinned_results]
+        if len(pinned) != n or len(warm) != n:
+            raise ValueError("pinned_results and warm need one entry per batch")
         P, R = (_Problems * n)(), (_Results * n)()
         results, keep = [], []
         for g, batch in enumerate(batches):
             self._check_site(batch)
-            P[g], R[g], res, k = self._marshal(batch, pinned_results, None if x_dev_ptrs is None else x_dev_ptrs[g])
+            P[g], R[g], res, k = self._marshal(batch, pinned[g], None if x_dev_ptrs is None else x_dev_ptrs[g], warm=warm[g])
             results.append(res)
             keep.append(k)
 
@@ -940,6 +946,11 @@ class SiteHandle:
         if self._lib.acnqp_debug_order_keys(self._h, C.byref(p), keys.ctypes.data_as(C.POINTER(C.c_int32))) != 0:
             raise RuntimeError("acnqp_debug_order_keys failed")
         return keys
+
+    def direct_x(self) -> int:
+        """Problems of this handle's last host-entry call whose schedule the kernel stored straight into the caller's pinned
+        result array instead of a copy (acnqp_debug_direct_x: introspection, not part of the ABI)."""
+        return int(self._lib.acnqp_debug_direct_x(self._h))
 
     def ordered_launches(self) -> int:
         """Launches of this handle whose queue order was sorted by a key (acnqp_ordered_launch_count)."""

@@ -88,6 +88,7 @@ struct acnqp_handle {
   hipEvent_t ev_start[kEvRing] = {}, ev_stop[kEvRing] = {};
   long long launches = 0, reported = 0;           // launches recorded / already handed out by acnqp_kernel_times
   long long ordered_launches = 0;                 // launches whose queue order was sorted by launch_order_keys' key (acnqp_ordered_launch_count)
+  long long direct_x_last = 0;                    // problems of the last host-entry call whose x the kernel stored into the caller's array (acnqp_debug_direct_x)
   // host-buffer entry points: kSlots pipeline slots, each with its own stream and device staging, so that the
   // H2D copies, the kernel and the D2H copies of successive chunks of a call overlap
   static constexpr int kSlots = 4;
@@ -226,7 +227,9 @@ int polish_block_doubles(const acnqp_handle* h, const acnqp::Route& rt) {
 }
 
 // acnqp_solve_batch_device with the pipeline's knowledge of what comes after the launch (nothing_follows: launch_with_polish)
-int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows);
+// and of where the schedules go (x_host: TiledArgs::x_host, a device array; null: r->x only)
+int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows,
+                       double* const* x_host = nullptr);
 
 }  // namespace
 
@@ -431,6 +434,7 @@ acnqp::TiledArgs tiled_args(const acnqp_handle* h, const acnqp_problems* p, cons
   for (auto& sl : h->slot) own = own || sl.st == st;
   a.grid_oversub = own ? 4 : 1;
   a.polish_iters = 0; a.polish_stall = 0; a.resume = 0; a.y_for_polish_only = 0; a.pol_rows = 0; a.pol_list = nullptr; a.pol_count = nullptr; a.pol_retired = nullptr; a.count_dev = nullptr;
+  a.x_host = nullptr;
   return a;
 }
 
@@ -554,6 +558,22 @@ hipError_t launch_solver(const acnqp_handle* h, const acnqp::Route& rt, const ac
   return acnqp::launch_general(ga, nt, st);
 }
 
+// The direct path for x (acn_qp_pipeline.hpp), the handed-over problems: a problem on the polish's list gets its final
+// schedule from the polish kernel or from the resume launch, so behind the two this kernel copies x of every listed
+// problem to its host destination (null: none), in flat order like the solver's own stores.  list[0 .. *count) holds the
+// problems (every entry published: the solver launch has ended); a handful per chunk.
+__global__ __launch_bounds__(256) void pol_x_to_host_kernel(const int32_t* list, const int32_t* count, int B, int nv, const double* x,
+                                                            double* const* x_host) {
+  const int n = min(*count, B);
+  for (int pos = blockIdx.x; pos < n; pos += gridDim.x) {
+    const int b = list[pos];
+    if (b < 0 || b >= B) continue;
+    double* const dst = x_host[b];
+    if (dst == nullptr) continue;
+    for (int k = threadIdx.x; k < nv; k += blockDim.x) dst[k] = x[(size_t)b * nv + k];
+  }
+}
+
 // ---- the polish (acn_qp_polish.hpp): small sites, separable objective, served by an on-chip kernel ------------------
 // solver kernel (pass 0 up to polish_iters iterations; what has not converged by then is listed) -> polish kernel over
 // the list -> solver kernel again over the list for what the polish gave up on (from scratch, with the retry passes:
@@ -659,14 +679,21 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
     // retry passes that may follow start cold, as always).  Measured on jpl52 x 24 x 4,096, where two problems have more
     // tight rows than the polish holds: from scratch the launch took 93 ms against 61 ms without a polish.
     a3.warm_x = r->x; a3.warm_y = ybuf;
+    a3.x_host = nullptr;   // (the listed problems' schedules go to the host below, whoever had the last word on them)
     a3.ws_by_slot = 1; a3.grid_cap = std::min(p->batch, a.grid_oversub > 1 ? 64 : 2 * h->cus);   // (<= the grid the workspace was sized for)
     if (!a.ws_by_slot) a3.grid_cap = std::min(a3.grid_cap, a.grid_cap);
     *e = launch_solver(h, rt, a3, ws, st);
   }
+  if (*e == hipSuccess && a.x_host != nullptr) {   // (not a launch of acnqp_launch_count: it belongs to this one)
+    hipLaunchKernelGGL(pol_x_to_host_kernel, dim3((unsigned)std::min(p->batch, 64)), dim3(256), 0, st, list, ctr + 2, p->batch,
+                       s.N * p->t_max, r->x, a.x_host);
+    *e = hipGetLastError();
+  }
   return ACNQP_OK;
 }
 
-int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows) {
+int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows,
+                       double* const* x_host) {
   int rc = check_problem_shapes(h, p, o, r);
   if (rc != ACNQP_OK) return rc;
   if (p->batch == 0) return ACNQP_OK;
@@ -680,6 +707,8 @@ int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_opt
   const int evk = (int)(h->launches % acnqp_handle::kEvRing);
   HIP_TRY(hipEventRecord(h->ev_start[evk], st));
   const acnqp::Route rt = route_of(h, p->t_max, p->k_sessions, p->batch);
+  if (x_host != nullptr && !rt.direct_x()) return fail(ACNQP_ERR_INVALID, "direct x on a route that cannot store it");   // (run_call asks the same table)
+  a.x_host = x_host;
   acnqp_handle::Work* wk = h->work_for(st);
   if ((rc = schedule_launch(h, wk, rt, p, st, &a)) != ACNQP_OK) return rc;
   Workspace ws;
@@ -744,6 +773,11 @@ extern "C" int64_t acnqp_debug_polish_alongside(acnqp_handle* h) {
   if (hipMemset(h->pol_stats + 16, 0, sizeof v) != hipSuccess) return -1;
   return v;
 }
+
+// Introspection outside include/acn_qp.h (every build): the problems of the handle's last host-entry call
+// (acnqp_solve_batch / _batches / _table) whose schedule the kernel stored straight into the caller's result array
+// (the direct path, acn_qp_pipeline.hpp) instead of a copy; 0 where every x was copied, -1 without a handle.
+extern "C" int64_t acnqp_debug_direct_x(acnqp_handle* h) { return h ? (int64_t)h->direct_x_last : -1; }
 
 // Introspection outside include/acn_qp.h (every build): out[0] = live eigenpairs of the site's G G', out[1] = the MFMA
 // k-steps that hold them once compacted (acn_qp_rank.hpp), out[2] = the eigen extent in k-steps of the wave kernel's

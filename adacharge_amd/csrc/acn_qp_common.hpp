@@ -81,6 +81,9 @@ struct TiledArgs {
   int32_t* pol_retired;       // null, or (wave kernel, work-queue launches): the problems of this launch that are finished and, where
                               // handed over, published -- what a polish launch running ALONGSIDE this one waits for
   const int32_t* count_dev;   // number of queue positions, on the device (null: B)
+  double* const* x_host;      // null, or (wave kernel, one wave per problem: Route::direct_x) [B] device-addressable HOST destinations
+                              // of the problems' schedules (null entry: none): the wave that gives problem b its verdict also
+                              // stores x there, in flat order -- the host entries then copy no x back
   int ws_by_slot;  // 1: a streaming kernel's workspace belongs to the workgroup slot (work-queue launches), 0: to the problem
   int grid_oversub; // host side only: workgroups of a work-queue launch per resident slot (1: fully persistent; the pipelined
                     // host entries use 4, so that slots come free while a launch runs and the next stream's small launches --

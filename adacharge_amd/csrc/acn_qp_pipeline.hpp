@@ -18,9 +18,10 @@ inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // device layout of one chunk of `cn` problems (inputs in slot.in, results in slot.out)
 struct ChunkLayout {
-  size_t lb, ub, q, pd, hz, so, sl, sc, eq, pk, lf, dc, df, wx, wy, in_total;
+  size_t lb, ub, q, pd, hz, so, sl, sc, eq, pk, lf, dc, df, xh, wx, wy, in_total;
   size_t x, st, it, pr, du, ob, y, out_total;
-  ChunkLayout(size_t cn, size_t N, size_t Tm, size_t K, size_t Mg, bool peak, bool flat, bool mx, bool warm, bool want_y) {
+  // direct: the chunk carries the host destinations of its problems' schedules (xh: one double* per problem, a small input)
+  ChunkLayout(size_t cn, size_t N, size_t Tm, size_t K, size_t Mg, bool peak, bool flat, bool mx, bool warm, bool want_y, bool direct = false) {
     size_t o = 0;
     lb = o; o += al256(cn * N * Tm * 8);
     ub = o; o += al256(cn * N * Tm * 8);
@@ -35,6 +36,7 @@ struct ChunkLayout {
     lf = o; o += al256(flat ? cn * 8 : 0);
     dc = o; o += al256(mx ? cn * 8 : 0);
     df = o; o += al256(mx ? cn * 8 : 0);
+    xh = o; o += al256(direct ? cn * sizeof(double*) : 0);
     wx = o; o += al256(warm ? cn * N * Tm * 8 : 0);
     wy = o; o += al256(warm ? cn * Mg * Tm * 8 : 0);
     in_total = o;
@@ -56,6 +58,8 @@ struct PlanEnv {
   long long chunk = 0;          // ACNQP_CHUNK > 0: problems per chunk instead of the route's wanted size
   const char* plan = nullptr;   // ACNQP_PLAN "a,b,c": explicit chunk sizes of a planned (wave) call; the rest goes into a last chunk
   bool ramp = true;             // ACNQP_NO_RAMP unset
+  bool direct = false;          // not a variable: the kernel stores every schedule of the call into the caller's host arrays
+                                // (Route::direct_x, run_call), so no copy of x stands behind the last launch
 };
 
 // inputs + results staged per problem -- every one of the kSlots pipeline slots holds a chunk of each, so a chunk is
@@ -72,6 +76,8 @@ inline long long chunk_cap_by_memory(size_t N, size_t Tm, size_t K) {
 //    for its inputs, and nothing overlaps that copy), full chunks, and a quarter-size one at the END (what follows the
 //    last solver launch -- its polish, its result copies -- is exposed too): c/4 + c/2 + k c + c/4 = total with the
 //    smallest k for which c <= cap.  Fewer than 2,048 problems (or a cap below that) make one chunk.
+//  * ... with env.direct (the kernel writes the schedules to the caller's arrays itself) without the small last chunk:
+//    u, 2u, 2u in front, then chunks of 3u (below).
 //  * Every other call ramps: a quarter-size first chunk, then a half-size one, then full ones.
 inline std::vector<long long> plan_chunk_caps(long long total, long long want, long long by_mem, bool wave, bool uniform,
                                               const PlanEnv& env) {
@@ -83,6 +89,24 @@ inline std::vector<long long> plan_chunk_caps(long long total, long long want, l
     if (env.plan) {
       // (an entry below 1 would never end the call: clamped)
       for (const char* q = env.plan; *q;) { caps.push_back(std::max<long long>(1, std::atoll(q))); while (*q && *q != ',') ++q; if (*q == ',') ++q; }
+    } else if (env.direct && total >= 2048 && cap >= 2048) {
+      // Nothing but the copy of the small result arrays follows the last launch, so the small last chunk goes: in units of
+      // u the chunks are u, 2u, 2u in front and then m chunks of 3u -- 2,048 / 4,096 / 4,096 / 6,144 for 16,384 problems --
+      // with u = ceil(total / (5 + 3 m)) and the smallest m >= 1 for which 3u <= cap; the front takes what the m last
+      // chunks leave (f <= 5u problems: f/5, 2f/5 and the rest).  The last chunk is the largest: its launch starts when
+      // its inputs have landed, and the inputs of the whole call land only two thirds into the step (41 GB/s measured
+      // on the headline step), so what it holds is what the chip has left to do from then on; a last chunk of half the call
+      // (u, u, 2u, 4u) measured no gain over the copy path, the small one of the copy path's plan 0.15 ms.
+      long long m = 1, u = 0;
+      for (;; ++m) {
+        u = (total + 4 + 3 * m) / (5 + 3 * m);
+        if (3 * u <= cap) break;
+      }
+      const long long f = total - 3 * u * m;   // (> 0: with m - 1 last chunks 3u was above the cap, so total > (2 + 3m) u)
+      caps.push_back(std::max<long long>(1, f / 5));
+      caps.push_back(std::max<long long>(1, 2 * f / 5));
+      caps.push_back(std::max<long long>(1, f - f / 5 - 2 * f / 5));
+      for (long long i = 0; i < m; ++i) caps.push_back(3 * u);
     } else if (total >= 2048 && cap >= 2048) {
       const long long k = (total + cap - 1) / cap - 1;
       long long c = total / (k + 1);
@@ -328,7 +352,26 @@ struct Call {
   acnqp_results* R = nullptr;      // [nb]; the table's one
   std::vector<BatchShape> bs;
   std::vector<Scatter> scatter;    // dense entry with staged small arrays
+  std::vector<double*> xdst;       // [nb] the direct path: R[g].x as the device addresses it (null: batch g keeps its copies)
 };
+
+// ---- the direct path for x ---------------------------------------------------------------------------------------------
+// A result array x in device-addressable host memory (pinned: acnqp_host_alloc, hipHostMalloc, hipHostRegister) is written
+// by the kernel itself where the route can do that (Route::direct_x; TiledArgs::x_host): the wave that gives a problem
+// its verdict stores the schedule there, pol_x_to_host_kernel (acn_qp_api.hip) those of the handed-over problems, and the
+// chunk loop queues no copy of x.  The destinations ride with the chunk's small inputs (ChunkLayout::xh), so only the
+// dense entry with its pinned mirrors takes the path.  Pageable and device arrays keep their copies; a call may mix both.
+// ACNQP_NO_DIRECT_X=1 (diagnostic, read once per process): the copy path everywhere.
+double* direct_destination(const double* x) {
+  static const bool off = std::getenv("ACNQP_NO_DIRECT_X") != nullptr;
+  if (off || x == nullptr) return nullptr;
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, x) != hipSuccess) {   // (memory the runtime does not know: pageable)
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return at.type == hipMemoryTypeHost ? static_cast<double*>(at.devicePointer) : nullptr;
+}
 
 // the device-side view of a chunk of cn problems laid out by L in a slot's staging (di: inputs, dq: results)
 void device_views(const ChunkLayout& L, char* di, char* dq, const acnqp::SiteShape& s, size_t cn, const BatchShape& b,
@@ -381,8 +424,10 @@ std::vector<std::vector<Piece>> split_call(const acnqp_handle* h, const std::vec
         if (caps.empty() || !uniform) {
           // (the planner asks for the route of the CALL: under ACNQP_WAVE_MIN_BATCH a chunk may run another family)
           const acnqp::Route rt = acnqp::route_for(h->shape, b.t_max, b.k_sessions, (int)std::min<long long>(total, acnqp::kRouteAnyBatch), route_switches());
+          acnqp::PlanEnv e = env;   // (env.direct: every batch of the call has a direct destination)
+          e.direct = env.direct && rt.direct_x();
           caps = acnqp::plan_chunk_caps(total, rt.chunk_want(), acnqp::chunk_cap_by_memory((size_t)h->shape.N, (size_t)b.t_max, (size_t)b.k_sessions),
-                                        rt.wv > 0, uniform, env);
+                                        rt.wv > 0, uniform, e);
         }
         cap = acnqp::chunk_cap(caps, chunks.size() - 1);
       }
@@ -431,6 +476,11 @@ int fill_dense(acnqp_handle* h, const Call& call, size_t c, const std::vector<Pi
     if (s.has_flat) H2S(lf, L.lf, 8, 1);
     if (s.has_max) { H2S(dc, L.dc, 8, 1); H2S(dfloor, L.df, 8, 1); }
     if (b.warm) { H2D(warm_x, L.wx, 8, nv); H2D(warm_y, L.wy, 8, Mg * Tm); }
+    if (hs && L.xh != L.wx) {   // a direct chunk: where the kernel stores each problem's schedule (null: this piece is copied)
+      double** tab = reinterpret_cast<double**>(hs + L.xh) + pos;
+      double* const dst = call.xdst[pc.g];
+      for (size_t i = 0; i < n; ++i) tab[i] = dst ? dst + (lo + i) * nv : nullptr;
+    }
 #undef H2S
 #undef H2D
   }
@@ -491,10 +541,28 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
   env.plan = std::getenv("ACNQP_PLAN");
   static const bool ramp = std::getenv("ACNQP_NO_RAMP") == nullptr;
   env.ramp = ramp;
+  // the direct path: the batches' destinations, asked once per batch (dense entry only)
+  h->direct_x_last = 0;
+  call.xdst.assign(call.bs.size(), nullptr);
+  env.direct = !table && !call.bs.empty();
+  for (size_t g = 0; g < call.bs.size() && !table; ++g) {
+    call.xdst[g] = call.bs[g].batch > 0 ? direct_destination(call.R[g].x) : nullptr;
+    env.direct = env.direct && (call.xdst[g] != nullptr || call.bs[g].batch == 0);
+  }
   const std::vector<std::vector<Piece>> chunks = split_call(h, call.bs, env);
-  auto layout = [&](const std::vector<Piece>& pcs) {
+  // a chunk is direct if its launch's route can store to the host and one of its pieces has a destination
+  std::vector<char> direct(chunks.size(), 0);
+  for (size_t c = 0; c < chunks.size() && !table; ++c) {
+    const std::vector<Piece>& pcs = chunks[c];
     const BatchShape& b = call.bs[pcs[0].g];
-    return ChunkLayout((size_t)(pcs.back().pos + pcs.back().n), N, b.t_max, b.k_sessions, Mg, s.has_peak, s.has_flat, s.has_max, b.warm, b.want_y);
+    if (!route_of(h, b.t_max, b.k_sessions, (int)(pcs.back().pos + pcs.back().n)).direct_x()) continue;
+    for (const Piece& pc : pcs) direct[c] = direct[c] || call.xdst[pc.g] != nullptr;
+  }
+  auto layout = [&](size_t c) {
+    const std::vector<Piece>& pcs = chunks[c];
+    const BatchShape& b = call.bs[pcs[0].g];
+    return ChunkLayout((size_t)(pcs.back().pos + pcs.back().n), N, b.t_max, b.k_sessions, Mg, s.has_peak, s.has_flat, s.has_max, b.warm, b.want_y,
+                       direct[c] != 0);
   };
   // Dense entry only: pinned mirrors of the chunks' SMALL arrays (device ranges [pd, wx) and [st, y) of ChunkLayout),
   // whole call -- one H2D and one D2H per chunk instead of nine and five per piece; beyond kSmallCap the per-batch copies
@@ -505,7 +573,7 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
   std::vector<size_t> in_off(chunks.size()), out_off(chunks.size());
   size_t in_sum = 0, out_sum = 0;
   for (size_t c = 0; c < chunks.size() && !table; ++c) {
-    const ChunkLayout L = layout(chunks[c]);
+    const ChunkLayout L = layout(c);
     in_off[c] = in_sum; in_sum += L.wx - L.pd;
     out_off[c] = out_sum; out_sum += L.y - L.st;
   }
@@ -514,13 +582,15 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
   if (staged) {
     HIP_TRY(h->small_in.reserve(in_sum));
     HIP_TRY(h->small_out.reserve(out_sum));
+  } else {
+    std::fill(direct.begin(), direct.end(), 0);   // (the destinations ride in the mirror)
   }
   for (size_t c = 0; c < chunks.size(); ++c) {
     acnqp_handle::Slot& S = h->slot[c % acnqp_handle::kSlots];
     const std::vector<Piece>& pcs = chunks[c];   // (table entry: one piece)
     const BatchShape& b = call.bs[pcs[0].g];
     const size_t cn = (size_t)(pcs.back().pos + pcs.back().n), Tm = b.t_max;
-    const ChunkLayout L = layout(pcs);
+    const ChunkLayout L = layout(c);
     const TableLayout TL = table ? TableLayout(call.T, pcs[0].lo, pcs[0].n, N * Tm) : TableLayout();
     if (L.in_total > S.in.cap || L.out_total > S.out.cap || TL.total > S.tin.cap) HIP_TRY(hipStreamSynchronize(S.st));   // staging still in use
     HIP_TRY(S.in.reserve(L.in_total));
@@ -536,7 +606,8 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
     acnqp_problems dp;
     acnqp_results dr;
     device_views(L, di, dq, s, cn, b, &dp, &dr);
-    rc = solve_batch_device(h, &dp, o, &dr, S.st, c + 1 == chunks.size());   // (the last chunk: nothing follows its launch)
+    double* const* x_host = direct[c] ? reinterpret_cast<double* const*>(di + L.xh) : nullptr;
+    rc = solve_batch_device(h, &dp, o, &dr, S.st, c + 1 == chunks.size(), x_host);   // (the last chunk: nothing follows its launch)
     if (rc != ACNQP_OK) return rc;
     if (staged) HIP_TRY(hipMemcpyAsync(ho + L.st, dq + L.st, L.y - L.st, hipMemcpyDeviceToHost, S.st));
     for (const Piece& pc : pcs) {
@@ -545,7 +616,8 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
 #define D2H(field, base, elem, per)                                                                          \
   HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(r.field) + lo * (per) * (elem), dq + (base) + pos * (per) * (elem), \
                          n * (per) * (elem), hipMemcpyDeviceToHost, S.st))
-      D2H(x, L.x, 8, N * Tm);
+      if (direct[c] && call.xdst[pc.g]) h->direct_x_last += (long long)n;   // (the kernel has stored them, or will have)
+      else D2H(x, L.x, 8, N * Tm);
       if (staged) {
         call.scatter.push_back(Scatter{pc.g, lo, n, pos, ho, L.st, L.it, L.pr, L.du, L.ob});
       } else {

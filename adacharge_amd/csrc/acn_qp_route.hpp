@@ -113,6 +113,11 @@ struct Route {
   // 8,192 although tiled_shape is false for it.
   long long chunk_want() const { return wv > 0 ? 8192 : (tiled ? 1024 : 2048); }
 
+  // The kernel can store a problem's schedule straight into a device-addressable host array (TiledArgs::x_host; the host
+  // entries then copy no x back and plan their chunks without the small last one, acn_qp_pipeline.hpp): the wave kernel
+  // with one wave per problem.  By shape alone.
+  bool direct_x() const { return wv == 1; }
+
   // Anderson columns the family can hold (acnqp_accel_columns = min(requested, this)); `Kn`: the kernels' own numbers
   template <class Kn> int accel_cap() const {
     if (wv > 0) return Kn::wave_accel();

@@ -108,6 +108,24 @@ __device__ inline void wave_lds_sync() {   // this wave's LDS writes are visible
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The direct path for x (TiledArgs::x_host): the n = N * Tm doubles of one problem's schedule go to the
+// caller's host array in FLAT order -- lane i stores elements i, i + 64, ..., so one store instruction covers 512
+// contiguous bytes (the lane = EVSE layout would send 8-byte pieces at a stride of Tm doubles over the link).  `xt`: the
+// schedule in the wave's transpose scratch (row = EVSE, `xs` doubles apart), or null for a schedule of zeros.  Posted
+// writes: the host reads them after the stream has drained.  Inlined on purpose: the headline instantiation keeps its 18
+// spilled registers and 80 bytes of scratch this way, while a call here (noinline) cost it 10 more spills and 144 bytes
+// (profiles/r10_kernel_resources.md against r09; the loop lost 4 % to the mere presence of the prox code once).
+__device__ __attribute__((always_inline)) inline void wave_x_to_host(const double* xt, int xs, int n, int Tm, double* dst) {
+  const int lane = threadIdx.x & 63;
+  int row = lane / Tm, col = lane - row * Tm;
+  const int drow = 64 / Tm, dcol = 64 - drow * Tm;   // (element k + 64 from element k, without a division per store)
+  for (int k = lane; k < n; k += 64) {
+    dst[k] = xt != nullptr ? xt[row * xs + col] : 0.0;
+    row += drow; col += dcol;
+    if (col >= Tm) { col -= Tm; ++row; }
+  }
+}
+
 template <int AM, int NPW, int TSV, int MT, bool PROX, int EK = 0, int NE = 0>
 __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledArgs A_kernarg) {
   static_assert(NPW == 1 || NPW == 2 || NPW == 4, "one, two or four waves per problem");
@@ -457,6 +475,10 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
 #pragma unroll
       for (int t = 0; t < TS; ++t)
         if (act && tb + t < Tm) A.x[((size_t)b * N + lane) * Tm + tb + t] = 0;
+      if constexpr (NPW == 1) {   // the direct path (wave-uniform)
+        double* const xh = A.x_host != nullptr ? A.x_host[b] : nullptr;
+        if (xh != nullptr) wave_x_to_host(nullptr, 0, N * Tm, Tm, xh);
+      }
       if (A.y_out && !A.y_for_polish_only && half == 0)
         for (int k = lane; k < A.Mg * Tm; k += 64) A.y_out[(size_t)b * A.Mg * Tm + k] = 0;
       if (lane == 0 && half == 0) {
@@ -1175,6 +1197,20 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
         A.x[((size_t)b * N + lane_o) * Tm + tb + t] = z1[t];
         ol += (0.5 * pd_user * z1[t] + qv[t]) * z1[t];
       }
+    // The direct path: behind its device copy (the polish, the resume launch, x_dev and the dual report read A.x) the
+    // schedule goes to the caller's host array, through the wave's transpose scratch (free here; the pad columns are not
+    // touched).  A problem that is handed over is stored by pol_x_to_host_kernel once its answer is final; a retry pass
+    // that replaces A.x stores again, the same lanes to the same addresses.  Wave-uniform.
+    if constexpr (NPW == 1) {
+      double* const xh = A.x_host != nullptr ? A.x_host[b] : nullptr;
+      if (xh != nullptr && status != kStatusPolish) {
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int t = 0; t < TS; ++t) XT[lane_o * XS + t] = z1[t];
+        wave_lds_sync();
+        wave_x_to_host(XT, XS, N * Tm, Tm, xh);
+      }
+    }
     if (A.y_out && (!A.y_for_polish_only || status == kStatusPolish)) {   // site-row multipliers, caller's row order and units
       const real* RS = static_cast<const real*>(A.rowscale);
       const int g_o = lane_o >> 4, t_o = lane_o & 15;

@@ -250,7 +250,9 @@ int acnqp_solve_batch(acnqp_handle* h, const acnqp_problems* p,
  * problem; chunks rotate over internal streams with their own device staging, so that
  * the H2D copies of chunk c+1 and the D2H copies of chunk c-1 overlap chunk c's kernel.
  * Buffers allocated with acnqp_host_alloc (pinned) are copied by DMA without a staging
- * hop; pageable buffers work, slower.  Every pointer is a HOST pointer; nothing is
+ * hop; pageable buffers work, slower.  A pinned r[g].x may be written by the kernels
+ * themselves while the call runs (it is the call's to write until it returns; read it
+ * after that).  Every pointer is a HOST pointer; nothing is
  * retained after return.  Every problem's status is set (never ACNQP_STATUS_UNSET) or
  * the call fails with ACNQP_ERR_HIP.                                                 */
 int acnqp_solve_batches(acnqp_handle* h, int32_t n_batches, const acnqp_problems* p,

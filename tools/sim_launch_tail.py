@@ -21,7 +21,16 @@ tests/order_key_spec.py (every session at its upper bound until its cap is used 
   overload_periods_x64_plus_sessions  periods with an overloaded cell, times 64, plus the session count
 and -- as the bound for any key -- the true iteration counts.  Every key also reports its makespans in wave-iterations.
 --site K: instead of the headline workload, the 1,024 demand scenarios of site K of bench.py's configs[3] legs
-(cfg3_site in bench.py), one launch on 512 and on 1,024 slots; `lone_iterations_by_slots` per key."""
+(cfg3_site in bench.py), one launch on 512 and on 1,024 slots; `lone_iterations_by_slots` per key.
+
+The step in TIME (`timed`, printed with --link-gbs; the launch-order key the library ships, overload_key):
+  --link-gbs G   chunk c's launch cannot start before its inputs have landed: 21.65 KB per problem (bench shape: lb, ub, q
+                 and the small arrays) over a host link of G GB/s, the chunks' inputs one after the other, plus 60 us for
+                 the order kernels and the launch; behind each chunk the copy of its schedules (5,184 B per problem, the
+                 link's other direction, one copy at a time) -- the step ends with the last of them
+  --direct       no result copy behind a chunk (the kernel stores the schedules into the caller's pinned arrays)
+  --plan a,b,c   explicit chunk sizes, the rest in a last chunk (like ACNQP_PLAN); several plans separated by `/`
+`--plan` without --link-gbs replaces the chunk plan of `pipelined`."""
 import argparse
 import heapq
 import json
@@ -65,6 +74,45 @@ def pipelined(iters, chunks):
     return int(wg_free.max())
 
 
+IN_BYTES, OUT_BYTES, LAUNCH_MS = 21650.0, 54 * 12 * 8.0, 0.060   # per problem in, per problem out, order kernels + launch
+
+
+def timed(iters, chunks, ms_per_iteration, link_gbs, direct):
+    """End of the step in ms: `pipelined` in time, with the chunks' arrival times and (not direct) the result copies."""
+    per_ms = link_gbs * 1e6   # bytes per ms
+    wg_free = np.zeros(WAVES // PER_WG)
+    landed, copy_free, end_step = 0.0, 0.0, 0.0
+    for order in chunks:
+        landed += len(order) * IN_BYTES / per_ms
+        ready = landed + LAUNCH_MS
+        heap = [(max(float(wg_free[w // PER_WG]), ready), w) for w in range(WAVES)]
+        heapq.heapify(heap)
+        last = np.maximum(wg_free, ready)
+        for b in order:
+            t, w = heapq.heappop(heap)
+            t += float(iters[b]) * ms_per_iteration
+            last[w // PER_WG] = max(last[w // PER_WG], t)
+            heapq.heappush(heap, (t, w))
+        wg_free = last
+        end = float(last.max())
+        if not direct:
+            copy_free = max(copy_free, end) + len(order) * OUT_BYTES / per_ms
+            end = copy_free
+        end_step = max(end_step, end)
+    return end_step
+
+
+def plan_of(text, total):
+    caps, left, out = [int(v) for v in text.split(",")], total, []
+    for cap in caps:
+        if left > 0:
+            out.append(min(cap, left))
+            left -= out[-1]
+    if left > 0:
+        out.append(left)
+    return out
+
+
 def plan(total):
     c = 8192   # plan_chunk_caps for 16,384 problems: c / 4, c / 2, c, the rest
     caps, left, out = [c // 4, c // 2, c], total, []
@@ -85,6 +133,10 @@ if __name__ == "__main__":
     ap.add_argument("--batches", type=int, default=64)
     ap.add_argument("--cap-iterations", type=int, default=808,
                     help="the device hands a problem to the polish after 800 iterations (808 is the most it reports on this workload); the twin iterates on")
+    ap.add_argument("--link-gbs", type=float, default=None, help="host link in GB/s: print the step in time (`timed`)")
+    ap.add_argument("--direct", action="store_true", help="with --link-gbs: no result copy behind a chunk")
+    ap.add_argument("--plan", default=None, help="explicit chunk sizes a,b,c (the rest in a last chunk); several plans separated by /")
+    ap.add_argument("--save-iterations", default=None, help="keep the twin's iteration counts and keys in this .npz (and reuse them)")
     args = ap.parse_args()
 
     from adacharge_amd import ObjectiveComponent, equal_share, quick_charge, sites
@@ -139,21 +191,27 @@ if __name__ == "__main__":
     iface = Interface({"infrastructure_info": infra, "period": 5})
     objective = [ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-12)]
     site = make_site(infra, "SOC")
-    iters, keys = [], {k: [] for k in DEMAND + CONGESTION}
-    for g in range(args.batches):
-        sn = sites.snapshot_batch(infra, 12, 256, seed=20240 + 7919 * args.rank + 104729 * g)
-        batch = build_batch(sn, infra, iface, objective, "SOC", site=site)
-        iters.append(admm_port.solve_batch(batch, threads=args.threads, accel_mem=5)["iters"])
-        for k, v in keys_of(batch).items():
-            keys[k].append(v)
-    raw_iters = np.concatenate(iters).astype(np.int64)
+    if args.save_iterations and os.path.exists(args.save_iterations):
+        with np.load(args.save_iterations) as z:
+            raw_iters, keys = z["raw_iters"], {k: z[k] for k in DEMAND + CONGESTION}
+    else:
+        iters, keys = [], {k: [] for k in DEMAND + CONGESTION}
+        for g in range(args.batches):
+            sn = sites.snapshot_batch(infra, 12, 256, seed=20240 + 7919 * args.rank + 104729 * g)
+            batch = build_batch(sn, infra, iface, objective, "SOC", site=site)
+            iters.append(admm_port.solve_batch(batch, threads=args.threads, accel_mem=5)["iters"])
+            for k, v in keys_of(batch).items():
+                keys[k].append(v)
+        raw_iters = np.concatenate(iters).astype(np.int64)
+        keys = {k: np.concatenate(v) for k, v in keys.items()}
+        if args.save_iterations:
+            np.savez_compressed(args.save_iterations, raw_iters=raw_iters, **keys)
     iters = np.minimum(raw_iters, args.cap_iterations)
-    keys = {k: np.concatenate(v) for k, v in keys.items()}
     keys["natural"] = np.zeros(iters.size)
     keys["true_iterations"] = iters
     total = iters.size
     ms = args.us_per_iteration * 1e-3
-    sizes = plan(total)
+    sizes = plan_of(args.plan.split("/")[0], total) if args.plan else plan(total)
     bounds = np.r_[0, np.cumsum(sizes)]
     by_sessions = np.argsort(-keys["sessions"], kind="stable")
     out = {"simulation": "list schedule of the CPU twin's iteration counts; nothing here was measured on a GPU",
@@ -173,4 +231,11 @@ if __name__ == "__main__":
         l, p = li * ms, pi * ms
         out["keys"][name] = {"lone_ms": round(l, 2), "pipelined_ms": round(p, 2), "lone_over_even": round(l / out["even_ms"] - 1, 3),
                              "pipelined_over_even": round(p / out["even_ms"] - 1, 3), "lone_iterations": li, "pipelined_iterations": pi}
+    if args.link_gbs:
+        key = keys["overload_key"]
+        out["timed"] = {"link_gbs": args.link_gbs, "direct": bool(args.direct), "key": "overload_key", "end_of_step_ms": {}}
+        for text in (args.plan.split("/") if args.plan else [",".join(str(v) for v in sizes)]):
+            b_ = np.r_[0, np.cumsum(plan_of(text, total))]
+            chunks = [lo + np.argsort(-key[lo:hi], kind="stable") for lo, hi in zip(b_[:-1], b_[1:])]
+            out["timed"]["end_of_step_ms"]["/".join(str(int(hi - lo)) for lo, hi in zip(b_[:-1], b_[1:]))] = round(timed(iters, chunks, ms, args.link_gbs, args.direct), 3)
     print(json.dumps(out, indent=1))
