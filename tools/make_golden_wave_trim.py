@@ -8,7 +8,7 @@ GPU -- the bits that the wave kernel's EVSE extent, and any later change to its 
 iterations (the ring of 5 slots, one event per 5 iterations, wraps: every slot written twice) and a problem that adapts
 rho (the ring restarts): the twin does not report its adaptations, so a problem counts as adapting if its iteration count
 changes when adaptation is switched off.  Recording runs the parent library in a child process of its own (ACNQP_LIBRARY
-selects it, as in tools/gpu_wave_rank_ab.py) under a time limit, and keeps x, status, iters, pri_res, dua_res, obj."""
+selects it, as in tools/gpu_bench_ab.py) under a time limit, and keeps x, status, iters, pri_res, dua_res, obj."""
 import os
 import subprocess
 import sys
