@@ -38,44 +38,39 @@ int fail(int rc, const std::string& msg) {
       return fail(ACNQP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));    \
   } while (0)
 
-struct DevBuf {
+// grow-only buffer over one pair of allocate / free calls; reserve() frees before it allocates anew (nothing is kept)
+template <hipError_t (*Alloc)(void**, size_t), hipError_t (*Free)(void*)>
+struct GrowBuf {
   void* p = nullptr;
   size_t cap = 0;
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
+    release();
+    hipError_t e = Alloc(&p, bytes ? bytes : 16);
     if (e == hipSuccess) cap = bytes;
     return e;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) (void)Free(p);
     p = nullptr;
     cap = 0;
   }
 };
+inline hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+inline hipError_t pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+using DevBuf = GrowBuf<device_alloc, hipFree>;
+using HostBuf = GrowBuf<pinned_alloc, hipHostFree>;   // pinned host staging
 
-// pinned host staging, grow-only
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+// Grow the device buffers that earlier operations on stream `st` may still use: a buffer that must grow is freed first, so
+// the stream is drained before (once, and only if one of them grows).
+struct Want { DevBuf* buf; size_t bytes; };
+inline hipError_t reserve_behind(hipStream_t st, std::initializer_list<Want> wants) {
+  const bool grow = std::any_of(wants.begin(), wants.end(), [](const Want& w) { return w.bytes > w.buf->cap; });
+  hipError_t e = grow ? hipStreamSynchronize(st) : hipSuccess;
+  for (const Want& w : wants)
+    if (e == hipSuccess) e = w.buf->reserve(w.bytes);
+  return e;
+}
 
 }  // namespace
 
@@ -104,11 +99,12 @@ struct acnqp_handle {
   struct Work {
     hipStream_t st; DevBuf buf; DevBuf ord; DevBuf pol; long long used; hipEvent_t last; DevBuf dua;   // pol: the polish's list and multiplier buffer; dua: g of a dual report without z
     hipEvent_t fork = nullptr, join = nullptr;   // the polish alongside a solver launch: where it may start, where it has ended (created on first use)
-    void release_events() {
+    void release() {
       if (last) (void)hipEventDestroy(last);
       if (fork) (void)hipEventDestroy(fork);
       if (join) (void)hipEventDestroy(join);
       last = fork = join = nullptr;
+      for (DevBuf* b : {&buf, &ord, &pol, &dua}) b->release();
     }
   };
   std::vector<Work> work;
@@ -124,7 +120,6 @@ struct acnqp_handle {
     }();
     return v;
   }
-  DevBuf* workspace_for(hipStream_t st) { return &work_for(st)->buf; }
   Work* work_for(hipStream_t st) {
     for (auto& w : work) if (w.st == st) { w.used = ++work_clock; return &w; }
     // a caller that keeps creating streams must not grow the handle without bound: evict the least recently used
@@ -143,11 +138,7 @@ struct acnqp_handle {
       }
       if (callers >= max_caller_workspaces()) {
         if (work[lru].last) (void)hipEventSynchronize(work[lru].last);   // (behind the launch's join with the auxiliary stream)
-        work[lru].release_events();
-        work[lru].buf.release();
-        work[lru].ord.release();
-        work[lru].pol.release();
-        work[lru].dua.release();
+        work[lru].release();
         work.erase(work.begin() + (long)lru);
       }
     }
@@ -155,16 +146,6 @@ struct acnqp_handle {
     (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     work.push_back(Work{st, DevBuf(), DevBuf(), DevBuf(), ++work_clock, ev, DevBuf()});
     return &work.back();
-  }
-  void release_work() {
-    for (auto& w : work) {
-      w.release_events();
-      w.buf.release();
-      w.ord.release();
-      w.pol.release();
-      w.dua.release();
-    }
-    work.clear();
   }
   int cus = 0;   // compute units of the device (the work-queue launches size their grid from it)
   int32_t* pol_stats = nullptr;   // device counters of the polish kernel, summed over the handle's life (acnqp_polish_stats);
@@ -343,15 +324,13 @@ void acnqp_destroy(acnqp_handle* h) {
   }
   for (auto& sl : h->slot) {
     if (sl.st) { (void)hipStreamSynchronize(sl.st); (void)hipStreamDestroy(sl.st); }
-    sl.in.release();
-    sl.out.release();
-    sl.tin.release();
+    for (DevBuf* b : {&sl.in, &sl.out, &sl.tin}) b->release();
   }
   if (h->aux) { (void)hipStreamSynchronize(h->aux); (void)hipStreamDestroy(h->aux); }
   h->small_in.release();
   h->small_out.release();
   for (auto& ev : h->h2d_done) if (ev) (void)hipEventDestroy(ev);
-  h->release_work();
+  for (auto& w : h->work) w.release();
   h->post_stage.release();
   if (h->pol_stats) (void)hipFree(h->pol_stats);
   delete h;
@@ -485,8 +464,7 @@ int schedule_launch(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route&
   if (!no_queue || want_order) {
     // scheduling buffer of this stream: [0] the queue counter (its own 256-byte line), then keys[B], order[B]
     const size_t need = 256 + (want_order ? (size_t)p->batch * 2 * sizeof(int32_t) : 0);
-    if (need > wk->ord.cap) HIP_TRY(hipStreamSynchronize(st));   // an earlier launch on this stream may still read the old one
-    HIP_TRY(wk->ord.reserve(need));
+    HIP_TRY(reserve_behind(st, {{&wk->ord, need}}));
     if (!no_queue) {
       a->queue = static_cast<int32_t*>(wk->ord.p);
       HIP_TRY(hipMemsetAsync(a->queue, 0, sizeof(int32_t), st));
@@ -517,8 +495,7 @@ int reserve_workspace(acnqp_handle::Work* wk, const acnqp::Route& rt, hipStream_
   if (rt.stream || rt.lng) a->accel_mem = std::min(a->accel_mem, rt.accel_cap<Kernels>());
   ws->per_problem = rt.workspace_doubles<Kernels>(a->accel_mem);
   const size_t need = (size_t)ws->per_problem * a->grid_cap * sizeof(double);
-  if (need > wk->buf.cap) HIP_TRY(hipStreamSynchronize(st));   // an earlier launch on this stream may still use the old buffer
-  HIP_TRY(wk->buf.reserve(need));
+  HIP_TRY(reserve_behind(st, {{&wk->buf, need}}));
   ws->p = wk->buf.p;
   return ACNQP_OK;
 }
@@ -618,8 +595,7 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   const size_t ybytes = r->y ? 0 : (size_t)p->batch * s.Mg * p->t_max * sizeof(double);
   const size_t lbytes = ((size_t)p->batch * sizeof(int32_t) + 255) & ~(size_t)255;
   const size_t need = 256 + lbytes + ybytes;
-  if (need > wk->pol.cap) HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(wk->pol.reserve(need));
+  HIP_TRY(reserve_behind(st, {{&wk->pol, need}}));
   int32_t* ctr = static_cast<int32_t*>(wk->pol.p);
   int32_t* list = ctr + 64;
   double* ybuf = r->y ? r->y : reinterpret_cast<double*>(static_cast<char*>(wk->pol.p) + 256 + lbytes);

@@ -3,52 +3,158 @@
 // ONE planner, ONE chunk loop and ONE epilogue for both entries; they differ in how a chunk's inputs reach the device
 // (fill_dense / fill_table) and in nothing else.
 //
-// Part 1 (chunk layout and planner) is plain host code: tests/test_route_table.py compiles it with the host compiler.
+// Part 1 (the tables of a chunk's arrays and of the session-table staging, their layouts, the planner) is plain host
+// code: tests/test_chunk_layout.py and tests/test_route_table.py compile it with the host compiler.
 // Part 2 (the kernels of this unit, the chunk loop) belongs to the API translation unit: acn_qp_api.hip includes this
 // file after acnqp_handle, fail() and HIP_TRY.
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <vector>
+
+#include "acn_qp.h"
+
+namespace {
+// the arguments of table_expand_kernel (Part 2); up here because the staging table of Part 1 names its pointer members
+struct TableExpandArgs {
+  int N, Tm, K;
+  long long s_base, r_base;          // first session / rate entry of the chunk (the segment arrays hold global indices)
+  const int32_t *q_index, *sess_seg, *s_evse, *s_slot, *s_off, *s_len, *rate_seg;
+  const double *q_table, *s_cap, *min_rates, *max_rates;
+  double *lb, *ub, *q, *sc;
+  int32_t *so, *sl;
+};
+}  // namespace
 
 namespace acnqp {
 
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// device layout of one chunk of `cn` problems (inputs in slot.in, results in slot.out)
+// ---- the arrays of a chunk: ONE table ----------------------------------------------------------------------------------
+// A chunk of `cn` problems carries 16 input arrays (slot.in) and 7 result arrays (slot.out).  Each is one row below, and
+// the layout, the device views, the copies in and out and the scatter of the small results all walk the rows: a new
+// array is one row (and its name in the enum).  Rows stand in DEVICE order, every array on a 256-byte line.
+struct ChunkShape { size_t N, Tm, K, Mg; bool peak, flat, max, warm, want_y, direct; };
+enum class Per : uint8_t { One, NT, KN, T, MgT };                          // elements per problem
+enum class When : uint8_t { Always, Peak, Flat, Max, Warm, WantY, Direct };  // the shapes that have the array
+// Large: a copy per piece.  Small: rides in the call's pinned mirror, ONE copy per chunk and side (run_call), so the small
+// rows of a side must stand together (static_assert below).
+enum class Size : uint8_t { Large, Small };
+constexpr size_t kNoField = ~(size_t)0;   // an array the library makes itself: no member of the ABI struct
+struct ArrayRow { size_t field; uint8_t elem; Per per; When when; Size size; };   // field: offsetof in acnqp_problems / acnqp_results
+
+enum In { kLb, kUb, kQ, kPd, kHz, kSo, kSl, kSc, kEq, kPk, kLf, kDc, kDf, kXh, kWx, kWy, kInRows };
+enum Out { kX, kSt, kIt, kPr, kDu, kOb, kY, kOutRows };
+constexpr ArrayRow kIn[kInRows] = {
+    {offsetof(acnqp_problems, lb), 8, Per::NT, When::Always, Size::Large},
+    {offsetof(acnqp_problems, ub), 8, Per::NT, When::Always, Size::Large},
+    {offsetof(acnqp_problems, q), 8, Per::NT, When::Always, Size::Large},
+    {offsetof(acnqp_problems, pdiag), 8, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_problems, horizon), 4, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_problems, s_off), 4, Per::KN, When::Always, Size::Small},
+    {offsetof(acnqp_problems, s_len), 4, Per::KN, When::Always, Size::Small},
+    {offsetof(acnqp_problems, s_cap), 8, Per::KN, When::Always, Size::Small},
+    {offsetof(acnqp_problems, s_eq), 1, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_problems, peak), 8, Per::T, When::Peak, Size::Small},
+    {offsetof(acnqp_problems, lf), 8, Per::One, When::Flat, Size::Small},
+    {offsetof(acnqp_problems, dc), 8, Per::One, When::Max, Size::Small},
+    {offsetof(acnqp_problems, dfloor), 8, Per::One, When::Max, Size::Small},
+    // xh, the direct path: where the kernel stores each problem's schedule (one double* per problem, filled by fill_dense)
+    {kNoField, sizeof(double*), Per::One, When::Direct, Size::Small},
+    {offsetof(acnqp_problems, warm_x), 8, Per::NT, When::Warm, Size::Large},
+    {offsetof(acnqp_problems, warm_y), 8, Per::MgT, When::Warm, Size::Large},
+};
+constexpr ArrayRow kOut[kOutRows] = {   // (acnqp_results::x_dev is a destination of x, not an array of the chunk)
+    {offsetof(acnqp_results, x), 8, Per::NT, When::Always, Size::Large},
+    {offsetof(acnqp_results, status), 4, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_results, iters), 4, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_results, pri_res), 8, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_results, dua_res), 8, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_results, obj), 8, Per::One, When::Always, Size::Small},
+    {offsetof(acnqp_results, y), 8, Per::MgT, When::WantY, Size::Large},
+};
+
+constexpr bool present(const ArrayRow& r, const ChunkShape& s) {
+  const bool on[] = {true, s.peak, s.flat, s.max, s.warm, s.want_y, s.direct};   // (the order of When)
+  return on[(int)r.when];
+}
+constexpr size_t bytes_per_problem(const ArrayRow& r, const ChunkShape& s) {
+  const size_t n[] = {1, s.N * s.Tm, s.K * s.N, s.Tm, s.Mg * s.Tm};   // (the order of Per)
+  return r.elem * n[(int)r.per];
+}
+// the small rows of a side: [first, end), or {n, n} if they do not stand together
+struct RowRange { int first, end; };
+constexpr RowRange small_rows(const ArrayRow* rows, int n) {
+  int first = 0, end = 0;
+  while (first < n && rows[first].size != Size::Small) ++first;
+  for (end = first; end < n && rows[end].size == Size::Small;) ++end;
+  for (int k = end; k < n; ++k)
+    if (rows[k].size == Size::Small) return {n, n};
+  return {first, end};
+}
+constexpr RowRange kSmallIn = small_rows(kIn, kInRows), kSmallOut = small_rows(kOut, kOutRows);
+static_assert(kSmallIn.first < kSmallIn.end && kSmallOut.first < kSmallOut.end, "the small rows of a side are one contiguous run: the pinned mirror is one copy");
+
+// device layout of one chunk of `cn` problems: in[k] / out[k] is where row k starts in slot.in / slot.out, in[kInRows] /
+// out[kOutRows] the bytes of the side; an array the shape does not have takes no bytes
 struct ChunkLayout {
-  size_t lb, ub, q, pd, hz, so, sl, sc, eq, pk, lf, dc, df, xh, wx, wy, in_total;
-  size_t x, st, it, pr, du, ob, y, out_total;
-  // direct: the chunk carries the host destinations of its problems' schedules (xh: one double* per problem, a small input)
-  ChunkLayout(size_t cn, size_t N, size_t Tm, size_t K, size_t Mg, bool peak, bool flat, bool mx, bool warm, bool want_y, bool direct = false) {
-    size_t o = 0;
-    lb = o; o += al256(cn * N * Tm * 8);
-    ub = o; o += al256(cn * N * Tm * 8);
-    q = o;  o += al256(cn * N * Tm * 8);
-    pd = o; o += al256(cn * 8);
-    hz = o; o += al256(cn * 4);
-    so = o; o += al256(cn * K * N * 4);
-    sl = o; o += al256(cn * K * N * 4);
-    sc = o; o += al256(cn * K * N * 8);
-    eq = o; o += al256(cn);
-    pk = o; o += al256(peak ? cn * Tm * 8 : 0);
-    lf = o; o += al256(flat ? cn * 8 : 0);
-    dc = o; o += al256(mx ? cn * 8 : 0);
-    df = o; o += al256(mx ? cn * 8 : 0);
-    xh = o; o += al256(direct ? cn * sizeof(double*) : 0);
-    wx = o; o += al256(warm ? cn * N * Tm * 8 : 0);
-    wy = o; o += al256(warm ? cn * Mg * Tm * 8 : 0);
-    in_total = o;
-    o = 0;
-    x = o;  o += al256(cn * N * Tm * 8);
-    st = o; o += al256(cn * 4);
-    it = o; o += al256(cn * 4);
-    pr = o; o += al256(cn * 8);
-    du = o; o += al256(cn * 8);
-    ob = o; o += al256(cn * 8);
-    y = o;  o += al256(want_y ? cn * Mg * Tm * 8 : 0);
-    out_total = o;
+  ChunkShape shape;
+  size_t cn, in[kInRows + 1], out[kOutRows + 1];
+  bool direct;   // the chunk carries the host destinations of its problems' schedules (kXh)
+  ChunkLayout(size_t cn_, const ChunkShape& s) : shape(s), cn(cn_), direct(s.direct) {
+    auto lay = [&](const ArrayRow* rows, int n, size_t* off) {
+      off[0] = 0;
+      for (int k = 0; k < n; ++k) off[k + 1] = off[k] + al256(present(rows[k], s) ? cn * bytes_per_problem(rows[k], s) : 0);
+    };
+    lay(kIn, kInRows, in);
+    lay(kOut, kOutRows, out);
+  }
+  // the device ranges that the pinned mirrors shadow: the small rows of each side
+  size_t mirror_in() const { return in[kSmallIn.first]; }
+  size_t mirror_in_bytes() const { return in[kSmallIn.end] - in[kSmallIn.first]; }
+  size_t mirror_out() const { return out[kSmallOut.first]; }
+  size_t mirror_out_bytes() const { return out[kSmallOut.end] - out[kSmallOut.first]; }
+};
+
+// ---- the session-table staging: ONE table -------------------------------------------------------------------------------
+// What fill_table uploads into slot.tin for the chunk of problems [lo, lo + cn): their ns sessions from s0 on and those
+// sessions' nr rate entries from r0 on (sess_seg / rate_seg hold global indices), and the whole q_table.
+struct TableSpan { long long lo = 0, cn = 0, s0 = 0, ns = 0, r0 = 0, nr = 0; size_t qt = 0; };   // qt: elements of q_table, H N Tm
+enum class Count : uint8_t { Cn, Cn1, Ns, Ns1, Nr, Qt };
+enum class Base : uint8_t { Lo, S0, R0, Zero };
+struct TableRow { size_t field, arg; uint8_t elem; Count count; Base base; };   // field: offsetof in acnqp_table, arg: in TableExpandArgs
+#define ACNQP_T(f) offsetof(acnqp_table, f), offsetof(TableExpandArgs, f)   // (the two structs name an array alike)
+constexpr TableRow kTable[] = {
+    {ACNQP_T(q_index), 4, Count::Cn, Base::Lo},
+    {ACNQP_T(sess_seg), 4, Count::Cn1, Base::Lo},
+    {ACNQP_T(s_evse), 4, Count::Ns, Base::S0},
+    {ACNQP_T(s_slot), 4, Count::Ns, Base::S0},
+    {ACNQP_T(s_off), 4, Count::Ns, Base::S0},
+    {ACNQP_T(s_len), 4, Count::Ns, Base::S0},
+    {ACNQP_T(rate_seg), 4, Count::Ns1, Base::S0},
+    {ACNQP_T(s_cap), 8, Count::Ns, Base::S0},
+    {ACNQP_T(min_rates), 8, Count::Nr, Base::R0},
+    {ACNQP_T(max_rates), 8, Count::Nr, Base::R0},
+    {ACNQP_T(q_table), 8, Count::Qt, Base::Zero},
+};
+#undef ACNQP_T
+constexpr int kTableRows = (int)(sizeof(kTable) / sizeof(kTable[0]));
+constexpr size_t table_count(const TableRow& r, const TableSpan& s) {   // elements uploaded ...
+  const size_t n[] = {(size_t)s.cn, (size_t)s.cn + 1, (size_t)s.ns, (size_t)s.ns + 1, (size_t)s.nr, s.qt};
+  return n[(int)r.count];
+}
+constexpr size_t table_base(const TableRow& r, const TableSpan& s) {   // ... from this element of the caller's array on
+  const long long at[] = {s.lo, s.s0, s.r0, 0};
+  return (size_t)at[(int)r.base];
+}
+struct TableLayout {
+  TableSpan span;
+  size_t off[kTableRows] = {}, total = 0;
+  TableLayout() = default;   // (dense entry: no table staging)
+  explicit TableLayout(const TableSpan& s) : span(s) {
+    for (int k = 0; k < kTableRows; ++k) { off[k] = total; total += al256(table_count(kTable[k], s) * kTable[k].elem); }
   }
 };
 
@@ -64,6 +170,8 @@ struct PlanEnv {
 
 // inputs + results staged per problem -- every one of the kSlots pipeline slots holds a chunk of each, so a chunk is
 // capped at 1 GiB of the sum.  (The kernels' workspaces belong to the resident workgroup slots: no per-problem term.)
+// The formula APPROXIMATES the byte sum of the table above (lb, ub, q, x; the session slots; peak; 96 bytes of scalars) and
+// ignores the warm-start and y arrays.  Kept, not derived from the table: its values are the chunk sizes (test_route_table.py).
 inline long long chunk_cap_by_memory(size_t N, size_t Tm, size_t K) {
   const size_t per_problem = 4 * N * Tm * 8 + K * N * 16 + Tm * 8 + 96;
   return (long long)((size_t)1024 * 1024 * 1024 / std::max<size_t>(per_problem, 1));
@@ -140,8 +248,7 @@ inline long long chunk_cap(const std::vector<long long>& caps, size_t c) { retur
 
 namespace {
 
-using acnqp::al256;
-using acnqp::ChunkLayout;
+using namespace acnqp;   // the tables of Part 1
 
 // ---- launch order: longest expected problem first -------------------------------------------------------------------
 // A launch of B problems on S resident workgroup slots ends with its slowest slot; the hardware hands workgroups out in
@@ -277,15 +384,6 @@ __global__ __launch_bounds__(kOrderKeys) void order_sort_kernel(const int32_t* k
 }
 
 // ---- session-table entry: the dense problem arrays are formed on the device ---------------------------------------------
-struct TableExpandArgs {
-  int N, Tm, K;
-  long long s_base, r_base;          // first session / rate entry of the chunk (the segment arrays hold global indices)
-  const int32_t *q_index, *sess_seg, *s_evse, *s_slot, *s_off, *s_len, *rate_seg;
-  const double *q_table, *s_cap, *min_rates, *max_rates;
-  double *lb, *ub, *q, *sc;
-  int32_t *so, *sl;
-};
-
 // One workgroup per problem of the chunk: zero its bounds and session slots, copy its horizon's linear cost, then
 // scatter its sessions -- lb / ub over the window (aco.py:62-75, ub < lb -> lb) and (offset, length, cap) into the
 // EVSE's slot (aco.py:105-123).  Windows of one EVSE are disjoint: no two sessions write one entry.
@@ -314,36 +412,12 @@ __global__ __launch_bounds__(256) void table_expand_kernel(const TableExpandArgs
   }
 }
 
-// table staging of the chunk of problems [lo, lo + cn): q_index[cn], sess_seg[cn + 1], {evse, slot, off, len}[ns],
-// rate_seg[ns + 1], s_cap[ns], min / max [nr], q_table
-struct TableLayout {
-  long long s0 = 0, ns = 0, r0 = 0, nr = 0;
-  size_t qi = 0, sg = 0, ev = 0, sl = 0, of = 0, ln = 0, rs = 0, cp = 0, mn = 0, mxr = 0, qt = 0, total = 0;
-  TableLayout() = default;   // (dense entry: no table staging)
-  TableLayout(const acnqp_table* T, long long lo, long long cn, size_t nv) {
-    s0 = T->sess_seg[lo]; ns = T->sess_seg[lo + cn] - s0;
-    r0 = T->rate_seg[s0]; nr = T->rate_seg[s0 + ns] - r0;
-    size_t o = 0;
-    qi = o; o += al256((size_t)cn * 4);
-    sg = o; o += al256((size_t)(cn + 1) * 4);
-    ev = o; o += al256((size_t)ns * 4);
-    sl = o; o += al256((size_t)ns * 4);
-    of = o; o += al256((size_t)ns * 4);
-    ln = o; o += al256((size_t)ns * 4);
-    rs = o; o += al256((size_t)(ns + 1) * 4);
-    cp = o; o += al256((size_t)ns * 8);
-    mn = o; o += al256((size_t)nr * 8);
-    mxr = o; o += al256((size_t)nr * 8);
-    qt = o; o += al256((size_t)T->n_horizons * nv * 8);
-    total = o;
-  }
-};
-
 // ---- a call and its chunks ---------------------------------------------------------------------------------------------
 struct BatchShape { long long batch; int t_max, k_sessions; bool warm, want_y; };
 struct Piece { int g; long long lo, n, pos; };   // problems [lo, lo + n) of batch g sit at [pos, pos + n) of their chunk
-// what the caller's small result arrays still need after the streams have drained: a copy out of the pinned mirror
-struct Scatter { int g; size_t lo, n, pos; const char* host; size_t st, it, pr, du, ob; };
+// what the caller's small result arrays still need after the streams have drained, a copy out of the pinned mirror: the
+// piece, its chunk, and the mirror base (host + layout[c].out[k] is the mirror of row k)
+struct Scatter { Piece pc; size_t c; const char* host; };
 
 // one call of a host-buffer entry: dense batches P[nb] (acnqp_solve_batches) or ONE session table T (acnqp_solve_table)
 struct Call {
@@ -351,6 +425,7 @@ struct Call {
   const acnqp_table* T = nullptr;
   acnqp_results* R = nullptr;      // [nb]; the table's one
   std::vector<BatchShape> bs;
+  std::vector<ChunkLayout> layout; // [chunk], as run_call reaches them
   std::vector<Scatter> scatter;    // dense entry with staged small arrays
   std::vector<double*> xdst;       // [nb] the direct path: R[g].x as the device addresses it (null: batch g keeps its copies)
 };
@@ -359,7 +434,7 @@ struct Call {
 // A result array x in device-addressable host memory (pinned: acnqp_host_alloc, hipHostMalloc, hipHostRegister) is written
 // by the kernel itself where the route can do that (Route::direct_x; TiledArgs::x_host): the wave that gives a problem
 // its verdict stores the schedule there, pol_x_to_host_kernel (acn_qp_api.hip) those of the handed-over problems, and the
-// chunk loop queues no copy of x.  The destinations ride with the chunk's small inputs (ChunkLayout::xh), so only the
+// chunk loop queues no copy of x.  The destinations ride with the chunk's small inputs (row kXh), so only the
 // dense entry with its pinned mirrors takes the path.  Pageable and device arrays keep their copies; a call may mix both.
 // ACNQP_NO_DIRECT_X=1 (diagnostic, read once per process): the copy path everywhere.
 double* direct_destination(const double* x) {
@@ -373,33 +448,18 @@ double* direct_destination(const double* x) {
   return at.type == hipMemoryTypeHost ? static_cast<double*>(at.devicePointer) : nullptr;
 }
 
-// the device-side view of a chunk of cn problems laid out by L in a slot's staging (di: inputs, dq: results)
-void device_views(const ChunkLayout& L, char* di, char* dq, const acnqp::SiteShape& s, size_t cn, const BatchShape& b,
-                  acnqp_problems* dp, acnqp_results* dr) {
-  dp->batch = (int32_t)cn; dp->t_max = b.t_max; dp->k_sessions = b.k_sessions;
-  dp->lb = reinterpret_cast<const double*>(di + L.lb);
-  dp->ub = reinterpret_cast<const double*>(di + L.ub);
-  dp->q = reinterpret_cast<const double*>(di + L.q);
-  dp->pdiag = reinterpret_cast<const double*>(di + L.pd);
-  dp->horizon = reinterpret_cast<const int32_t*>(di + L.hz);
-  dp->s_off = reinterpret_cast<const int32_t*>(di + L.so);
-  dp->s_len = reinterpret_cast<const int32_t*>(di + L.sl);
-  dp->s_cap = reinterpret_cast<const double*>(di + L.sc);
-  dp->s_eq = reinterpret_cast<const uint8_t*>(di + L.eq);
-  dp->peak = s.has_peak ? reinterpret_cast<const double*>(di + L.pk) : nullptr;
-  dp->lf = s.has_flat ? reinterpret_cast<const double*>(di + L.lf) : nullptr;
-  dp->dc = s.has_max ? reinterpret_cast<const double*>(di + L.dc) : nullptr;
-  dp->dfloor = s.has_max ? reinterpret_cast<const double*>(di + L.df) : nullptr;
-  dp->warm_x = b.warm ? reinterpret_cast<const double*>(di + L.wx) : nullptr;
-  dp->warm_y = b.warm ? reinterpret_cast<const double*>(di + L.wy) : nullptr;
-  dr->x = reinterpret_cast<double*>(dq + L.x);
-  dr->status = reinterpret_cast<int32_t*>(dq + L.st);
-  dr->iters = reinterpret_cast<int32_t*>(dq + L.it);
-  dr->pri_res = reinterpret_cast<double*>(dq + L.pr);
-  dr->dua_res = reinterpret_cast<double*>(dq + L.du);
-  dr->obj = reinterpret_cast<double*>(dq + L.ob);
+// the pointer member at byte `field` of an ABI struct (every member the tables name is a pointer to objects)
+inline char* member(const void* s, size_t field) { char* p; std::memcpy(&p, static_cast<const char*>(s) + field, sizeof p); return p; }
+inline void set_member(void* s, size_t field, const void* p) { std::memcpy(static_cast<char*>(s) + field, &p, sizeof p); }
+
+// the device-side view of the chunk laid out by L in a slot's staging (di: inputs, dq: results); null for an array the
+// chunk's shape does not have
+void device_views(const ChunkLayout& L, char* di, char* dq, const BatchShape& b, acnqp_problems* dp, acnqp_results* dr) {
+  dp->batch = (int32_t)L.cn; dp->t_max = b.t_max; dp->k_sessions = b.k_sessions;
+  for (int k = 0; k < kInRows; ++k)
+    if (kIn[k].field != kNoField) set_member(dp, kIn[k].field, present(kIn[k], L.shape) ? di + L.in[k] : nullptr);
+  for (int k = 0; k < kOutRows; ++k) set_member(dr, kOut[k].field, present(kOut[k], L.shape) ? dq + L.out[k] : nullptr);
   dr->x_dev = nullptr;
-  dr->y = b.want_y ? reinterpret_cast<double*>(dq + L.y) : nullptr;
 }
 
 // chunks: consecutive batches of one shape (t_max, k_sessions) and one set of optional arrays (warm start, multiplier
@@ -440,94 +500,69 @@ std::vector<std::vector<Piece>> split_call(const acnqp_handle* h, const std::vec
 }
 
 // ---- fill: a chunk's inputs reach the slot's staging ------------------------------------------------------------------------
+// Problems [lo, lo + n) of the host arrays `src` to [pos, pos + n) of the chunk, row by row: a large row is a copy on st,
+// a small row goes into the pinned mirror hs (hs + L.in[k] mirrors di + L.in[k]; null: no mirror, a copy each).  A row
+// without a source (kXh; the arrays that table_expand_kernel forms) is not the caller's to copy.
+hipError_t upload_piece(const ChunkLayout& L, const acnqp_problems& src, size_t lo, size_t n, size_t pos, char* di, char* hs, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < kInRows && e == hipSuccess; ++k) {
+    const char* from = kIn[k].field != kNoField && present(kIn[k], L.shape) ? member(&src, kIn[k].field) : nullptr;
+    if (!from) continue;
+    const size_t per = bytes_per_problem(kIn[k], L.shape);
+    if (hs && kIn[k].size == Size::Small) std::memcpy(hs + L.in[k] + pos * per, from + lo * per, n * per);
+    else e = hipMemcpyAsync(di + L.in[k] + pos * per, from + lo * per, n * per, hipMemcpyHostToDevice, st);
+  }
+  return e;
+}
+
 // Dense entry: the large arrays piece by piece, the small ones through the call's pinned mirror (hs; one H2D per chunk)
 // or, without staging, a copy each; the chunks' input copies queue one chunk after the other (they share the link anyway:
 // the first kernel's inputs do not wait for a share of the bandwidth the second chunk's copies would take).
 int fill_dense(acnqp_handle* h, const Call& call, size_t c, const std::vector<Piece>& pcs, const ChunkLayout& L,
                acnqp_handle::Slot& S, char* hs) {
-  const acnqp::SiteShape& s = h->shape;
-  const BatchShape& b = call.bs[pcs[0].g];
-  const size_t N = s.N, Tm = b.t_max, K = b.k_sessions, Mg = s.Mg, nv = N * Tm, ns = K * N;
   char* di = static_cast<char*>(S.in.p);
   static const bool chain = std::getenv("ACNQP_NO_H2D_CHAIN") == nullptr;
   if (chain && c > 0) HIP_TRY(hipStreamWaitEvent(S.st, h->h2d_done[(c - 1) % acnqp_handle::kSlots], 0));
   for (const Piece& pc : pcs) {
-    const acnqp_problems& p = call.P[pc.g];
     const size_t lo = (size_t)pc.lo, n = (size_t)pc.n, pos = (size_t)pc.pos;
-#define H2D(field, base, elem, per)                                                                             \
-  HIP_TRY(hipMemcpyAsync(di + (base) + pos * (per) * (elem), reinterpret_cast<const char*>(p.field) + lo * (per) * (elem), \
-                         n * (per) * (elem), hipMemcpyHostToDevice, S.st))
-// small arrays: into the pinned mirror (one H2D per chunk below); without staging, a copy each
-#define H2S(field, base, elem, per)                                                                             \
-  do {                                                                                                          \
-    if (hs) std::memcpy(hs + (base) + pos * (per) * (elem), reinterpret_cast<const char*>(p.field) + lo * (per) * (elem), n * (per) * (elem)); \
-    else H2D(field, base, elem, per);                                                                           \
-  } while (0)
-    H2D(lb, L.lb, 8, nv);
-    H2D(ub, L.ub, 8, nv);
-    H2D(q, L.q, 8, nv);
-    H2S(pdiag, L.pd, 8, 1);
-    H2S(horizon, L.hz, 4, 1);
-    H2S(s_off, L.so, 4, ns);
-    H2S(s_len, L.sl, 4, ns);
-    H2S(s_cap, L.sc, 8, ns);
-    H2S(s_eq, L.eq, 1, 1);
-    if (s.has_peak) H2S(peak, L.pk, 8, Tm);
-    if (s.has_flat) H2S(lf, L.lf, 8, 1);
-    if (s.has_max) { H2S(dc, L.dc, 8, 1); H2S(dfloor, L.df, 8, 1); }
-    if (b.warm) { H2D(warm_x, L.wx, 8, nv); H2D(warm_y, L.wy, 8, Mg * Tm); }
-    if (hs && L.xh != L.wx) {   // a direct chunk: where the kernel stores each problem's schedule (null: this piece is copied)
-      double** tab = reinterpret_cast<double**>(hs + L.xh) + pos;
+    HIP_TRY(upload_piece(L, call.P[pc.g], lo, n, pos, di, hs, S.st));
+    if (hs && L.direct) {   // where the kernel stores each problem's schedule (null: this piece is copied)
+      double** tab = reinterpret_cast<double**>(hs + L.in[kXh]) + pos;
       double* const dst = call.xdst[pc.g];
-      for (size_t i = 0; i < n; ++i) tab[i] = dst ? dst + (lo + i) * nv : nullptr;
+      for (size_t i = 0; i < n; ++i) tab[i] = dst ? dst + (lo + i) * L.shape.N * L.shape.Tm : nullptr;
     }
-#undef H2S
-#undef H2D
   }
-  if (hs) HIP_TRY(hipMemcpyAsync(di + L.pd, hs + L.pd, L.wx - L.pd, hipMemcpyHostToDevice, S.st));
+  if (hs) HIP_TRY(hipMemcpyAsync(di + L.mirror_in(), hs + L.mirror_in(), L.mirror_in_bytes(), hipMemcpyHostToDevice, S.st));
   if (chain) HIP_TRY(hipEventRecord(h->h2d_done[c % acnqp_handle::kSlots], S.st));
   return ACNQP_OK;
 }
 
-// Table entry: the chunk's slice of the session table into slot.tin, then table_expand_kernel forms lb, ub, q and the
-// session slots in slot.in.
-int fill_table(acnqp_handle* h, const Call& call, const Piece& pc, const ChunkLayout& L, const TableLayout& TL, acnqp_handle::Slot& S) {
-  const acnqp::SiteShape& s = h->shape;
+// the chunk of problems [lo, lo + cn) of a session table: its sessions and their rate entries
+TableSpan table_span(const acnqp_table* T, long long lo, long long cn, size_t nv) {
+  const long long s0 = T->sess_seg[lo], ns = T->sess_seg[lo + cn] - s0, r0 = T->rate_seg[s0], nr = T->rate_seg[s0 + ns] - r0;
+  return TableSpan{lo, cn, s0, ns, r0, nr, (size_t)T->n_horizons * nv};
+}
+
+// Table entry: the per-problem arrays that the table has (a copy each), the chunk's slice of the session table into
+// slot.tin, then table_expand_kernel forms lb, ub, q and the session slots in slot.in.
+int fill_table(const Call& call, const Piece& pc, const ChunkLayout& L, const TableLayout& TL, acnqp_handle::Slot& S) {
   const acnqp_table* T = call.T;
-  const size_t N = s.N, Tm = T->t_max, K = T->k_sessions, nv = N * Tm;
-  const long long lo = pc.lo, cn = pc.n, s0 = TL.s0, ns = TL.ns, r0 = TL.r0, nr = TL.nr;
   char* di = static_cast<char*>(S.in.p);
   char* dt = static_cast<char*>(S.tin.p);
-#define TH2D(dst, src, bytes) do { if ((bytes) > 0) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, S.st)); } while (0)
-  TH2D(di + L.hz, T->horizon + lo, (size_t)cn * 4);
-  TH2D(di + L.pd, T->pdiag + lo, (size_t)cn * 8);
-  TH2D(di + L.eq, T->s_eq + lo, (size_t)cn);
-  if (s.has_peak) TH2D(di + L.pk, T->peak + lo * Tm, (size_t)cn * Tm * 8);
-  if (s.has_flat) TH2D(di + L.lf, T->lf + lo, (size_t)cn * 8);
-  if (s.has_max) { TH2D(di + L.dc, T->dc + lo, (size_t)cn * 8); TH2D(di + L.df, T->dfloor + lo, (size_t)cn * 8); }
-  TH2D(dt + TL.qi, T->q_index + lo, (size_t)cn * 4);
-  TH2D(dt + TL.sg, T->sess_seg + lo, (size_t)(cn + 1) * 4);
-  TH2D(dt + TL.ev, T->s_evse + s0, (size_t)ns * 4);
-  TH2D(dt + TL.sl, T->s_slot + s0, (size_t)ns * 4);
-  TH2D(dt + TL.of, T->s_off + s0, (size_t)ns * 4);
-  TH2D(dt + TL.ln, T->s_len + s0, (size_t)ns * 4);
-  TH2D(dt + TL.rs, T->rate_seg + s0, (size_t)(ns + 1) * 4);
-  TH2D(dt + TL.cp, T->s_cap + s0, (size_t)ns * 8);
-  TH2D(dt + TL.mn, T->min_rates + r0, (size_t)nr * 8);
-  TH2D(dt + TL.mxr, T->max_rates + r0, (size_t)nr * 8);
-  TH2D(dt + TL.qt, T->q_table, (size_t)T->n_horizons * nv * 8);
-#undef TH2D
+  acnqp_problems src = {};
+  src.horizon = T->horizon; src.pdiag = T->pdiag; src.s_eq = T->s_eq; src.peak = T->peak; src.lf = T->lf; src.dc = T->dc; src.dfloor = T->dfloor;
+  HIP_TRY(upload_piece(L, src, (size_t)pc.lo, (size_t)pc.n, 0, di, nullptr, S.st));
   TableExpandArgs ea;
-  ea.N = (int)N; ea.Tm = (int)Tm; ea.K = (int)K; ea.s_base = s0; ea.r_base = r0;
-  ea.q_index = reinterpret_cast<const int32_t*>(dt + TL.qi); ea.sess_seg = reinterpret_cast<const int32_t*>(dt + TL.sg);
-  ea.s_evse = reinterpret_cast<const int32_t*>(dt + TL.ev); ea.s_slot = reinterpret_cast<const int32_t*>(dt + TL.sl);
-  ea.s_off = reinterpret_cast<const int32_t*>(dt + TL.of); ea.s_len = reinterpret_cast<const int32_t*>(dt + TL.ln);
-  ea.rate_seg = reinterpret_cast<const int32_t*>(dt + TL.rs); ea.q_table = reinterpret_cast<const double*>(dt + TL.qt);
-  ea.s_cap = reinterpret_cast<const double*>(dt + TL.cp); ea.min_rates = reinterpret_cast<const double*>(dt + TL.mn);
-  ea.max_rates = reinterpret_cast<const double*>(dt + TL.mxr);
-  ea.lb = reinterpret_cast<double*>(di + L.lb); ea.ub = reinterpret_cast<double*>(di + L.ub); ea.q = reinterpret_cast<double*>(di + L.q);
-  ea.so = reinterpret_cast<int32_t*>(di + L.so); ea.sl = reinterpret_cast<int32_t*>(di + L.sl); ea.sc = reinterpret_cast<double*>(di + L.sc);
-  hipLaunchKernelGGL(table_expand_kernel, dim3((unsigned)cn), dim3(256), 0, S.st, ea);
+  for (int k = 0; k < kTableRows; ++k) {
+    const TableRow& r = kTable[k];
+    const size_t bytes = table_count(r, TL.span) * r.elem;
+    if (bytes > 0) HIP_TRY(hipMemcpyAsync(dt + TL.off[k], member(T, r.field) + table_base(r, TL.span) * r.elem, bytes, hipMemcpyHostToDevice, S.st));
+    set_member(&ea, r.arg, dt + TL.off[k]);
+  }
+  ea.N = (int)L.shape.N; ea.Tm = (int)L.shape.Tm; ea.K = (int)L.shape.K; ea.s_base = TL.span.s0; ea.r_base = TL.span.r0;
+  ea.lb = reinterpret_cast<double*>(di + L.in[kLb]); ea.ub = reinterpret_cast<double*>(di + L.in[kUb]); ea.q = reinterpret_cast<double*>(di + L.in[kQ]);
+  ea.so = reinterpret_cast<int32_t*>(di + L.in[kSo]); ea.sl = reinterpret_cast<int32_t*>(di + L.in[kSl]); ea.sc = reinterpret_cast<double*>(di + L.in[kSc]);
+  hipLaunchKernelGGL(table_expand_kernel, dim3((unsigned)pc.n), dim3(256), 0, S.st, ea);
   return ACNQP_OK;
 }
 
@@ -561,21 +596,21 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
   auto layout = [&](size_t c) {
     const std::vector<Piece>& pcs = chunks[c];
     const BatchShape& b = call.bs[pcs[0].g];
-    return ChunkLayout((size_t)(pcs.back().pos + pcs.back().n), N, b.t_max, b.k_sessions, Mg, s.has_peak, s.has_flat, s.has_max, b.warm, b.want_y,
-                       direct[c] != 0);
+    return ChunkLayout((size_t)(pcs.back().pos + pcs.back().n),
+                       ChunkShape{N, (size_t)b.t_max, (size_t)b.k_sessions, Mg, s.has_peak != 0, s.has_flat != 0, s.has_max != 0, b.warm, b.want_y, direct[c] != 0});
   };
-  // Dense entry only: pinned mirrors of the chunks' SMALL arrays (device ranges [pd, wx) and [st, y) of ChunkLayout),
-  // whole call -- one H2D and one D2H per chunk instead of nine and five per piece; beyond kSmallCap the per-batch copies
-  // of old (a call that large is not bound by their latency).  The table entry has neither the mirrors nor the H2D chain
-  // of fill_dense: its small arrays keep a copy each, and it records and waits on no h2d_done event.  Giving it either
+  // Dense entry only: pinned mirrors of the chunks' SMALL arrays (ChunkLayout::mirror_in / mirror_out: the small rows of
+  // the table), whole call -- one H2D and one D2H per chunk instead of nine and five per piece; beyond kSmallCap the per-batch
+  // copies of old (a call that large is not bound by their latency).  The table entry has neither the mirrors nor the H2D
+  // chain of fill_dense: its small arrays keep a copy each, and it records and waits on no h2d_done event.  Giving it either
   // would change its speed, not its structure -- a change of its own, to be measured on its own.
   constexpr size_t kSmallCap = (size_t)256 << 20;
   std::vector<size_t> in_off(chunks.size()), out_off(chunks.size());
   size_t in_sum = 0, out_sum = 0;
   for (size_t c = 0; c < chunks.size() && !table; ++c) {
     const ChunkLayout L = layout(c);
-    in_off[c] = in_sum; in_sum += L.wx - L.pd;
-    out_off[c] = out_sum; out_sum += L.y - L.st;
+    in_off[c] = in_sum; in_sum += L.mirror_in_bytes();
+    out_off[c] = out_sum; out_sum += L.mirror_out_bytes();
   }
   static const bool no_stage = std::getenv("ACNQP_NO_STAGING") != nullptr;   // diagnostic: the per-batch copies
   const bool staged = !table && !no_stage && in_sum + out_sum <= kSmallCap;
@@ -589,48 +624,39 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
     acnqp_handle::Slot& S = h->slot[c % acnqp_handle::kSlots];
     const std::vector<Piece>& pcs = chunks[c];   // (table entry: one piece)
     const BatchShape& b = call.bs[pcs[0].g];
-    const size_t cn = (size_t)(pcs.back().pos + pcs.back().n), Tm = b.t_max;
-    const ChunkLayout L = layout(c);
-    const TableLayout TL = table ? TableLayout(call.T, pcs[0].lo, pcs[0].n, N * Tm) : TableLayout();
-    if (L.in_total > S.in.cap || L.out_total > S.out.cap || TL.total > S.tin.cap) HIP_TRY(hipStreamSynchronize(S.st));   // staging still in use
-    HIP_TRY(S.in.reserve(L.in_total));
-    HIP_TRY(S.out.reserve(L.out_total));
-    if (table) HIP_TRY(S.tin.reserve(TL.total));
+    call.layout.push_back(layout(c));
+    const ChunkLayout& L = call.layout.back();
+    const TableLayout TL = table ? TableLayout(table_span(call.T, pcs[0].lo, pcs[0].n, N * L.shape.Tm)) : TableLayout();
+    HIP_TRY(reserve_behind(S.st, {{&S.in, L.in[kInRows]}, {&S.out, L.out[kOutRows]}, {&S.tin, TL.total}}));
     char* di = static_cast<char*>(S.in.p);
     char* dq = static_cast<char*>(S.out.p);
-    char* hs = staged ? static_cast<char*>(h->small_in.p) + in_off[c] - L.pd : nullptr;    // hs + L.field = the mirror of di + L.field
-    char* ho = staged ? static_cast<char*>(h->small_out.p) + out_off[c] - L.st : nullptr;  // ho + L.field = the mirror of dq + L.field
+    char* hs = staged ? static_cast<char*>(h->small_in.p) + in_off[c] - L.mirror_in() : nullptr;     // hs + L.in[k] = the mirror of di + L.in[k]
+    char* ho = staged ? static_cast<char*>(h->small_out.p) + out_off[c] - L.mirror_out() : nullptr;  // ho + L.out[k] = the mirror of dq + L.out[k]
     // the ONE difference between the entries (see above for what the table entry deliberately does not share)
-    int rc = table ? fill_table(h, call, pcs[0], L, TL, S) : fill_dense(h, call, c, pcs, L, S, hs);
+    int rc = table ? fill_table(call, pcs[0], L, TL, S) : fill_dense(h, call, c, pcs, L, S, hs);
     if (rc != ACNQP_OK) return rc;
     acnqp_problems dp;
     acnqp_results dr;
-    device_views(L, di, dq, s, cn, b, &dp, &dr);
-    double* const* x_host = direct[c] ? reinterpret_cast<double* const*>(di + L.xh) : nullptr;
+    device_views(L, di, dq, b, &dp, &dr);
+    double* const* x_host = L.direct ? reinterpret_cast<double* const*>(di + L.in[kXh]) : nullptr;
     rc = solve_batch_device(h, &dp, o, &dr, S.st, c + 1 == chunks.size(), x_host);   // (the last chunk: nothing follows its launch)
     if (rc != ACNQP_OK) return rc;
-    if (staged) HIP_TRY(hipMemcpyAsync(ho + L.st, dq + L.st, L.y - L.st, hipMemcpyDeviceToHost, S.st));
+    if (staged) HIP_TRY(hipMemcpyAsync(ho + L.mirror_out(), dq + L.mirror_out(), L.mirror_out_bytes(), hipMemcpyDeviceToHost, S.st));
     for (const Piece& pc : pcs) {
       const acnqp_results& r = call.R[pc.g];
       const size_t lo = (size_t)pc.lo, n = (size_t)pc.n, pos = (size_t)pc.pos;
-#define D2H(field, base, elem, per)                                                                          \
-  HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(r.field) + lo * (per) * (elem), dq + (base) + pos * (per) * (elem), \
-                         n * (per) * (elem), hipMemcpyDeviceToHost, S.st))
-      if (direct[c] && call.xdst[pc.g]) h->direct_x_last += (long long)n;   // (the kernel has stored them, or will have)
-      else D2H(x, L.x, 8, N * Tm);
-      if (staged) {
-        call.scatter.push_back(Scatter{pc.g, lo, n, pos, ho, L.st, L.it, L.pr, L.du, L.ob});
-      } else {
-        D2H(status, L.st, 4, 1);
-        D2H(iters, L.it, 4, 1);
-        D2H(pri_res, L.pr, 8, 1);
-        D2H(dua_res, L.du, 8, 1);
-        D2H(obj, L.ob, 8, 1);
+      const bool stored = L.direct && call.xdst[pc.g];   // (the kernel has stored this piece's x, or will have)
+      if (stored) h->direct_x_last += (long long)n;
+      for (int k = 0; k < kOutRows; ++k) {   // a copy each, but: x of a stored piece, the small rows of a staged call
+        if (!present(kOut[k], L.shape) || (k == kX && stored) || (staged && kOut[k].size == Size::Small)) continue;
+        const size_t per = bytes_per_problem(kOut[k], L.shape);
+        HIP_TRY(hipMemcpyAsync(member(&r, kOut[k].field) + lo * per, dq + L.out[k] + pos * per, n * per, hipMemcpyDeviceToHost, S.st));
       }
-      if (b.want_y) D2H(y, L.y, 8, Mg * Tm);
-#undef D2H
-      if (r.x_dev)
-        HIP_TRY(hipMemcpyAsync(r.x_dev + lo * N * Tm, dq + L.x + pos * N * Tm * 8, n * N * Tm * 8, hipMemcpyDeviceToDevice, S.st));
+      if (staged) call.scatter.push_back(Scatter{pc, c, ho});
+      if (r.x_dev) {
+        const size_t per = bytes_per_problem(kOut[kX], L.shape);
+        HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(r.x_dev) + lo * per, dq + L.out[kX] + pos * per, n * per, hipMemcpyDeviceToDevice, S.st));
+      }
     }
   }
   return ACNQP_OK;
@@ -657,12 +683,11 @@ int solve_call(acnqp_handle* h, Call& call, const acnqp_options* o, const char* 
   if (rc != ACNQP_OK) return rc;
   if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
   for (const Scatter& sc : call.scatter) {   // the small result arrays: pinned mirror -> the caller's arrays
-    const acnqp_results& rr = call.R[sc.g];
-    std::memcpy(rr.status + sc.lo, sc.host + sc.st + sc.pos * 4, sc.n * 4);
-    std::memcpy(rr.iters + sc.lo, sc.host + sc.it + sc.pos * 4, sc.n * 4);
-    std::memcpy(rr.pri_res + sc.lo, sc.host + sc.pr + sc.pos * 8, sc.n * 8);
-    std::memcpy(rr.dua_res + sc.lo, sc.host + sc.du + sc.pos * 8, sc.n * 8);
-    std::memcpy(rr.obj + sc.lo, sc.host + sc.ob + sc.pos * 8, sc.n * 8);
+    const ChunkLayout& L = call.layout[sc.c];
+    for (int k = kSmallOut.first; k < kSmallOut.end; ++k) {
+      const size_t per = bytes_per_problem(kOut[k], L.shape);
+      std::memcpy(member(&call.R[sc.pc.g], kOut[k].field) + (size_t)sc.pc.lo * per, sc.host + L.out[k] + (size_t)sc.pc.pos * per, (size_t)sc.pc.n * per);
+    }
   }
   for (size_t g = 0; g < call.bs.size(); ++g)
     for (long long b = 0; b < call.bs[g].batch; ++b)

@@ -134,8 +134,7 @@ int acnqp_duals_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_opt
   if (!a.gbuf && !acnqp::duals_wave_shape(h->shape.N, p->t_max)) {   // z not wanted: g goes to a scratch of this stream (the wave form keeps g in LDS)
     acnqp_handle::Work* wk = h->work_for(st);
     const size_t need = (size_t)p->batch * h->shape.N * p->t_max * sizeof(double);
-    if (need > wk->dua.cap) HIP_TRY(hipStreamSynchronize(st));   // an earlier report on this stream may still use the old one
-    HIP_TRY(wk->dua.reserve(need));
+    HIP_TRY(reserve_behind(st, {{&wk->dua, need}}));
     a.gbuf = static_cast<double*>(wk->dua.p);
   }
   (void)hipGetLastError();

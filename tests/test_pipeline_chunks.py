@@ -1,9 +1,20 @@
 """The host-buffer entries' chunk pipeline (adacharge_amd/csrc/acn_qp_pipeline.hpp): however a call is cut into chunks --
 ``ACNQP_PLAN`` / ``ACNQP_CHUNK`` (diagnostic variables read at every call) or the default ramp -- and whichever entry
 takes it (dense, pinned or pageable results, with a device sink; session table), every output equals BIT FOR BIT the
-unchunked solve of the same problems.  Six chunks on four slots reuse two slots whose staging grows between uses."""
+unchunked solve of the same problems.  Six chunks on four slots reuse two slots whose staging grows between uses.
+
+Run as a script (``name out.npz``) it solves the warm-row case of one pool, unchunked and in chunks of 8, under the
+environment it was started with and saves every output: ``ACNQP_NO_STAGING`` is read once per process."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
 
 from adacharge_amd import ObjectiveComponent, equal_share, quick_charge, sites
 from adacharge_amd.acn import InfrastructureInfo, Interface
@@ -119,3 +130,73 @@ def test_non_wave_ramp_gives_both_entries_the_bits_of_the_pool_solved_alone():
         m = min(32, 1800 - lo)
         for k in KEYS:
             assert np.array_equal(getattr(dense, k)[lo:lo + m], getattr(alone, k)[:m]), (lo, k)
+
+
+# ---- the arrays no chunked case above carries: lf, dc, dfloor, warm_x, warm_y -------------------------------------------
+WARM_ROW_POOLS = ("n100_t24_lf", "jpl_t28_dc")   # a flat row; a max row (tests/warm_cases.py)
+CUTS = ((0, 9), (9, 13), (13, 20))               # chunks of 8: 8 | 1 + 4 + 3 | 4 -- three pieces in the middle one
+CHILD_TIMEOUT = 120                               # seconds for the child process of the unstaged case
+
+
+def _warm_rows(name, chunk):
+    """20 problems of a warm pool as batches of 9, 4 and 7 with their warm points and want_y through ``solve_many``, with
+    pinned and with pageable results; ``chunk``: ACNQP_CHUNK (None: unset).  -> {"pinned" | "pageable": {key: (20, ...)}}"""
+    from adacharge_amd.backend import SiteHandle, default_options
+    from tests import warm_cases
+
+    pool = warm_cases.pool(name)
+    wx, wy = warm_cases.warm(name, "perturbed")
+    batches = [pool.subset(slice(a, b)) for a, b in CUTS]
+    warm = [(wx[a:b], wy[a:b]) for a, b in CUTS]
+    assert (pool.site.has_flat or pool.site.has_max) and pool.B >= 20
+    if chunk is None:
+        os.environ.pop("ACNQP_CHUNK", None)
+    else:
+        os.environ["ACNQP_CHUNK"] = str(chunk)
+    h = SiteHandle(pool.site, 0)
+    out = {}
+    try:
+        for tag, pinned in (("pinned", True), ("pageable", False)):
+            n0 = _launches(h)
+            res = h.solve_many(batches, default_options(), pinned_results=pinned, want_y=[True] * 3, warm=warm)
+            assert _launches(h) - n0 == (1 if chunk is None else 3)
+            out[tag] = {k: np.concatenate([np.array(getattr(r, k)) for r in res]) for k in KEYS}
+    finally:
+        h.close()
+        os.environ.pop("ACNQP_CHUNK", None)
+    return out
+
+
+def _same_runs(ref, got, what):
+    for tag in ("pinned", "pageable"):
+        for k in KEYS:
+            assert np.array_equal(ref[tag][k], got[tag][k]), (what, tag, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", WARM_ROW_POOLS)
+def test_flat_max_and_warm_rows_in_chunks_of_8_keep_every_bit(name, monkeypatch):
+    monkeypatch.delenv("ACNQP_CHUNK", raising=False)   # (restored whatever _warm_rows does to it)
+    ref = _warm_rows(name, None)
+    assert (ref["pinned"]["status"] != 0).all() and ref["pinned"]["iters"].min() >= 1   # (0: UNSET)
+    _same_runs(ref, _warm_rows(name, 8), name)
+    for k in KEYS:
+        assert np.array_equal(ref["pinned"][k], ref["pageable"][k]), k
+
+
+@pytest.mark.gpu
+def test_flat_and_warm_rows_without_staging_keep_every_bit(tmp_path):
+    """the per-array copies of ACNQP_NO_STAGING=1, in a fresh process (the switch is read once)"""
+    name, path = WARM_ROW_POOLS[0], str(tmp_path / "unstaged.npz")
+    env = {k: v for k, v in os.environ.items() if k not in ("ACNQP_CHUNK", "ACNQP_PLAN")}
+    subprocess.run([sys.executable, os.path.abspath(__file__), name, path], check=True, env=dict(env, ACNQP_NO_STAGING="1"), timeout=CHILD_TIMEOUT)
+    got = np.load(path)
+    for tag in ("pinned", "pageable"):
+        for k in KEYS:
+            assert np.array_equal(got[f"whole_{tag}_{k}"], got[f"chunks_{tag}_{k}"]), (tag, k)
+    assert got["whole_pinned_x"].shape[0] == 20 and (got["whole_pinned_status"] != 0).all()   # (0: UNSET)
+
+
+if __name__ == "__main__":
+    runs = {"whole": _warm_rows(sys.argv[1], None), "chunks": _warm_rows(sys.argv[1], 8)}
+    np.savez(sys.argv[2], **{f"{run}_{tag}_{k}": v for run, d in runs.items() for tag, r in d.items() for k, v in r.items()})
