@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "acn_qp_common.hpp"
+#include "acn_qp_project.hpp"
 
 namespace acnqp {
 
@@ -131,11 +132,7 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
       a += l; c += u;
     }
     mu[s] = 0; slo[s] = a; shi[s] = c;
-    if (len > 0) {
-      const real cap = (real)A.s_cap[sidx];
-      const real slack = (real)64 * M::proj_tol * fmax((real)1, fabs(cap));
-      if (a > cap + slack || (eq && c < cap - slack)) bad = 1;
-    }
+    if (len > 0 && bounds_miss_energy_row<real>(a, c, (real)A.s_cap[sidx], eq, M::proj_tol)) bad = 1;
   }
   __syncthreads();
   const real qnorm = block_reduce_max<real, kGenThreads>(qn, red, tid);
@@ -183,13 +180,12 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
         lo = fmin(lo, v[t] - ub_[t]);
         hi = fmax(hi, v[t] - (real)lb_[t]);
       }
-      const real tol = M::proj_tol * fmax((real)1, fabs(cap));
-      const bool need = eq ? fabs(s0 - cap) > tol : s0 > cap + tol;
-      if (!need) { mu[s] = 0; continue; }
-      if (eq && cap >= shi[s]) { for (int t = 0; t < len; ++t) z[t] = ub_[t]; mu[s] = 0; continue; }
-      if (cap <= slo[s]) { for (int t = 0; t < len; ++t) z[t] = (real)lb_[t]; mu[s] = 0; continue; }
-      if (!eq && lo < 0) lo = 0;
-      real m = fmin(fmax(mu[s], lo), hi);
+      const real tol = fill_tol<real>(cap, M::proj_tol);
+      const int mode = fill_mode<real>(true, eq, s0, slo[s], shi[s], cap, tol);
+      if (mode == kFillNone) { mu[s] = 0; continue; }
+      if (mode == kFillAtUb) { for (int t = 0; t < len; ++t) z[t] = ub_[t]; mu[s] = 0; continue; }
+      if (mode == kFillAtLb) { for (int t = 0; t < len; ++t) z[t] = (real)lb_[t]; mu[s] = 0; continue; }
+      real m = fill_start<real>(eq, mu[s], lo, hi);
       for (int guard = 0; guard <= 100; ++guard) {
         real g = 0, nf = 0;
         for (int t = 0; t < len; ++t) {
@@ -198,11 +194,8 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
           nf += (u > (real)lb_[t] && u < ub_[t]) ? (real)1 : (real)0;
         }
         const real d = g - cap;
-        if (fabs(d) <= tol) break;
-        if (d > 0) lo = m; else hi = m;
-        real mn = nf > 0 ? m + d / nf : (real)0.5 * (lo + hi);
-        if (!(mn > lo && mn < hi)) mn = (real)0.5 * (lo + hi);
-        m = mn;
+        if (fill_done<real>(d, tol)) break;
+        fill_step<real>(m, d, nf, lo, hi, true);
       }
       mu[s] = m;
       for (int t = 0; t < len; ++t) z[t] = fmin(fmax(v[t] - m, (real)lb_[t]), ub_[t]);
@@ -393,18 +386,19 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
       const int r = k / T, t = k - r * T;
       const int ty = A.rowtype[r];
       if (ty == kRowMax && dc_on) continue;   // written by wave 0 below, and by nobody else (no write-write race)
-      real zn = zh2[k];
-      if (ty == kRowBox) zn = fmin(zn, RL[r]);
-      else if (ty == kRowQuad) zn = zn * (rho / (rho + (A.lf ? (real)(A.lf[b] / (A.flat_scale * A.flat_scale)) : (real)0)));
+      real lim = 0, pk = M::big, quad = 1, scl = 1;   // what the row's type reads (site_row_z, acn_qp_project.hpp)
+      if (ty == kRowBox) lim = RL[r];
+      else if (ty == kRowQuad) quad = rho / (rho + (A.lf ? (real)(A.lf[b] / (A.flat_scale * A.flat_scale)) : (real)0));
       else if (ty == kRowPeak) {
         const double pv = A.peak ? A.peak[(size_t)b * T + t] : 1e300;
-        zn = fmin(zn, pv < (double)M::big ? (real)(pv * A.peak_scale) : M::big);
+        pk = pv < (double)M::big ? (real)(pv * A.peak_scale) : M::big;
       } else if (ty == kRowSocRe || ty == kRowSocIm) {
         const int rr = ty == kRowSocRe ? r : r - GA.pair_stride;
         const real re = zh2[rr * T + t], im = zh2[(rr + GA.pair_stride) * T + t];
-        const real n2 = re * re + im * im, lim = RL[rr];
-        if (n2 > lim * lim) zn = zn * (lim / sqrt(n2));
+        const real n2 = re * re + im * im, l2 = RL[rr];
+        if (n2 > l2 * l2) scl = l2 / sqrt(n2);
       }
+      const real zn = site_row_z<real>(ty, zh2[k], lim, pk, quad, scl);
       y2[k] = rho * (zh2[k] - zn);
       z2[k] = zn;
     }
@@ -424,10 +418,9 @@ __global__ __launch_bounds__(kGenThreads) void admm_general_kernel(const General
             real Sl = 0, nl = 0;
             for (int t = tid; t < T; t += 64) if (zv[t] > tau) { Sl += zv[t] - tau; nl += 1; }
             const real S = wave_sum<real>(Sl), nn = wave_sum<real>(nl);
-            const real f = S - cw;
-            const real tn = nn > 0 ? tau + f / nn : vmax - cw;
-            if (fabs(f) <= M::proj_tol * fmax((real)1, cw) * (real)16 || tn == tau) break;
-            tau = tn;
+            const DcStep<real> st = dc_tau_step<real>(tau, S, nn, cw, vmax, M::proj_tol, guard, 200);   // (the loop bound is the guard)
+            if (st.fin) break;
+            tau = st.tn;
           }
           const real lev = fmax(tau, fl);
           for (int t = tid; t < T; t += 64) {

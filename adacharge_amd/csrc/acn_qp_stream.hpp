@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "acn_qp_common.hpp"
+#include "acn_qp_project.hpp"
 
 namespace acnqp {
 
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
         sl = row_sum<real>(sl); su = row_sum<real>(su);
         if (len > 0) {
           const real cap = A.s_cap[sidx];
-          const real slack = 64.0 * M::proj_tol * fmax(1.0, fabs(cap));
+          const real slack = 64.0 * M::proj_tol * fmax(1.0, fabs(cap));   // the rule: bounds_miss_energy_row, acn_qp_project.hpp
           if (sl > cap + slack || (eq && su < cap - slack)) bad = 1;
         }
         if (t == 0 && ev < NP) MU[(size_t)k * NP + ev] = 0;
@@ -417,13 +418,11 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
       }
       s0 = row_sum<real>(s0); sl = row_sum<real>(sl); su = row_sum<real>(su);
       real lo = row_min<real>(lo_l), hi = row_max<real>(hi_l);
-      const real tol = M::proj_tol * fmax(1.0, fabs(cap));
-      const bool act = len > 0 && (eq ? fabs(s0 - cap) > tol : s0 > cap + tol);
-      const int mode = !act ? 4 : ((eq && cap >= su) ? 2 : (cap <= sl ? 3 : 0));   // 0 root-find, 2 at ub, 3 at lb, 4 nothing
-      bool need = mode == 0;
-      if (!eq && lo < 0) lo = 0;
+      const real tol = fill_tol<real>(cap, M::proj_tol);
+      const int mode = fill_mode<real>(len > 0, eq, s0, sl, su, cap, tol);
+      bool need = mode == kFillRoot;
       const real mu0 = (reset_mu || ev >= N) ? 0.0 : (pre ? first.mu : MU[(size_t)k * NP + ev]);
-      real m = fmin(fmax(mu0, lo), hi);
+      real m = fill_start<real>(eq, mu0, lo, hi);
 #pragma unroll 1
       for (int guard = 0; guard <= 100; ++guard) {
         if (!__any(need)) break;
@@ -438,23 +437,19 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
         }
         const real gs = row_sum<real>(gl), nf = row_sum<real>(nl);
         const real d = gs - cap;
-        need = need && !(fabs(d) <= tol);
-        lo = (need && d > 0) ? m : lo;
-        hi = (need && !(d > 0)) ? m : hi;
-        real mn = nf > 0 ? m + d / nf : 0.5 * (lo + hi);
-        if (!(mn > lo && mn < hi)) mn = 0.5 * (lo + hi);
-        m = need ? mn : m;
+        need = need && !fill_done<real>(d, tol);
+        fill_step<real>(m, d, nf, lo, hi, need);
       }
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
         const int tp = 16 * c + t;
         if (tp >= off && tp < off + len) {
-          if (mode == 0) z1[c] = fmin(fmax(zh[c] - m, lbv[c]), ubv[c]);
-          else if (mode == 2) z1[c] = ubv[c];
-          else if (mode == 3) z1[c] = lbv[c];
+          if (mode == kFillRoot) z1[c] = fmin(fmax(zh[c] - m, lbv[c]), ubv[c]);
+          else if (mode == kFillAtUb) z1[c] = ubv[c];
+          else if (mode == kFillAtLb) z1[c] = lbv[c];
         }
       }
-      if (t == 0 && ev < N) MU[(size_t)k * NP + ev] = (mode == 0 && !reset_mu) ? m : 0.0;
+      if (t == 0 && ev < N) MU[(size_t)k * NP + ev] = (mode == kFillRoot && !reset_mu) ? m : 0.0;
     }
   };
 
@@ -676,7 +671,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = ((mo * CT + c) * 4 + r) * 64 + lane;
-      real zn = zhr[r];
+      real zn = zhr[r];   // the rule: site_row_z, acn_qp_project.hpp
       if (ty[r] == kRowBox) zn = fmin(zn, lim[r]);
       else if (ty[r] == kRowPeak) zn = fmin(zn, pk);
       else if (ty[r] == kRowQuad) zn = zn * (rho / (rho + lfb));
@@ -698,32 +693,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? ACNQP_STREAM_OCC : 1) void adm
     real zv[CT], gxv[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) { const int i = ((mo * CT + c) * 4 + rd_) * 64 + lane; zv[c] = Z2[i]; gxv[c] = GX[i]; }
-    const real cw = dcb / rho;
-    real vmax_l = -M::big;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) vmax_l = (16 * c + t < Tm) ? fmax(vmax_l, zv[c]) : vmax_l;
-    const real vmax = row_max<real>(vmax_l);
-    real tau = vmax - cw;
-    bool need = g == gd;
-    int guard = 0;
-    while (__any(need)) {
-      ++guard;
-      real sl = 0, nl = 0;
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        const real dd = zv[c] - tau;
-        const bool on = (16 * c + t < Tm) && dd > 0.0;
-        sl += on ? dd : 0.0;
-        nl += on ? 1.0 : 0.0;
-      }
-      const real S = row_sum<real>(sl), nn = row_sum<real>(nl);
-      const real f = S - cw;
-      const real tn = nn > 0.0 ? tau + f / nn : vmax - cw;
-      const bool fin = fabs(f) <= M::proj_tol * fmax(1.0, cw) * 16.0 || tn == tau || guard > 200;
-      tau = (need && !fin) ? tn : tau;
-      need = need && !fin;
-    }
-    const real lev = fmax(tau, dfl);
+    const real lev = fmax(dc_row_tau<CT>(zv, dcb / rho, t, Tm, g == gd), dfl);
     if (g == gd) {
 #pragma unroll
       for (int c = 0; c < CT; ++c) {

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void admm_tiled_kernel(const TiledArg
       scap[k] = sact ? (real)A.s_cap[sidx] : (real)0;
       if (len > 0) {
         smode[k] = 0;
-        const real slack = (real)64 * M::proj_tol * fmax((real)1, fabs(scap[k]));
+        const real slack = (real)64 * M::proj_tol * fmax((real)1, fabs(scap[k]));   // the rule: bounds_miss_energy_row, acn_qp_project.hpp
         if (sl > scap[k] + slack) empty_set = true;
         if (eq && su < scap[k] - slack) empty_set = true;
         if (eq && scap[k] >= su) smode[k] = 2;

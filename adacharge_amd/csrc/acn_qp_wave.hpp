@@ -428,7 +428,7 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     scap = act ? A.s_cap[sidx] : 0.0;
     if (len > 0) {
       smode = 0;
-      const real slack = 64.0 * M::proj_tol * fmax(1.0, fabs(scap));
+      const real slack = 64.0 * M::proj_tol * fmax(1.0, fabs(scap));   // the rule: bounds_miss_energy_row, acn_qp_project.hpp
       if (sl > scap + slack) empty_set = true;
       if (eq && su < scap - slack) empty_set = true;
       if (eq && scap >= su) smode = 2;

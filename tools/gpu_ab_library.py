@@ -2,7 +2,9 @@
 tests/test_route_certificate.py (all eleven kernel families and the polish) and of tests/test_verdicts_gpu.py (every
 probe, both sides of the boundary, and the max_iter = check_every = 20 runs), each padded to every family it reaches
 and launched through the device entry with every output poisoned.  x, y, status, iters, pri_res, dua_res and obj must
-agree BIT FOR BIT between the two libraries.  One child process per library and pool group (ACNQP_LIBRARY selects the
+agree BIT FOR BIT between the two libraries.  The `warm` group feeds the one input those pools leave out: the pools of
+tests/warm_cases.py on every family they reach, from every kind of warm point after 60 plain iterations and from the
+perturbed point as shipped.  One child process per library and pool group (ACNQP_LIBRARY selects the
 library), one at a time, each under its own time limit; the first non-zero exit ends the run.
 
     python tools/gpu_ab_library.py child <group> <out.npz>          one library (ACNQP_LIBRARY), one group of pools
@@ -14,12 +16,12 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 KEYS = ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")
-GROUPS = ("routes", "verdicts_a", "verdicts_b", "max_iter")
+GROUPS = ("routes", "verdicts_a", "verdicts_b", "max_iter", "warm")
 CHILD_TIMEOUT = 900   # seconds per child
 
 
 def runs(group):
-    """(tag, handle, padded batch, options) of every launch of the group"""
+    """(tag, handle, padded batch, options, warm point or None) of every launch of the group"""
     from adacharge_amd.backend import SiteHandle, default_options
     from adacharge_amd.builder import ProblemBatch
     from tests import helpers as H
@@ -31,7 +33,7 @@ def runs(group):
             pool = R.POOLS[name]()
             h = SiteHandle(pool.site, 0)
             for fam, (t, k) in H.route_shapes(h, pool).items():
-                yield f"route/{name}/{fam}", h, H.pad_batch(pool, t, k), None
+                yield f"route/{name}/{fam}", h, H.pad_batch(pool, t, k), None, None
             h.close()
     elif group in ("verdicts_a", "verdicts_b"):
         names = list(G.POOLS)
@@ -40,14 +42,25 @@ def runs(group):
             h = SiteHandle(pool.site, 0)
             for fam, (t, k) in H.route_shapes(h, pool).items():
                 if G.POOLS[name]["want"] is None or fam in G.POOLS[name]["want"]:
-                    yield f"verdict/{name}/{fam}", h, H.pad_batch(pool, t, k), None
+                    yield f"verdict/{name}/{fam}", h, H.pad_batch(pool, t, k), None, None
+            h.close()
+    elif group == "warm":
+        from tests import warm_cases as WC
+
+        for name, want in WC.POOLS.items():
+            pool = WC.pool(name)
+            h = SiteHandle(pool.site, 0)
+            for fam, (t, k) in H.route_shapes(h, pool).items():
+                if want is None or fam in want:
+                    for kind, run in [(kind, "m60") for kind in WC.kinds_of(name, t)] + [("perturbed", "shipped")]:
+                        yield f"warm/{name}/{fam}/{kind}/{run}", h, H.pad_batch(pool, t, k), default_options(**WC.RUNS[run]), WC.warm(name, kind, t)
             h.close()
     else:
         for name in G.MAX_ITER_POOLS:
             pool = ProblemBatch.concatenate(G._filler(G.POOLS[name], np.random.default_rng(77), 24))
             h = SiteHandle(pool.site, 0)
             for fam, (t, k) in H.route_shapes(h, pool).items():
-                yield f"max_iter/{name}/{fam}", h, H.pad_batch(pool, t, k), default_options(max_iter=20, check_every=20)
+                yield f"max_iter/{name}/{fam}", h, H.pad_batch(pool, t, k), default_options(max_iter=20, check_every=20), None
             h.close()
 
 
@@ -55,8 +68,8 @@ def child(group, path):
     from tests import helpers as H
 
     res = {}
-    for tag, h, padded, opts in runs(group):
-        out = H.launch_poisoned(h, padded, opts)
+    for tag, h, padded, opts, warm in runs(group):
+        out = H.launch_poisoned(h, padded, opts, warm=warm)
         for k in KEYS:
             res[f"{tag}/{k}"] = out[k]
     np.savez(path, **res)
