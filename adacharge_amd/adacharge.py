@@ -278,6 +278,12 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         from ``interface.get_prices(steps + t_max, start_time)``, or from ``prices`` -- ``(P,)`` or ``(B, P)``, entry 0 the price
         of period ``start_time``, one tariff per scenario (with a ``FleetTable`` the table's own ``prices`` hold) -- and the result
         carries ``energy_cost (B,)``.  Every other objective that reads the clock raises ``ValueError``.
+        A record may carry ``battery``: ``dict(capacity=kWh, init_charge=kWh, max_power=kW, transition_soc=None or a fraction
+        inside (0, 1))`` -- the battery decides what the EV DRAWS of its pilot (``acnqp_plant_device`` between the pilots and
+        the advance: a current limit, the room left to full and, past ``transition_soc``, a rate that falls with that room).
+        The advance, the demand-charge floor, ``delivered`` and ``energy_cost`` then follow what was drawn, and the result
+        carries ``actual (steps, B, N)`` and ``plant_flags (steps, B)``.  A rollout whose fleets carry no battery launches
+        and returns exactly what it did without the feature.  ``estimate_max_rate`` waits for an estimator on top of it.
         ``warm_start``: every solve but the first starts from the previous
         period's schedule and multipliers, shifted on the device.  ``observer(step, state, pilots)``: diagnostic hook called
         after each period's solve has been enqueued (it may synchronise and read the ``DeviceBatch``)."""

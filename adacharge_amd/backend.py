@@ -42,6 +42,7 @@ STATUS_NAMES = {
 PILOTS_CONTINUOUS, PILOTS_DISCRETE, PILOTS_REALLOCATE = 0, 1, 2
 ADVANCE_REFUSED, ADVANCE_NO_ROW, ADVANCE_BAD_SLOT = 1, 2, 4
 PREPARE_FUTURE = 1
+PLANT_BAD_PLUG, PLANT_BAD_BATTERY = 1, 2
 # kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
 ROUTE_NAMES = {1: "wave1", 2: "wave2", 3: "wave3", 4: "wave4", 5: "wave5", 6: "tiled_ct1", 7: "tiled_ct2",
                8: "long_lds", 9: "long_ws", 10: "stream", 11: "general"}
@@ -67,6 +68,7 @@ _ADVANCE_ARRAYS = dict(q_table=_F8, h_scal=_F8, h_row=_I4, peak_series=_F8, a_se
                        a_rate_seg=_I4, a_min=_F8, a_max=_F8)
 _COST_ARRAYS = dict(c_weight=_F8, c_series=_F8)   # weight and series of acnqp_clock_cost, under AdvancePlan's names
 _PREPARE_ARRAYS = dict(key=_I4, cre=_F8, cim=_F8, limits=_F8, min_pilot=_F8)
+_PLANT_ARRAYS = dict(t_room=_F8, t_amps=_F8, t_knee=_F8, t_slope=_F8, plug=_I4)   # the plant entries take them as plain arguments
 
 
 def _ints(*names):
@@ -178,6 +180,8 @@ def _abi():
         ("acnqp_advance", advance + [P(_Next), ptr]),
         ("acnqp_advance_priced", advance + [P(ClockCost), P(_Next), ptr]),
         ("acnqp_prepare", [h, P(_Problems), P(_PreparePlan), ptr, ptr, P(_PrepareView), ptr]),
+        # cur, pilots, status, n_batteries, t_room, t_amps, t_knee, t_slope, plug, bat, room, actual, flags
+        ("acnqp_plant", [h, P(_Problems), ptr, ptr, i32] + [ptr] * 9),
     ):
         rows += [(stem + "_host", rc, args), (stem + "_device", rc, args + [stream])]
     introspection = [
@@ -379,7 +383,7 @@ class DualResult:
 
 
 class _PlanArrays:
-    """What the three plan classes share.  ``_DTYPES``: {array field: the dtype the ABI reads}."""
+    """What the plan classes share.  ``_DTYPES``: {array field: the dtype the ABI reads}."""
 
     _DTYPES = {}
 
@@ -507,6 +511,26 @@ class PreparePlan(_PlanArrays):
     def _struct(self, N: int, key_row=None, min_rates: bool = True, keep=None) -> "_PreparePlan":
         return _PreparePlan(int(N), self._len("cre"), self._p("key", keep, 0 if key_row is None else key_row, 3), self._p("cre", keep),
                             self._p("cim", keep), self._p("limits", keep), self._p("min_pilot", keep) if min_rates else None)
+
+
+@dataclass
+class PlantPlan(_PlanArrays):
+    """The battery table and the plug-in rows of ``acnqp_plant_device / _host`` (include/acn_qp.h, "the plant"): numpy arrays
+    for ``SiteHandle.plant_host``, torch tensors on the handle's GPU (``to_device``) for ``SiteHandle.plant_device``.  ``plug``
+    may hold one (B, N) block per step (``(steps, B, N)``): ``plug_row`` picks the step's.  ``rollout.FleetTable`` builds one."""
+    t_room: object    # (R,) room left at plug-in, A-periods
+    t_amps: object    # (R,) the battery's current limit, A
+    t_knee: object    # (R,) room at which the tail begins; 0: no tail
+    t_slope: object   # (R,) t_amps / t_knee where t_knee > 0, else 0
+    plug: object      # (B, N) or (rows, B, N) int32: the row plugged in at the step, -1 elsewhere
+
+    _DTYPES = _PLANT_ARRAYS
+    _ARRAYS = tuple(_PLANT_ARRAYS)
+
+    def _args(self, plug_row=None, keep=None) -> list:
+        """n_batteries and the five pointers, in the order of the entries' arguments"""
+        return [C.c_int32(self._len("t_room"))] + [self._p(k, keep, 0 if plug_row is None else plug_row, 3 if k == "plug" else None)
+                                                   for k in _PLANT_ARRAYS]
 
 
 class _PinnedBlock:
@@ -893,6 +917,59 @@ class SiteHandle:
         v = _PrepareView(_dptr(v_evse), _dptr(v_arrived), _dptr(v_cap))
         _check(self._lib.acnqp_prepare_device(self._h, C.byref(p), C.byref(pl), _dptr(cur.lb), _dptr(cur.ub), C.byref(v), _dptr(flags),
                                               C.c_void_p(stream)), "acnqp_prepare_device")
+
+    # -- the plant (acn_qp_plant.hpp) -----------------------------------------------------------------------------------
+    def plant_host(self, cur: dict, plan: PlantPlan, pilots, bat, room, status=None, plug_row=None) -> dict:
+        """acnqp_plant_host: what the EVs of the state ``cur`` -- numpy arrays ``s_off, s_len`` (B, 1, N) or (B, N) -- draw of
+        ``pilots`` (B, N) under ``plan`` (numpy arrays), from the plant state ``bat`` (B, N) int32 and ``room`` (B, N).  Returns
+        ``bat, room`` (copies, advanced), ``actual`` (B, N) and ``flags`` (B,)."""
+        off, ln, pil, stat = _i4(cur["s_off"]), _i4(cur["s_len"]), _f8(pilots), _i4(status)
+        bat, room = np.array(bat, np.int32, order="C"), np.array(room, np.float64, order="C")   # copies: the entry writes them
+        if pil.ndim != 2 or pil.shape[1] != self.site.N:
+            raise ValueError("pilots must have the shape (B, N) of the handle's site")
+        B, N = pil.shape
+        K = off.shape[1] if off.ndim == 3 else 1
+        if off.size != B * K * N or ln.size != off.size or bat.shape != (B, N) or room.shape != (B, N):
+            raise ValueError("cur needs s_off, s_len of shape (B, K, N); bat and room have the shape (B, N)")
+        plug = plan.plug if plan.plug.ndim == 2 else plan.plug[0 if plug_row is None else plug_row]
+        if plug.shape != (B, N) or (stat is not None and stat.shape != (B,)):
+            raise ValueError("plan.plug needs one (B, N) block per step and status the shape (B,)")
+        actual, flags = np.empty((B, N)), np.empty(B, np.int32)
+        p = _Problems(B, 1, K, s_off=_ptr(off), s_len=_ptr(ln))
+        keep = []
+        _check(self._lib.acnqp_plant_host(self._h, C.byref(p), _ptr(pil), _ptr(stat), *plan._args(plug_row, keep), _ptr(bat), _ptr(room),
+                                          _ptr(actual), _ptr(flags)), "acnqp_plant_host")
+        del keep
+        return dict(bat=bat, room=room, actual=actual, flags=flags)
+
+    def plant_device(self, cur: "DeviceBatch", plan: PlantPlan, pilots, bat, room, actual, flags, status=None, plug_row=None,
+                     stream: int = 0) -> None:
+        """acnqp_plant_device: ``actual`` (B, N) float64 receives what the EVs of ``cur`` draw of ``pilots`` (B, N); the plant
+        state ``bat`` (B, N) int32 and ``room`` (B, N) float64 is advanced in place; ``flags`` (B,) int32.  ``status``: (B,)
+        int32 (a problem it does not call solved draws nothing) or None.  ``plan`` from ``PlantPlan.to_device``.  Asynchronous
+        on ``stream``."""
+        import torch
+
+        here = torch.device("cuda", self.device)
+        B, N, K = cur.B, cur.N, cur.K
+        R = plan._len("t_room")
+        if plan.plug is None or not hasattr(plan.plug, "dim"):
+            raise ValueError("plan.plug must be a tensor on the handle's GPU (PlantPlan.to_device)")
+        _want(plan.plug, "plan.plug", _I4, (B, N) if plan.plug.dim() == 2 else (plan.plug.shape[0], B, N), here)
+        if plan.plug.dim() == 3 and not 0 <= (0 if plug_row is None else int(plug_row)) < plan.plug.shape[0]:
+            raise ValueError("plug_row is outside plan.plug")
+        for k in ("t_room", "t_amps", "t_knee", "t_slope"):
+            _want(getattr(plan, k), "plan." + k, _F8, (R,), here)
+        for k in ("s_off", "s_len"):
+            _want(getattr(cur, k), "cur." + k, _I4, (B, K, N), here)
+        for t, name, dt, shape in ((pilots, "pilots", _F8, (B, N)), (bat, "bat", _I4, (B, N)), (room, "room", _F8, (B, N)),
+                                   (actual, "actual", _F8, (B, N)), (flags, "flags", _I4, (B,)), (status, "status", _I4, (B,))):
+            if t is None and name != "status":
+                raise ValueError(f"{name} is required")
+            _want(t, name, dt, shape, here)
+        p = _Problems(B, cur.Tm, K, s_off=_dptr(cur.s_off), s_len=_dptr(cur.s_len))
+        _check(self._lib.acnqp_plant_device(self._h, C.byref(p), _dptr(pilots), _dptr(status), *plan._args(plug_row), _dptr(bat), _dptr(room),
+                                            _dptr(actual), _dptr(flags), C.c_void_p(stream)), "acnqp_plant_device")
 
     def _kernel_ms_of_call(self) -> float:
         """Sum of the HIP-event durations of the launches since the previous ``kernel_times`` call; NaN when an event

@@ -1,4 +1,4 @@
-// The post-solve entries (dual report, pilot signals, time passes, before the solve): argument checks, _device entries, _host entries.  A
+// The post-solve entries (dual report, pilot signals, time passes, before the solve, the plant): argument checks, _device entries, _host entries.  A
 // host entry is a TABLE of the arrays it stages and a body that rebuilds the argument structs on staging addresses and
 // calls the _device entry; ONE planner lays the table out and ONE loop (run_staged) moves it.
 // Part 1 (table row, planner, overlap predicate) is plain host code: tests/test_post_stage.py compiles it with the host
@@ -471,6 +471,79 @@ int acnqp_prepare_host(acnqp_handle* h, const acnqp_problems* c, const acnqp_pre
     pc.key = dev(KEY); pc.cre = dev(CRE); pc.cim = dev(CIM); pc.limits = dev(LIM); pc.min_pilot = dev(MINP);
     acnqp_prepare_view vc{dev(VE), dev(VA), dev(VC)};
     return acnqp_prepare_device(h, &cc, &pc, dev(LB), dev(UB), &vc, dev(FLG), h->slot[0].st);
+  });
+}
+
+// ---- the plant (acn_qp_plant.hpp) ---------------------------------------------------------------------------------------
+static int check_plant_args(const acnqp_handle* h, const acnqp_problems* c, const double* pilots, const int32_t* status, int32_t n_batteries,
+                            const double* t_room, const double* t_amps, const double* t_knee, const double* t_slope, const int32_t* plug,
+                            const int32_t* bat, const double* room, const double* actual, const int32_t* flags, const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!c) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  if (c->k_sessions != 1) return fail(ACNQP_ERR_INVALID, w + ": k_sessions must be 1 (online MPC: one session per EVSE)");
+  if (c->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (n_batteries < 0) return fail(ACNQP_ERR_INVALID, w + ": negative n_batteries");
+  if (n_batteries > 0 && (!t_room || !t_amps || !t_knee || !t_slope))
+    return fail(ACNQP_ERR_INVALID, w + ": n_batteries is " + std::to_string(n_batteries) + " but t_room, t_amps, t_knee or t_slope is null");
+  if (c->batch == 0) return ACNQP_OK;
+  const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, R = (size_t)n_batteries;
+  if (B * N > ((size_t)1 << 31)) return fail(ACNQP_ERR_INVALID, w + ": batch too large");
+  if (!c->s_off || !c->s_len || !pilots || !plug || !bat || !room || !actual || !flags)
+    return fail(ACNQP_ERR_INVALID, w + ": null slot array, pilots, plug, bat, room, actual or flags");
+  struct Span { const void* p; size_t n; const char* name; };
+  const Span in[] = {{c->s_off, B * N * 4, "s_off"}, {c->s_len, B * N * 4, "s_len"}, {pilots, B * N * 8, "pilots"}, {status, B * 4, "status"},
+                     {t_room, R * 8, "t_room"}, {t_amps, R * 8, "t_amps"}, {t_knee, R * 8, "t_knee"}, {t_slope, R * 8, "t_slope"},
+                     {plug, B * N * 4, "plug"}};
+  const Span out[] = {{bat, B * N * 4, "bat"}, {room, B * N * 8, "room"}, {actual, B * N * 8, "actual"}, {flags, B * 4, "flags"}};
+  const size_t n_out = sizeof(out) / sizeof(out[0]);
+  for (size_t a = 0; a < n_out; ++a) {
+    for (const Span& s : in)
+      if (acnqp::spans_meet(out[a].p, out[a].n, s.p, s.n))
+        return fail(ACNQP_ERR_INVALID, w + ": an output aliases an input (" + out[a].name + " overlaps " + s.name + ")");
+    for (size_t b2 = a + 1; b2 < n_out; ++b2)
+      if (acnqp::spans_meet(out[a].p, out[a].n, out[b2].p, out[b2].n))
+        return fail(ACNQP_ERR_INVALID, w + ": two outputs overlap (" + out[a].name + " and " + out[b2].name + ")");
+  }
+  return ACNQP_OK;
+}
+
+int acnqp_plant_device(acnqp_handle* h, const acnqp_problems* c, const double* pilots, const int32_t* status, int32_t n_batteries,
+                       const double* t_room, const double* t_amps, const double* t_knee, const double* t_slope, const int32_t* plug,
+                       int32_t* bat, double* room, double* actual, int32_t* flags, void* hip_stream) {
+  const int rc = check_plant_args(h, c, pilots, status, n_batteries, t_room, t_amps, t_knee, t_slope, plug, bat, room, actual, flags,
+                                  "acnqp_plant_device");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  acnqp::PlantArgs a;
+  a.B = c->batch; a.N = h->shape.N; a.R = n_batteries;
+  a.s_off = c->s_off; a.s_len = c->s_len; a.pilots = pilots; a.status = status;
+  a.t_room = t_room; a.t_amps = t_amps; a.t_knee = t_knee; a.t_slope = t_slope; a.plug = plug;
+  a.bat = bat; a.room = room; a.actual = actual; a.flags = flags;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_plant(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("plant kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_plant_host(acnqp_handle* h, const acnqp_problems* c, const double* pilots, const int32_t* status, int32_t n_batteries,
+                     const double* t_room, const double* t_amps, const double* t_knee, const double* t_slope, const int32_t* plug,
+                     int32_t* bat, double* room, double* actual, int32_t* flags) {
+  const int rc = check_plant_args(h, c, pilots, status, n_batteries, t_room, t_amps, t_knee, t_slope, plug, bat, room, actual, flags,
+                                  "acnqp_plant_host");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t N = (size_t)h->shape.N, R = (size_t)n_batteries;
+  enum { TROOM, TAMPS, TKNEE, TSLOPE, SOFF, SLEN, PIL, STAT, PLUG, BAT, ROOM, ACT, FLG, NARR };
+  const S arr[NARR] = {S::plan(t_room, R * 8), S::plan(t_amps, R * 8), S::plan(t_knee, R * 8), S::plan(t_slope, R * 8),
+                       S::in(c->s_off, N * 4), S::in(c->s_len, N * 4), S::in(pilots, N * 8), S::in(status, status ? 4 : 0), S::in(plug, N * 4),
+                       S::inout(bat, N * 4), S::inout(room, N * 8), S::out(actual, N * 8), S::out(flags, 4)};
+  return run_staged(h, arr, NARR, (size_t)c->batch, [&](size_t, size_t nb, auto dev) {
+    acnqp_problems cc = *c;
+    cc.batch = (int32_t)nb;
+    cc.s_off = dev(SOFF); cc.s_len = dev(SLEN);
+    return acnqp_plant_device(h, &cc, dev(PIL), dev(STAT), n_batteries, dev(TROOM), dev(TAMPS), dev(TKNEE), dev(TSLOPE), dev(PLUG), dev(BAT),
+                              dev(ROOM), dev(ACT), dev(FLG), h->slot[0].st);
   });
 }
 

@@ -37,6 +37,9 @@ class RolloutResult:
     visits: Optional[np.ndarray] = None          # (steps, B) int32 visits of the reallocation's round robin (reallocate=True)
     prepare_flags: Optional[np.ndarray] = None   # (steps, B) int32 flags of acnqp_prepare_device (a session_order was stated)
     energy_cost: Optional[np.ndarray] = None     # (B,) sum over s, i of pilots[s, b, i] * weight[i] * series[b][s]; None without a clock cost
+    actual: Optional[np.ndarray] = None          # (steps, B, N) what the EVs drew of the pilots (a fleet carries batteries); then
+                                                 # ``delivered`` and ``energy_cost`` are computed from it, not from ``pilots``
+    plant_flags: Optional[np.ndarray] = None     # (steps, B) int32 flags of acnqp_plant_device (a fleet carries batteries)
 
 
 class FleetTable:
@@ -64,7 +67,13 @@ class FleetTable:
     minimum-rate walk and reallocation read, and the slot state does not carry: ``"fleet"`` (a session stands where its record
     stands in its fleet), ``"arrival"`` (plug-in order: the rank of (arrival, fleet index), with the EV's true arrival also
     when it lies before ``start_time``) or None.  ``order_keys`` (steps, B, N) int32 then holds, for every step and EVSE, the
-    position of the record whose stay covers that step (the ``key`` of ``acnqp_prepare_plan``); None without an order."""
+    position of the record whose stay covers that step (the ``key`` of ``acnqp_prepare_plan``); None without an order.
+    A record may carry ``battery``: a dict with ``capacity`` and ``init_charge`` (kWh), ``max_power`` (kW) and optionally
+    ``transition_soc`` (absent or None: an ideal battery; a fraction strictly inside (0, 1): the two-stage battery, whose
+    accepted rate falls in proportion to the room left once the state of charge has passed it).  ``has_plant`` says whether
+    any record does; ``plant_plan`` is then the battery table and the plug-in rows of ``acnqp_plant_device`` (include/acn_qp.h,
+    "the plant"): one table row per admitted record -- a record without ``battery`` gets the "no battery model" row -- and
+    ``plug`` (steps, B, N) int32, the record's row at the step it becomes visible, -1 elsewhere.  None without a battery."""
 
     ORDERS = ("fleet", "arrival")
 
@@ -90,6 +99,8 @@ class FleetTable:
         max_pilot = np.asarray(infrastructure.max_pilot, float)
         index = {s: i for i, s in enumerate(infrastructure.station_ids)}
         recs = []   # (visible step, scenario, evse, len, cap, min rates, max rates)
+        rows = []   # the battery table: (t_room, t_amps, t_knee, t_slope) of every record admitted, in the order of _stays
+        self.has_plant = any(ev.get("battery") is not None for fleet in self.fleets for ev in fleet)
         self._stays = []   # (scenario, evse, first step, end step, fleet index, arrival) of every record admitted
         self.windows = []   # per scenario: (evse, first step, end step) of every EV, relative to start (clipped to the run)
         longest = 1
@@ -101,6 +112,7 @@ class FleetTable:
                 tv = max(arr, self.start)
                 ln = dep - tv
                 wins.append((i, tv - self.start, dep - self.start))
+                row = self._battery_row(ev.get("battery"), b, n, ev, volt[i], self.kwh_per_amp_period[i])
                 cap = float(ev["requested"]) / self.kwh_per_amp_period[i]
                 if ln <= 0 or tv >= self.start + self.steps or cap <= self.done_tol:
                     continue
@@ -120,9 +132,17 @@ class FleetTable:
                     raise ValueError("max_rate must be finite (the site gives no max_pilot for this EVSE)")
                 recs.append((tv - self.start, b, i, ln, cap, rates[0], rates[1]))
                 self._stays.append((b, i, tv - self.start, dep - self.start, n, arr))
+                rows.append(row)
                 longest = max(longest, ln)
             self.windows.append(wins)
         self.order_keys = None if session_order is None else self.keys_for(session_order)
+        self.plant_plan = None
+        if self.has_plant:
+            plug = np.full((self.steps, self.B, self.N), -1, np.int32)
+            for r, (b, i, lo, _, _, _) in enumerate(self._stays):
+                plug[lo, b, i] = r
+            t = np.array(rows, np.float64).reshape(len(rows), 4)
+            self.plant_plan = backend.PlantPlan(*(np.ascontiguousarray(t[:, k]) for k in range(4)), plug)
         self.Tm = int(t_max) if t_max is not None else longest
         if self.Tm < longest:
             raise ValueError(f"t_max = {self.Tm} is shorter than the longest stay ({longest} periods)")
@@ -186,6 +206,33 @@ class FleetTable:
             a_seg=a_seg, a_evse=np.array([r[2] for r in recs], np.int32), a_slot=np.zeros(A, np.int32), a_len=lens,
             a_cap=np.array([r[4] for r in recs], np.float64), a_rate_seg=rate_seg, a_min=cat(5), a_max=cat(6),
             c_coef=self.c_coef, c_weight=self.c_weight, c_series=self.c_series)
+
+    NO_BATTERY = (np.inf, np.inf, 0.0, 0.0)   # the table row "no battery model": the EV draws what it is offered
+
+    @classmethod
+    def _battery_row(cls, bat, b, n, ev, voltage, kwh_per_amp_period):
+        """(t_room, t_amps, t_knee, t_slope) of a record's ``battery`` in the units of the slot state (A, A-periods): the
+        division of the tail's slope is done here, once; the device multiplies.  Every battery is validated, admitted or not."""
+        if bat is None:
+            return cls.NO_BATTERY
+        who = f"scenario {b}, EV {n} ({ev.get('sid', ev['station'])}): battery"
+        try:
+            cap, init, power = (float(bat[k]) for k in ("capacity", "init_charge", "max_power"))
+        except (KeyError, TypeError, ValueError) as exc:
+            raise ValueError(f"{who} needs numbers capacity, init_charge (kWh) and max_power (kW)") from exc
+        soc = bat.get("transition_soc")
+        if not (np.isfinite(cap) and cap > 0):
+            raise ValueError(f"{who}: capacity must be finite and > 0, not {cap!r}")
+        if not 0 <= init <= cap:
+            raise ValueError(f"{who}: init_charge must lie in [0, capacity], not {init!r}")
+        if not (np.isfinite(power) and power > 0):
+            raise ValueError(f"{who}: max_power must be finite and > 0, not {power!r}")
+        if soc is not None and not 0 < float(soc) < 1:
+            raise ValueError(f"{who}: transition_soc must lie strictly inside (0, 1) or be None, not {soc!r}")
+        t_room = max(cap - init, 0.0) / kwh_per_amp_period
+        t_amps = power * 1000 / voltage
+        t_knee = (1 - float(soc)) * cap / kwh_per_amp_period if soc is not None else 0.0
+        return (t_room, t_amps, t_knee, t_amps / t_knee if t_knee > 0 else 0.0)
 
     @staticmethod
     def _split_clock_cost(objective):
@@ -268,7 +315,8 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
     from .postprocessing import pilot_plan_arrays
 
     for on, why in ((alg.reallocate, "reallocate=True: the round robin breaks ties by session-list order, which the slot state does not carry"),
-                    (alg.estimate_max_rate, "estimate_max_rate: per-step pre-processing that reads the evolving state"),
+                    (alg.estimate_max_rate, "estimate_max_rate: per-step pre-processing that reads the evolving state (it waits for an "
+                                            "estimator of what each battery accepts; the plant it would read is served: ``battery``)"),
                     (alg.uninterrupted_charging, "uninterrupted_charging: per-step pre-processing that reads the evolving state")):
         if on and (session_order is None or why.startswith("estimate_max_rate")):
             raise ValueError(f"simulate_batch does not serve {why}")
@@ -345,6 +393,14 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
         wx = torch.zeros((B, N, Tm), dtype=torch.float64, device=dev) if want_y else None
         wy = torch.zeros((B, site.Mg, Tm), dtype=torch.float64, device=dev) if want_y else None
         nothing = torch.zeros((B, N), dtype=torch.float64, device=dev)
+        # a battery per EV (the plant): what is drawn of the pilots goes to the advance, not the pilots themselves
+        actual = plflags = None
+        if table.has_plant:
+            plplan = table.plant_plan.to_device(dev)
+            bat = torch.full((B, N), -1, dtype=torch.int32, device=dev)
+            room = torch.zeros((B, N), dtype=torch.float64, device=dev)
+            actual = torch.zeros((steps, B, N), dtype=torch.float64, device=dev)
+            plflags = torch.zeros((steps, B), dtype=torch.int32, device=dev)
         # the first period's problems: time "passes" on an empty state, its arrivals are admitted
         handle.advance_device(bufs[1], bufs[0], nothing, plan, -1, flags[0], use_status=False, stream=stream, seg_row=0)
         prepare(bufs[0], 0)
@@ -353,6 +409,8 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             warm = want_y and s > 0   # (a site without rows has no multipliers to carry: it starts cold)
             handle.solve_device(cur, options, stream=stream, warm_x=wx if warm else None, warm_y=wy if warm else None)
             handle.pilots_device(pplan, cur.x, first=pilots[s], visits=visits[s] if realloc else None, stream=stream)
+            if actual is not None:
+                handle.plant_device(cur, plplan, pilots[s], bat, room, actual[s], plflags[s], status=cur.status, plug_row=s, stream=stream)
             status[s].copy_(cur.status)
             iters[s].copy_(cur.iters)
             if xs is not None:
@@ -360,7 +418,7 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             if observer is not None:
                 observer(s, cur, pilots[s])
             if s + 1 < steps:
-                handle.advance_device(cur, nxt, pilots[s], plan, s, flags[s + 1], use_status=True, warm_x=wx,
+                handle.advance_device(cur, nxt, pilots[s] if actual is None else actual[s], plan, s, flags[s + 1], use_status=True, warm_x=wx,
                                       warm_y=wy, stream=stream, seg_row=s + 1)
                 prepare(nxt, s + 1)
         torch.cuda.synchronize(dev)
@@ -372,6 +430,7 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             s_bad, b_bad = (int(v[0]) for v in np.nonzero(vis < 0))
             raise ValueError(f"step {s_bad}, scenario {b_bad}: allowable pilots end below a session's cap; the reallocation of the "
                              "rounding loss would never end")
-        return RolloutResult(p, st, iters.cpu().numpy(), flags.cpu().numpy(), table.delivered(p),
+        drawn = p if actual is None else actual.cpu().numpy()   # (the plant draws nothing in a step that did not solve)
+        return RolloutResult(p, st, iters.cpu().numpy(), flags.cpu().numpy(), table.delivered(drawn),
                              None if xs is None else xs.cpu().numpy(), vis, None if pflags is None else pflags.cpu().numpy(),
-                             table.energy_cost(p))
+                             table.energy_cost(drawn), None if actual is None else drawn, None if plflags is None else plflags.cpu().numpy())

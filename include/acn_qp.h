@@ -645,6 +645,56 @@ int acnqp_prepare_device(acnqp_handle* h, const acnqp_problems* cur, const acnqp
 int acnqp_prepare_host(acnqp_handle* h, const acnqp_problems* cur, const acnqp_prepare_plan* plan, double* lb, double* ub,
                        acnqp_prepare_view* view, int32_t* flags);
 
+/* ---- the plant (additive to ABI v10: new symbols only, no new struct) ---------------------------------------------------
+ * What every EV DRAWS of the pilot it is offered.  The advance's rule 1 takes `applied` as delivered; a closed loop that
+ * hands it the pilots themselves models an EV that draws exactly what it is offered.  This entry puts a battery per EV in
+ * between: a current limit, the room left to full and, in the two-stage model, a tail in which the accepted rate falls in
+ * proportion to that room (acnportal's Battery and Linear2StageBattery in their stepwise form, as recalled: its rate cap
+ * (1 - soc) / (1 - transition_soc) * max_power once soc >= transition_soc is room / knee * amps in the units below).
+ * Units are the slot state's: amperes and ampere-periods.  K = 1 only (online MPC: one session per EVSE).
+ * The caller owns a read-only battery TABLE of n_batteries rows, computed once per EV:
+ *    t_room[r]   room left at plug-in, A-periods        t_amps[r]   the battery's current limit, A
+ *    t_knee[r]   room at which the tail begins, or 0 for a battery without one (ideal)
+ *    t_slope[r]  t_amps[r] / t_knee[r] where t_knee > 0, else 0 -- divided by the caller, once: the entry never divides
+ * A row with t_room = t_amps = +inf and t_knee = 0 is "no battery model": it draws what it is offered.
+ * The state is bat[e] (the row of the battery on EVSE i of problem b, e = b*N + i; -1: none) and room[e].
+ * For every (b, i), in this order:
+ *    1  plug:    r = plug[e].  r < 0: nothing changes.  0 <= r < n_batteries: bat[e] = r, room[e] = t_room[r].
+ *                r >= n_batteries: ignored, flag ACNQP_PLANT_BAD_PLUG.
+ *    2  offer:   p = pilots[e] when the slot is present (s_len[e] > 0 and s_off[e] == 0), status is NULL or status[b] is
+ *                SOLVED or SOLVED_INACCURATE, and pilots[e] > 0; else p = 0 (rule 1 of the advance: time passes,
+ *                nothing is delivered).
+ *    3  draw:    r = bat[e] as rule 1 left it.  r < 0: a = p.  r >= n_batteries: a = p, flag ACNQP_PLANT_BAD_BATTERY (the
+ *                entry leaves such a bat[e] and its room[e] as they came).  Otherwise
+ *                  lim = t_amps[r];  where t_knee[r] > 0 and room[e] <= t_knee[r]:  lim = min(lim, room[e] * t_slope[r])
+ *                  a = max(min(p, lim, room[e]), 0);  room[e] = room[e] - a
+ *                -- comparisons, ONE product and ONE subtraction, each rounded once (no fused multiply-add).
+ *    4  output:  actual[e] = a; bat[e] and room[e] are written back.
+ *    5  flags[b] is written for every problem, 0 when nothing was flagged.
+ * tests/plant_spec.py states the rules in plain loops and the library returns its bits.  No atomics; every output element
+ * is written whatever the input; a problem gives the same bits alone and at any position of any batch.  Inputs are
+ * finite or +inf: the library is built without NaN semantics, a NaN pilot is not served.                               */
+#define ACNQP_PLANT_BAD_PLUG 1      /* flags: plug[e] >= n_batteries (ignored)                                          */
+#define ACNQP_PLANT_BAD_BATTERY 2   /* flags: bat[e] >= n_batteries (drawn as if there were no battery)                 */
+
+/* acnqp_plant_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns without
+ * synchronising.  cur: batch, k_sessions (must be 1), s_off and s_len are read.  pilots, plug, bat, room, actual: [B*N];
+ * status: [B] or NULL; the four tables: [n_batteries]; flags: [B].  Refused with ACNQP_ERR_INVALID and acnqp_last_error
+ * set, before any device work: a null handle or required pointer, k_sessions != 1, a negative batch or n_batteries,
+ * n_batteries > 0 with a null table, an output (bat, room, actual, flags) that overlaps an input or another output.
+ * batch == 0 returns ACNQP_OK.                                                                                       */
+int acnqp_plant_device(acnqp_handle* h, const acnqp_problems* cur, const double* pilots, const int32_t* status,
+                       int32_t n_batteries, const double* t_room, const double* t_amps, const double* t_knee,
+                       const double* t_slope, const int32_t* plug, int32_t* bat, double* room, double* actual,
+                       int32_t* flags, void* hip_stream);
+
+/* acnqp_plant_host -- the same with host pointers, synchronous; a large batch is processed in chunks (the tables are
+ * uploaded once per call).  Same bits as the device entry, at any chunking.                                         */
+int acnqp_plant_host(acnqp_handle* h, const acnqp_problems* cur, const double* pilots, const int32_t* status,
+                     int32_t n_batteries, const double* t_room, const double* t_amps, const double* t_knee,
+                     const double* t_slope, const int32_t* plug, int32_t* bat, double* room, double* actual,
+                     int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif
