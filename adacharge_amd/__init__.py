@@ -33,5 +33,6 @@ from .postprocessing import (  # noqa: F401
     project_into_discrete_feasible_pilots,
 )
 from .utils import infrastructure_constraints_feasible  # noqa: F401
+from .acn import SimpleRampdown  # noqa: F401  (the estimator estimate_max_rate=True reads; acnportal is not a dependency)
 
 __version__ = "0.1.0"

@@ -159,6 +159,16 @@ class Interface:
     def current_time(self):
         return self.data.get("current_time", 0)
 
+    @property
+    def last_applied_pilot_signals(self) -> Dict:
+        """{station_id: A} the pilots of the period before (read by ``SimpleRampdown``)"""
+        return self.data.get("last_applied_pilot_signals", {})
+
+    @property
+    def last_actual_charging_rate(self) -> Dict:
+        """{station_id: A} what the EVs drew in the period before (read by ``SimpleRampdown``)"""
+        return self.data.get("last_actual_charging_rate", {})
+
     def active_sessions(self) -> List[SessionInfo]:
         sessions = self.data.get("active_sessions", [])
         out = []
@@ -314,6 +324,60 @@ def apply_upper_bound_estimate(ub_estimator, active_sessions):
         )
         reconcile_max_and_min(session)
     return new_sessions
+
+
+class SimpleRampdown:
+    """acnportal.algorithms.upper_bound_estimator.SimpleRampdown [recalled]: the estimator of what each EV accepts that
+    ``estimate_max_rate=True`` reads (``max_rate_estimator=``, ada.py:143-146).  tests/estimate_spec.py is the definition
+    (rules 3 and 4 of include/acn_qp.h, "the ramp-down estimator"), and this class does its arithmetic on Python floats in
+    the same order: the device closed loop (``simulate_batch``) and a host loop with this object keep the same bounds.
+
+    A session seen for the first time gets its own ``max_rates[0]``; after that its bound follows what the EV drew: when it
+    drew more than ``down_threshold`` less than its pilot, the bound becomes what it drew plus ``up_increment``; otherwise,
+    when it drew within ``up_threshold`` of the bound, the bound rises by ``up_increment``.  All three in amperes.  The
+    thresholds may be infinite (``down_threshold=inf, up_threshold=-inf``: the bound never moves).
+    History comes from the interface: ``last_applied_pilot_signals`` and ``last_actual_charging_rate``, dicts by station id
+    (a station that is missing counts as 0 A)."""
+
+    def __init__(self, up_threshold: float = 1.0, down_threshold: float = 1.0, up_increment: float = 1.0):
+        up_threshold, down_threshold, up_increment = float(up_threshold), float(down_threshold), float(up_increment)
+        if up_threshold != up_threshold or down_threshold != down_threshold:
+            raise ValueError("up_threshold and down_threshold must not be NaN")
+        if not (np.isfinite(up_increment) and up_increment >= 0):
+            raise ValueError(f"up_increment must be finite and >= 0, not {up_increment!r}")
+        self.up_threshold, self.down_threshold, self.up_increment = up_threshold, down_threshold, up_increment
+        self.upper_bounds: Dict = {}   # session id -> bound, A
+        self._interface = None
+
+    @property
+    def interface(self):
+        if self._interface is not None:
+            return self._interface
+        raise NotImplementedError("No interface has been registered yet. Please call register_interface prior to using the estimator.")
+
+    def register_interface(self, interface) -> None:
+        self._interface = interface
+
+    def get_maximum_rates(self, sessions) -> Dict:
+        """{session_id: bound} for ``sessions``, and the estimator's state moves on one period"""
+        offered = self.interface.last_applied_pilot_signals
+        drawn = self.interface.last_actual_charging_rate
+        out = {}
+        for session in sessions:
+            sid = session.session_id
+            if sid not in self.upper_bounds:                       # first sight: no history is read
+                u = float(session.max_rates[0])
+            else:
+                u = self.upper_bounds[sid]
+                pp = float(offered.get(session.station_id, 0.0))
+                pp = pp if pp > 0.0 else 0.0
+                pr = float(drawn.get(session.station_id, 0.0))
+                if pp - pr > self.down_threshold:
+                    u = pr + self.up_increment
+                elif u - pr < self.up_threshold:
+                    u = u + self.up_increment
+            self.upper_bounds[sid] = out[sid] = u
+        return out
 
 
 def remaining_amp_periods(session, infrastructure, period) -> float:

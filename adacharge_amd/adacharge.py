@@ -267,12 +267,19 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         ``solve_device -> pilots_device (first period) -> advance_device``, with no host synchronisation inside the loop; an
         EV becomes visible at its arrival step (online MPC, one session per EVSE).  Returns a ``rollout.RolloutResult``:
         ``pilots (steps, B, N)``, ``status``, ``iters`` and ``flags (steps, B)`` and the energy delivered to every EV, copied
-        back once at the end.  Serves continuous pilots and ``quantize=True``; ``reallocate``, ``estimate_max_rate`` and
+        back once at the end.  Serves continuous pilots and ``quantize=True``; ``reallocate`` and
         ``uninterrupted_charging`` raise ``ValueError`` -- unless the caller states the order of the session lists a plant
         would hand to ``schedule``, which those steps of the reference read and the device state does not carry:
         ``session_order="fleet"`` (a session stands where its record stands in its fleet) or ``"arrival"`` (plug-in order).
         Then ``uninterrupted_charging`` and ``reallocate`` are served (``acnqp_prepare_device`` between the advance and the
-        solve; the result carries ``visits`` and ``prepare_flags``); ``estimate_max_rate`` is refused either way.
+        solve; the result carries ``visits`` and ``prepare_flags``).
+        ``estimate_max_rate=True`` is served when ``max_rate_estimator`` is a ``SimpleRampdown`` (``adacharge_amd.SimpleRampdown``:
+        its rules run on the device, ``acnqp_estimate_device`` between the advance and the prepare step; it is per session and
+        needs no ``session_order``): each solve sees every session's bounds capped with the estimate of what its EV accepts,
+        moved on by what the EV drew of its last pilot, while the state keeps the session's own bounds.  The result carries
+        ``estimates (steps, B, N)`` -- the bound each solve saw, +inf where no session -- and ``estimate_flags (steps, B)``;
+        ``observer`` then receives a view of the state whose ``ub`` is the capped copy and whose ``own_ub`` is the state's.
+        With any other estimator, or none, ``estimate_max_rate`` raises ``ValueError``.
         One objective that reads the clock is served: ``tou_energy_cost`` (at most one component; keep it LAST in the list and
         every problem of the loop is the builder's bit for bit, ``rollout.FleetTable``).  The advance prices each new problem
         from ``interface.get_prices(steps + t_max, start_time)``, or from ``prices`` -- ``(P,)`` or ``(B, P)``, entry 0 the price
@@ -283,7 +290,7 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         the advance: a current limit, the room left to full and, past ``transition_soc``, a rate that falls with that room).
         The advance, the demand-charge floor, ``delivered`` and ``energy_cost`` then follow what was drawn, and the result
         carries ``actual (steps, B, N)`` and ``plant_flags (steps, B)``.  A rollout whose fleets carry no battery launches
-        and returns exactly what it did without the feature.  ``estimate_max_rate`` waits for an estimator on top of it.
+        and returns exactly what it did without the feature; so does one without the estimator.
         ``warm_start``: every solve but the first starts from the previous
         period's schedule and multipliers, shifted on the device.  ``observer(step, state, pilots)``: diagnostic hook called
         after each period's solve has been enqueued (it may synchronise and read the ``DeviceBatch``)."""

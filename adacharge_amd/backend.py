@@ -43,6 +43,7 @@ PILOTS_CONTINUOUS, PILOTS_DISCRETE, PILOTS_REALLOCATE = 0, 1, 2
 ADVANCE_REFUSED, ADVANCE_NO_ROW, ADVANCE_BAD_SLOT = 1, 2, 4
 PREPARE_FUTURE = 1
 PLANT_BAD_PLUG, PLANT_BAD_BATTERY = 1, 2
+ESTIMATE_BAD_FRESH, ESTIMATE_BAD_SLOT = 1, 2
 # kernel families of acnqp_route (ACNQP_ROUTE_* in include/acn_qp.h)
 ROUTE_NAMES = {1: "wave1", 2: "wave2", 3: "wave3", 4: "wave4", 5: "wave5", 6: "tiled_ct1", 7: "tiled_ct2",
                8: "long_lds", 9: "long_ws", 10: "stream", 11: "general"}
@@ -182,6 +183,8 @@ def _abi():
         ("acnqp_prepare", [h, P(_Problems), P(_PreparePlan), ptr, ptr, P(_PrepareView), ptr]),
         # cur, pilots, status, n_batteries, t_room, t_amps, t_knee, t_slope, plug, bat, room, actual, flags
         ("acnqp_plant", [h, P(_Problems), ptr, ptr, i32] + [ptr] * 9),
+        # cur, fresh, pilots, actual, status, up_threshold, down_threshold, up_increment, est, ub_out, flags
+        ("acnqp_estimate", [h, P(_Problems)] + [ptr] * 4 + [C.c_double] * 3 + [ptr] * 3),
     ):
         rows += [(stem + "_host", rc, args), (stem + "_device", rc, args + [stream])]
     introspection = [
@@ -970,6 +973,68 @@ class SiteHandle:
         p = _Problems(B, cur.Tm, K, s_off=_dptr(cur.s_off), s_len=_dptr(cur.s_len))
         _check(self._lib.acnqp_plant_device(self._h, C.byref(p), _dptr(pilots), _dptr(status), *plan._args(plug_row), _dptr(bat), _dptr(room),
                                             _dptr(actual), _dptr(flags), C.c_void_p(stream)), "acnqp_plant_device")
+
+    # -- the ramp-down estimator (acn_qp_estimate.hpp) ---------------------------------------------------------------------
+    def estimate_host(self, cur: dict, fresh, est, pilots=None, actual=None, status=None, up_threshold: float = 1.0,
+                      down_threshold: float = 1.0, up_increment: float = 1.0, fresh_row=None) -> dict:
+        """acnqp_estimate_host: the estimate ``est`` (B, N) of what the EVs of the state ``cur`` -- numpy arrays ``lb, ub``
+        (B, N, Tm) and ``s_off, s_len`` (B, 1, N) or (B, N) -- accept, moved on by the history of the period before: ``pilots``
+        (B, N) or None (no history), ``actual`` (B, N) or None (what was offered was drawn), ``status`` (B,) or None.  ``fresh``:
+        (B, N) int32, or (steps, B, N) with ``fresh_row``.  Returns ``est`` (a copy, moved on), ``ub`` (B, N, Tm), the bounds of
+        ``cur`` capped with it, and ``flags`` (B,)."""
+        lb, ub = _f8(cur["lb"]), _f8(cur["ub"])
+        off, ln, fr = _i4(cur["s_off"]), _i4(cur["s_len"]), _i4(fresh)
+        pil, act, stat = _f8(pilots), _f8(actual), _i4(status)
+        est = np.array(est, np.float64, order="C")   # a copy: the entry writes it
+        if ub.ndim != 3 or ub.shape[1] != self.site.N or lb.shape != ub.shape:
+            raise ValueError("cur needs lb, ub of shape (B, N, Tm) for the handle's site")
+        B, N, Tm = ub.shape
+        K = off.shape[1] if off.ndim == 3 else 1
+        if fr.ndim == 3:
+            fr = fr[0 if fresh_row is None else fresh_row]
+        if off.size != B * K * N or ln.size != off.size or fr.shape != (B, N) or est.shape != (B, N):
+            raise ValueError("cur needs s_off, s_len of shape (B, K, N); fresh needs one (B, N) block per step and est the shape (B, N)")
+        for a, name, shape in ((pil, "pilots", (B, N)), (act, "actual", (B, N)), (stat, "status", (B,))):
+            if a is not None and a.shape != shape:
+                raise ValueError(f"{name} must have the shape {shape}")
+        fr = np.ascontiguousarray(fr)
+        ub_out, flags = np.empty((B, N, Tm)), np.empty(B, np.int32)
+        p = _Problems(B, Tm, K, s_off=_ptr(off), s_len=_ptr(ln), lb=_ptr(lb), ub=_ptr(ub))
+        _check(self._lib.acnqp_estimate_host(self._h, C.byref(p), _ptr(fr), _ptr(pil), _ptr(act), _ptr(stat), float(up_threshold),
+                                             float(down_threshold), float(up_increment), _ptr(est), _ptr(ub_out), _ptr(flags)),
+               "acnqp_estimate_host")
+        return dict(est=est, ub=ub_out, flags=flags)
+
+    def estimate_device(self, cur: "DeviceBatch", fresh, est, ub_out, flags, pilots=None, actual=None, status=None, up_threshold: float = 1.0,
+                        down_threshold: float = 1.0, up_increment: float = 1.0, fresh_row=None, stream: int = 0) -> None:
+        """acnqp_estimate_device: ``est`` (B, N) float64 is moved on in place by the history of the period before -- ``pilots``,
+        ``actual`` (B, N) float64 and ``status`` (B,) int32, each may be None -- and ``ub_out`` (B, N, Tm) float64 receives
+        ``cur.ub`` capped with it (``cur.lb``, ``cur.ub`` are read only; ``ub_out`` must be another tensor); ``flags`` (B,)
+        int32.  ``fresh``: (B, N) int32, or (steps, B, N) with ``fresh_row``.  Asynchronous on ``stream``."""
+        import torch
+
+        here = torch.device("cuda", self.device)
+        B, N, Tm, K = cur.B, cur.N, cur.Tm, cur.K
+        if fresh is None or not hasattr(fresh, "dim"):
+            raise ValueError("fresh must be a tensor on the handle's GPU")
+        _want(fresh, "fresh", _I4, (B, N) if fresh.dim() == 2 else (fresh.shape[0], B, N), here)
+        row = 0
+        if fresh.dim() == 3:
+            row = 0 if fresh_row is None else int(fresh_row)
+            if not 0 <= row < fresh.shape[0]:
+                raise ValueError("fresh_row is outside fresh")
+        for k, shape in dict(lb=(B, N, Tm), ub=(B, N, Tm), s_off=(B, K, N), s_len=(B, K, N)).items():
+            _want(getattr(cur, k), "cur." + k, _PROBLEM_ARRAYS[k], shape, here)
+        for t, name, dt, shape in ((est, "est", _F8, (B, N)), (ub_out, "ub_out", _F8, (B, N, Tm)), (flags, "flags", _I4, (B,)),
+                                   (pilots, "pilots", _F8, (B, N)), (actual, "actual", _F8, (B, N)), (status, "status", _I4, (B,))):
+            if t is None and name in ("est", "ub_out", "flags"):
+                raise ValueError(f"{name} is required")
+            _want(t, name, dt, shape, here)
+        p = _Problems(B, Tm, K, s_off=_dptr(cur.s_off), s_len=_dptr(cur.s_len), lb=_dptr(cur.lb), ub=_dptr(cur.ub))
+        fr = C.c_void_p(fresh.data_ptr() + row * B * N * 4)
+        _check(self._lib.acnqp_estimate_device(self._h, C.byref(p), fr, _dptr(pilots), _dptr(actual), _dptr(status), float(up_threshold),
+                                               float(down_threshold), float(up_increment), _dptr(est), _dptr(ub_out), _dptr(flags),
+                                               C.c_void_p(stream)), "acnqp_estimate_device")
 
     def _kernel_ms_of_call(self) -> float:
         """Sum of the HIP-event durations of the launches since the previous ``kernel_times`` call; NaN when an event

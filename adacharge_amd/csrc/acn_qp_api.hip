@@ -1,6 +1,6 @@
 // Host side of the C ABI declared in include/acn_qp.h: the extern "C" entry points.  What they decide from a shape is
 // in acn_qp_route.hpp, the site upload in acn_qp_site.hpp, the host-buffer entries' chunk pipeline in acn_qp_pipeline.hpp,
-// the post-solve entries (duals, pilots, advance, prepare, plant) and their one staging loop in acn_qp_post.hpp.
+// the post-solve entries (duals, pilots, advance, prepare, plant, estimate) and their one staging loop in acn_qp_post.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include "acn_qp_advance.hpp"
 #include "acn_qp_prepare.hpp"
 #include "acn_qp_plant.hpp"
+#include "acn_qp_estimate.hpp"
 #include "acn_qp_site.hpp"
 
 namespace {

@@ -1,4 +1,4 @@
-// The post-solve entries (dual report, pilot signals, time passes, before the solve, the plant): argument checks, _device entries, _host entries.  A
+// The post-solve entries (dual report, pilot signals, time passes, before the solve, the plant, the estimator): argument checks, _device entries, _host entries.  A
 // host entry is a TABLE of the arrays it stages and a body that rebuilds the argument structs on staging addresses and
 // calls the _device entry; ONE planner lays the table out and ONE loop (run_staged) moves it.
 // Part 1 (table row, planner, overlap predicate) is plain host code: tests/test_post_stage.py compiles it with the host
@@ -544,6 +544,76 @@ int acnqp_plant_host(acnqp_handle* h, const acnqp_problems* c, const double* pil
     cc.s_off = dev(SOFF); cc.s_len = dev(SLEN);
     return acnqp_plant_device(h, &cc, dev(PIL), dev(STAT), n_batteries, dev(TROOM), dev(TAMPS), dev(TKNEE), dev(TSLOPE), dev(PLUG), dev(BAT),
                               dev(ROOM), dev(ACT), dev(FLG), h->slot[0].st);
+  });
+}
+
+// ---- the ramp-down estimator (acn_qp_estimate.hpp) ------------------------------------------------------------------------
+static int check_estimate_args(const acnqp_handle* h, const acnqp_problems* c, const int32_t* fresh, const double* pilots, const double* actual,
+                               const int32_t* status, const double* est, const double* ub_out, const int32_t* flags, const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!c) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  if (c->k_sessions != 1) return fail(ACNQP_ERR_INVALID, w + ": k_sessions must be 1 (online MPC: one session per EVSE)");
+  if (c->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (actual && !pilots) return fail(ACNQP_ERR_INVALID, w + ": actual is given without pilots");
+  if (c->batch == 0) return ACNQP_OK;
+  if (c->t_max < 1 || c->t_max > 4096) return fail(ACNQP_ERR_INVALID, w + ": t_max must be in [1, 4096]");
+  const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, Tm = (size_t)c->t_max;
+  if (B * N > ((size_t)1 << 31) || B * N * Tm > ((size_t)1 << 40)) return fail(ACNQP_ERR_INVALID, w + ": batch too large");
+  if (!c->s_off || !c->s_len || !c->lb || !c->ub || !fresh || !est || !ub_out || !flags)
+    return fail(ACNQP_ERR_INVALID, w + ": null slot array, lb, ub, fresh, est, ub_out or flags");
+  struct Span { const void* p; size_t n; const char* name; };
+  const size_t nb = B * N * Tm * 8;
+  const Span in[] = {{c->s_off, B * N * 4, "s_off"}, {c->s_len, B * N * 4, "s_len"}, {c->lb, nb, "lb"}, {c->ub, nb, "ub"}, {fresh, B * N * 4, "fresh"},
+                     {pilots, B * N * 8, "pilots"}, {actual, B * N * 8, "actual"}, {status, B * 4, "status"}};
+  const Span out[] = {{est, B * N * 8, "est"}, {ub_out, nb, "ub_out"}, {flags, B * 4, "flags"}};
+  const size_t n_out = sizeof(out) / sizeof(out[0]);
+  for (size_t a = 0; a < n_out; ++a) {
+    for (const Span& s : in)
+      if (acnqp::spans_meet(out[a].p, out[a].n, s.p, s.n))
+        return fail(ACNQP_ERR_INVALID, w + ": an output aliases an input (" + out[a].name + " overlaps " + s.name + ")");
+    for (size_t b2 = a + 1; b2 < n_out; ++b2)
+      if (acnqp::spans_meet(out[a].p, out[a].n, out[b2].p, out[b2].n))
+        return fail(ACNQP_ERR_INVALID, w + ": two outputs overlap (" + out[a].name + " and " + out[b2].name + ")");
+  }
+  return ACNQP_OK;
+}
+
+int acnqp_estimate_device(acnqp_handle* h, const acnqp_problems* c, const int32_t* fresh, const double* pilots, const double* actual,
+                          const int32_t* status, double up_threshold, double down_threshold, double up_increment, double* est, double* ub_out,
+                          int32_t* flags, void* hip_stream) {
+  const int rc = check_estimate_args(h, c, fresh, pilots, actual, status, est, ub_out, flags, "acnqp_estimate_device");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  acnqp::EstimateArgs a;
+  a.B = c->batch; a.N = h->shape.N; a.Tm = c->t_max;
+  a.s_off = c->s_off; a.s_len = c->s_len; a.lb = c->lb; a.ub = c->ub;
+  a.fresh = fresh; a.pilots = pilots; a.actual = actual; a.status = status;
+  a.up_threshold = up_threshold; a.down_threshold = down_threshold; a.up_increment = up_increment;
+  a.est = est; a.ub_out = ub_out; a.flags = flags;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_estimate(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("estimate kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_estimate_host(acnqp_handle* h, const acnqp_problems* c, const int32_t* fresh, const double* pilots, const double* actual,
+                        const int32_t* status, double up_threshold, double down_threshold, double up_increment, double* est, double* ub_out,
+                        int32_t* flags) {
+  const int rc = check_estimate_args(h, c, fresh, pilots, actual, status, est, ub_out, flags, "acnqp_estimate_host");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t N = (size_t)h->shape.N, nv = N * (size_t)c->t_max * 8;
+  enum { SOFF, SLEN, LB, UB, FRESH, PIL, ACT, STAT, EST, UBO, FLG, NARR };
+  const S arr[NARR] = {S::in(c->s_off, N * 4), S::in(c->s_len, N * 4), S::in(c->lb, nv), S::in(c->ub, nv), S::in(fresh, N * 4),
+                       S::in(pilots, pilots ? N * 8 : 0), S::in(actual, actual ? N * 8 : 0), S::in(status, status ? 4 : 0),
+                       S::inout(est, N * 8), S::out(ub_out, nv), S::out(flags, 4)};
+  return run_staged(h, arr, NARR, (size_t)c->batch, [&](size_t, size_t nb, auto dev) {
+    acnqp_problems cc = *c;
+    cc.batch = (int32_t)nb;
+    cc.s_off = dev(SOFF); cc.s_len = dev(SLEN); cc.lb = dev(LB); cc.ub = dev(UB);
+    return acnqp_estimate_device(h, &cc, dev(FRESH), dev(PIL), dev(ACT), dev(STAT), up_threshold, down_threshold, up_increment, dev(EST),
+                                 dev(UBO), dev(FLG), h->slot[0].st);
   });
 }
 

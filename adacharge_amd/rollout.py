@@ -14,6 +14,7 @@ loop: an EV becomes visible at its arrival step, so every EVSE carries one sessi
 """
 from __future__ import annotations
 
+import copy
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -40,6 +41,8 @@ class RolloutResult:
     actual: Optional[np.ndarray] = None          # (steps, B, N) what the EVs drew of the pilots (a fleet carries batteries); then
                                                  # ``delivered`` and ``energy_cost`` are computed from it, not from ``pilots``
     plant_flags: Optional[np.ndarray] = None     # (steps, B) int32 flags of acnqp_plant_device (a fleet carries batteries)
+    estimates: Optional[np.ndarray] = None       # (steps, B, N) the bound each solve saw (estimate_max_rate), +inf where no session
+    estimate_flags: Optional[np.ndarray] = None  # (steps, B) int32 flags of acnqp_estimate_device (estimate_max_rate)
 
 
 class FleetTable:
@@ -73,7 +76,8 @@ class FleetTable:
     accepted rate falls in proportion to the room left once the state of charge has passed it).  ``has_plant`` says whether
     any record does; ``plant_plan`` is then the battery table and the plug-in rows of ``acnqp_plant_device`` (include/acn_qp.h,
     "the plant"): one table row per admitted record -- a record without ``battery`` gets the "no battery model" row -- and
-    ``plug`` (steps, B, N) int32, the record's row at the step it becomes visible, -1 elsewhere.  None without a battery."""
+    ``plug`` (steps, B, N) int32, the record's row at the step it becomes visible, -1 elsewhere.  None without a battery.
+    ``fresh_rows()`` marks the same steps for ``acnqp_estimate_device`` ("the ramp-down estimator"), battery or not."""
 
     ORDERS = ("fleet", "arrival")
 
@@ -270,6 +274,14 @@ class FleetTable:
             keys[max(lo, 0): min(hi, self.steps), b, i] = n if session_order == "fleet" else pos[b, n]
         return keys
 
+    def fresh_rows(self) -> np.ndarray:
+        """(steps, B, N) int32: 1 at the step an admitted record becomes visible on its EVSE -- a session the estimator of
+        ``estimate_max_rate`` sees for the first time -- 0 elsewhere.  Built on demand: only such a rollout reads it."""
+        fresh = np.zeros((self.steps, self.B, self.N), np.int32)
+        for b, i, lo, _, _, _ in self._stays:
+            fresh[lo, b, i] = 1
+        return fresh
+
     def _refuse_clock_dependence(self, objective, infrastructure, interface, q_now):
         data = getattr(interface, "data", None)
         if not isinstance(data, dict):   # no clock to move: only components known not to read one
@@ -314,12 +326,17 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
     from .adaptive_charging_optimization import _site_handle
     from .postprocessing import pilot_plan_arrays
 
+    from .acn import SimpleRampdown
+
     for on, why in ((alg.reallocate, "reallocate=True: the round robin breaks ties by session-list order, which the slot state does not carry"),
-                    (alg.estimate_max_rate, "estimate_max_rate: per-step pre-processing that reads the evolving state (it waits for an "
-                                            "estimator of what each battery accepts; the plant it would read is served: ``battery``)"),
                     (alg.uninterrupted_charging, "uninterrupted_charging: per-step pre-processing that reads the evolving state")):
-        if on and (session_order is None or why.startswith("estimate_max_rate")):
+        if on and session_order is None:
             raise ValueError(f"simulate_batch does not serve {why}")
+    # the estimator of what each battery accepts: the one whose arithmetic the device does (acnqp_estimate_device)
+    ramp = alg.max_rate_estimator if alg.estimate_max_rate else None
+    if alg.estimate_max_rate and not isinstance(ramp, SimpleRampdown):
+        raise ValueError("simulate_batch serves estimate_max_rate with max_rate_estimator=SimpleRampdown(...) only (its rules run on the "
+                         f"device; any other estimator is Python code per step), not {type(ramp).__name__}")
     if session_order is not None and session_order not in FleetTable.ORDERS:
         raise ValueError(f'session_order must be "fleet", "arrival" or None, not {session_order!r}')
     if alg.constraint_type not in ("SOC", "LINEAR"):
@@ -401,11 +418,36 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             room = torch.zeros((B, N), dtype=torch.float64, device=dev)
             actual = torch.zeros((steps, B, N), dtype=torch.float64, device=dev)
             plflags = torch.zeros((steps, B), dtype=torch.int32, device=dev)
+        # an estimate per EV of what it accepts (estimate_max_rate): the solve, the prepare entry and the plant see a VIEW of the
+        # state whose ub is capped with it; the state keeps the session's own bounds, which the advance shifts
+        est = eflags = ests = None
+        if ramp is not None:
+            fresh = torch.from_numpy(table.fresh_rows()).to(dev)
+            est = torch.full((B, N), float("inf"), dtype=torch.float64, device=dev)
+            ests = torch.zeros((steps, B, N), dtype=torch.float64, device=dev)
+            eflags = torch.zeros((steps, B), dtype=torch.int32, device=dev)
+            capped = torch.zeros((B, N, Tm), dtype=torch.float64, device=dev)   # (one: everything is on one stream)
+
+        def estimate(state, row):
+            """the state the step's solve reads: ``state`` itself, or its view under the estimate moved on by step ``row - 1``"""
+            if ramp is None:
+                return state
+            past = row > 0
+            handle.estimate_device(state, fresh, est, capped, eflags[row], pilots=pilots[row - 1] if past else None,
+                                   actual=actual[row - 1] if past and actual is not None else None, status=status[row - 1] if past else None,
+                                   up_threshold=ramp.up_threshold, down_threshold=ramp.down_threshold, up_increment=ramp.up_increment,
+                                   fresh_row=row, stream=stream)
+            ests[row].copy_(est)
+            view = copy.copy(state)
+            view.own_ub, view.ub = state.ub, capped
+            return view
         # the first period's problems: time "passes" on an empty state, its arrivals are admitted
         handle.advance_device(bufs[1], bufs[0], nothing, plan, -1, flags[0], use_status=False, stream=stream, seg_row=0)
-        prepare(bufs[0], 0)
+        solve_next = estimate(bufs[0], 0)
+        prepare(solve_next, 0)
         for s in range(steps):
-            cur, nxt = bufs[s % 2], bufs[(s + 1) % 2]
+            state, nxt = bufs[s % 2], bufs[(s + 1) % 2]
+            cur = solve_next
             warm = want_y and s > 0   # (a site without rows has no multipliers to carry: it starts cold)
             handle.solve_device(cur, options, stream=stream, warm_x=wx if warm else None, warm_y=wy if warm else None)
             handle.pilots_device(pplan, cur.x, first=pilots[s], visits=visits[s] if realloc else None, stream=stream)
@@ -418,9 +460,10 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             if observer is not None:
                 observer(s, cur, pilots[s])
             if s + 1 < steps:
-                handle.advance_device(cur, nxt, pilots[s] if actual is None else actual[s], plan, s, flags[s + 1], use_status=True, warm_x=wx,
+                handle.advance_device(state, nxt, pilots[s] if actual is None else actual[s], plan, s, flags[s + 1], use_status=True, warm_x=wx,
                                       warm_y=wy, stream=stream, seg_row=s + 1)
-                prepare(nxt, s + 1)
+                solve_next = estimate(nxt, s + 1)
+                prepare(solve_next, s + 1)
         torch.cuda.synchronize(dev)
         p = pilots.cpu().numpy()
         st = status.cpu().numpy()
@@ -433,4 +476,5 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
         drawn = p if actual is None else actual.cpu().numpy()   # (the plant draws nothing in a step that did not solve)
         return RolloutResult(p, st, iters.cpu().numpy(), flags.cpu().numpy(), table.delivered(drawn),
                              None if xs is None else xs.cpu().numpy(), vis, None if pflags is None else pflags.cpu().numpy(),
-                             table.energy_cost(drawn), None if actual is None else drawn, None if plflags is None else plflags.cpu().numpy())
+                             table.energy_cost(drawn), None if actual is None else drawn, None if plflags is None else plflags.cpu().numpy(),
+                             None if ests is None else ests.cpu().numpy(), None if eflags is None else eflags.cpu().numpy())

@@ -695,6 +695,59 @@ int acnqp_plant_host(acnqp_handle* h, const acnqp_problems* cur, const double* p
                      const double* t_slope, const int32_t* plug, int32_t* bat, double* room, double* actual,
                      int32_t* flags);
 
+/* ---- the ramp-down estimator (additive to ABI v10: new symbols only, no new struct) ---------------------------------------
+ * The reference's estimate_max_rate (ada.py:143-146): an estimator of what each EV accepts caps the session's max_rates
+ * before the solve, then reconcile_max_and_min(choose_min = True).  The estimator is acnportal's SimpleRampdown, as
+ * recalled: an EV that drew clearly less than it was offered has its bound set to just above what it drew; an EV that
+ * draws all its bound allows has the bound raised by up_increment.  With the plant above, this closes the loop in which an
+ * EV in the tail of its battery stops holding infrastructure capacity it will not use.
+ * Units are the slot state's: amperes.  K = 1 only (online MPC: one session per EVSE).
+ * Parameters: up_threshold, down_threshold (either may be +-inf: with down_threshold = +inf and up_threshold = -inf the
+ * estimate never moves) and up_increment (finite, >= 0), in amperes.
+ * The state is est[e], the bound of the session on EVSE i of problem b, e = b*N + i; +inf where there is none.  It starts
+ * at +inf.  For every (b, i), in this order:
+ *    1  slot:    present = s_len[e] > 0 and s_off[e] == 0 and s_len[e] <= t_max.  Every other slot counts as absent: none
+ *                (s_len <= 0), one still to come (s_off > 0), and one whose window does not fit: s_len[e] > t_max, whatever
+ *                its s_off, flag ACNQP_ESTIMATE_BAD_SLOT.
+ *    2  absent:  est'[e] = +inf and ub_out[e][:] = ub[e][:], a copy.  fresh[e] != 0 here: flag ACNQP_ESTIMATE_BAD_FRESH.
+ *    3  first sight, present and fresh[e] != 0:  u = ub[e][0] -- the session's own max_rates[0] after enforce_pilot_limit.
+ *                No history is read.
+ *    4  update, present and not fresh:  u = est[e].  pilots == NULL (no history: the first step of a run): u is kept.
+ *                Otherwise, with served = status is NULL or status[b] is SOLVED or SOLVED_INACCURATE:
+ *                  pp = pilots[e] when served and pilots[e] > 0, else 0           (what was offered: the plant's rule 2)
+ *                  pr = pp when actual is NULL (what is offered is drawn), else actual[e] when served, else 0
+ *                  if      pp - pr > down_threshold:  u = pr + up_increment       (ramp down to just above what was drawn)
+ *                  else if u  - pr < up_threshold:    u = u + up_increment        (the EV draws what it may: probe upwards)
+ *                  else                               u is kept
+ *                -- at most two subtractions, two comparisons and one addition, each rounded once.
+ *    5  output:  est'[e] = u.  For t < s_len[e]:  v = (u < ub[e][t] ? u : ub[e][t]), then
+ *                ub_out[e][t] = (v < lb[e][t] ? lb[e][t] : v) -- reconcile_max_and_min with choose_min = True.
+ *                For t >= s_len[e]:  ub_out[e][t] = ub[e][t].
+ *    6  flags[b] is written for every problem, 0 when nothing was flagged.
+ * ub_out is an array of its own: the state keeps the session's own bounds (the advance shifts THEM into the next period,
+ * and the estimate may rise again), only the solve reads the capped copy.  lb is read and never written.
+ * tests/estimate_spec.py states the rules in plain loops and the library returns its bits.  No atomics; every output
+ * element is written whatever the input; a problem gives the same bits alone and at any position of any batch.  est may
+ * hold +inf; every other input is finite: the library is built without NaN semantics.                                 */
+#define ACNQP_ESTIMATE_BAD_FRESH 1   /* flags: fresh[e] != 0 on an absent slot                                           */
+#define ACNQP_ESTIMATE_BAD_SLOT 2    /* flags: s_len[e] > t_max (counted as absent)                                      */
+
+/* acnqp_estimate_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns
+ * without synchronising.  cur: batch, k_sessions (must be 1), t_max, s_off, s_len, lb and ub are read.  fresh, est: [B*N];
+ * pilots, actual: [B*N] or NULL; status: [B] or NULL; ub_out: [B*N*t_max]; flags: [B].  Refused with ACNQP_ERR_INVALID and
+ * acnqp_last_error set, before any device work: a null handle or required pointer, k_sessions != 1, a negative batch,
+ * t_max outside [1, 4096], actual given without pilots, an output (est, ub_out, flags) that overlaps an input or another
+ * output.  batch == 0 returns ACNQP_OK.                                                                              */
+int acnqp_estimate_device(acnqp_handle* h, const acnqp_problems* cur, const int32_t* fresh, const double* pilots,
+                          const double* actual, const int32_t* status, double up_threshold, double down_threshold,
+                          double up_increment, double* est, double* ub_out, int32_t* flags, void* hip_stream);
+
+/* acnqp_estimate_host -- the same with host pointers, synchronous; a large batch is processed in chunks.  Same bits as
+ * the device entry, at any chunking.                                                                                 */
+int acnqp_estimate_host(acnqp_handle* h, const acnqp_problems* cur, const int32_t* fresh, const double* pilots,
+                        const double* actual, const int32_t* status, double up_threshold, double down_threshold,
+                        double up_increment, double* est, double* ub_out, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif
