@@ -215,6 +215,10 @@ def polish(lb, ub, q, pd, sessions, eq, G, M, cone_soc, limits, peak, x0, y0, ve
         if m > MAX_ROWS:
             info["why"] = "rows"
             return x, info
+        # what the kernel's LDS tables must hold this round (acn_qp_polish.hpp: packed per-period blocks, session columns);
+        # the specification has no such limit, it reports the largest of each
+        per_t = np.bincount([t for (_, t, _, _, _) in R], minlength=T) if m else np.zeros(T, int)
+        info["blocks"] = max(info.get("blocks", 0), int((per_t * (per_t + 1) // 2).sum()))
         Rm = np.zeros((m, N, T))
         for a, (r, t, c0, c1, j) in enumerate(R):
             Rm[a, :, t] = c0 * G[j] + (c1 * G[j + M] if c1 != 0.0 else 0.0)
@@ -223,6 +227,7 @@ def polish(lb, ub, q, pd, sessions, eq, G, M, cone_soc, limits, peak, x0, y0, ve
         g = np.where(free, pd * x + q, 0.0)
         nfree = np.array([free[i, o:o + L].sum() for (i, o, L, cap, *_k) in sessions])
         on = s_act & (nfree > 0)
+        info["sessions"] = max(info.get("sessions", 0), int(on.sum()))
         c_E = np.array([cap - x[i, o:o + L].sum() for (i, o, L, cap, *_k) in sessions])
 
         def project(v):   # P v on the free variables
