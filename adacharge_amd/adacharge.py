@@ -261,7 +261,7 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         return out
 
     def simulate_batch(self, fleets, steps, start_time=0, warm_start=False, return_schedules=False, observer=None, session_order=None,
-                       prices=None):
+                       prices=None, resolve="every_step"):
         """Closed-loop extension: ``steps`` control periods of B scenarios of this site (``fleets``: one list of EV records
         per scenario, or a ``rollout.FleetTable``) with the whole state resident in HBM.  On one stream, per period:
         ``solve_device -> pilots_device (first period) -> advance_device``, with no host synchronisation inside the loop; an
@@ -293,10 +293,24 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         and returns exactly what it did without the feature; so does one without the estimator.
         ``warm_start``: every solve but the first starts from the previous
         period's schedule and multipliers, shifted on the device.  ``observer(step, state, pilots)``: diagnostic hook called
-        after each period's solve has been enqueued (it may synchronise and read the ``DeviceBatch``)."""
+        after each period's solve has been enqueued (it may synchronise and read the ``DeviceBatch``).
+        ``resolve``: ``"every_step"`` (the default) solves every scenario at every period and ignores ``max_recompute``.
+        ``"events"`` is the loop around the reference's ``schedule()`` and honours ``max_recompute``: a
+        scenario is solved afresh at step 0, at the steps an EV of its fleet plugs in or unplugs, and once ``max_recompute``
+        periods have passed since its last solve (``rollout.FleetTable.resolve_rows``); in between it plays the rest of the
+        schedule it holds -- the last solve's, shifted by the advance and clipped into the current bounds, NOT the schedule a
+        fresh solve would give once a battery has drawn less than it was offered or the tariff has moved.  Only the scenarios
+        with an event are solved (``acnqp_select_device -> solve -> acnqp_hold_device`` in place of the step's solve); the mask
+        is known before the run, so the loop still never synchronises.  The result carries ``solved (steps, B)`` bool (None
+        under ``"every_step"``) and ``resolve_flags``; ``status`` of a held step is the status of the solve its pilots came
+        from -- a scenario whose last solve was not accepted is delivered nothing until its next scheduled solve -- and
+        ``iters`` of a held step is 0.  ``quantize`` sets ``max_recompute = 1``: then, as with ``max_recompute=1`` itself, every
+        step is solved and the run is the ``"every_step"`` run.  Whenever some step is not solved, ``estimate_max_rate`` and
+        ``uninterrupted_charging`` raise ``ValueError``: both are per solve in the reference and have no rule under a held
+        schedule here."""
         from .rollout import simulate
 
-        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer, session_order, prices)
+        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer, session_order, prices, resolve)
 
 
 class AdaptiveChargingAlgorithmOffline(BaseAlgorithm):

@@ -70,6 +70,9 @@ _ADVANCE_ARRAYS = dict(q_table=_F8, h_scal=_F8, h_row=_I4, peak_series=_F8, a_se
 _COST_ARRAYS = dict(c_weight=_F8, c_series=_F8)   # weight and series of acnqp_clock_cost, under AdvancePlan's names
 _PREPARE_ARRAYS = dict(key=_I4, cre=_F8, cim=_F8, limits=_F8, min_pilot=_F8)
 _PLANT_ARRAYS = dict(t_room=_F8, t_amps=_F8, t_knee=_F8, t_slope=_F8, plug=_I4)   # the plant entries take them as plain arguments
+_RESOLVE_ARRAYS = dict(sel_seg=_I4, sel_idx=_I4, pos=_I4)   # idx of the select entries and pos of the hold entries, for every step of a run
+SELECT_BAD_INDEX = 1
+HOLD_BAD_ROW = 1
 
 
 def _ints(*names):
@@ -185,6 +188,10 @@ def _abi():
         ("acnqp_plant", [h, P(_Problems), ptr, ptr, i32] + [ptr] * 9),
         # cur, fresh, pilots, actual, status, up_threshold, down_threshold, up_increment, est, ub_out, flags
         ("acnqp_estimate", [h, P(_Problems)] + [ptr] * 4 + [C.c_double] * 3 + [ptr] * 3),
+        # cur, n_evse, n_rows, m, idx, out, s_eq, flags
+        ("acnqp_select", [h, P(_Problems), i32, i32, i32, ptr, P(_Next), ptr, ptr]),
+        # cur, n_evse, n_rows, m, pos, dense, held_x, held_y, prev_status, out, solved, flags
+        ("acnqp_hold", [h, P(_Problems), i32, i32, i32, ptr, P(_Results), ptr, ptr, ptr, P(_Results), ptr, ptr]),
     ):
         rows += [(stem + "_host", rc, args), (stem + "_device", rc, args + [stream])]
     introspection = [
@@ -534,6 +541,25 @@ class PlantPlan(_PlanArrays):
         """n_batteries and the five pointers, in the order of the entries' arguments"""
         return [C.c_int32(self._len("t_room"))] + [self._p(k, keep, 0 if plug_row is None else plug_row, 3 if k == "plug" else None)
                                                    for k in _PLANT_ARRAYS]
+
+
+@dataclass
+class ResolvePlan(_PlanArrays):
+    """Which scenarios of a closed loop are solved afresh at which step (``rollout.FleetTable.resolve_plan``), as
+    ``SiteHandle.select_device`` and ``SiteHandle.hold_device`` read it: numpy arrays, or torch tensors on the handle's GPU
+    (``to_device``).  Step s resolves the ``m_s = sel_seg[s + 1] - sel_seg[s]`` scenarios ``sel_idx[sel_seg[s]: sel_seg[s + 1]]``,
+    ascending; ``pos[s, b]`` is the row of scenario b in the step's dense batch, or -1 where b keeps the schedule it holds."""
+    sel_seg: object   # (steps + 1,) int32
+    sel_idx: object   # (sum of m_s,) int32
+    pos: object       # (steps, B) int32
+
+    _DTYPES = _RESOLVE_ARRAYS
+    _ARRAYS = tuple(_RESOLVE_ARRAYS)
+
+    def counts(self) -> list:
+        """m_s of every step, as Python ints (read from the host copy or, once, from the device)"""
+        seg = self.sel_seg.cpu().numpy() if hasattr(self.sel_seg, "cpu") else np.asarray(self.sel_seg)
+        return [int(v) for v in np.diff(seg)]
 
 
 class _PinnedBlock:
@@ -1036,6 +1062,96 @@ class SiteHandle:
                                                float(down_threshold), float(up_increment), _dptr(est), _dptr(ub_out), _dptr(flags),
                                                C.c_void_p(stream)), "acnqp_estimate_device")
 
+    # -- select and hold (acn_qp_hold.hpp) -------------------------------------------------------------------------------
+    def select_device(self, cur: "DeviceBatch", dense: "DeviceBatch", idx, flags, m: Optional[int] = None, warm_x=None, warm_y=None,
+                      out_warm_x=None, out_warm_y=None, stream: int = 0) -> None:
+        """acnqp_select_device: the first ``m`` problems of ``dense`` (a ``DeviceBatch`` of the same N, Tm, K with room for at
+        least m problems; m = len(idx) when None) receive the problems ``idx[0:m]`` of ``cur``; ``idx`` and ``flags`` int32
+        device tensors of at least m entries.  ``out_warm_x`` / ``out_warm_y`` (at least m rows): optional float64 device
+        tensors that receive rows ``idx`` of ``warm_x`` (B, N, Tm) / ``warm_y`` (B, Mg, Tm).  Asynchronous on ``stream``; m == 0
+        launches nothing."""
+        m = int(idx.shape[0] if m is None else m)
+        if (cur.N, cur.Tm, cur.K) != (dense.N, dense.Tm, dense.K):
+            raise ValueError("cur and dense must have the same shape (N, Tm, K)")
+        if m > dense.B or m > idx.shape[0] or m > flags.shape[0]:
+            raise ValueError(f"dense, idx and flags need room for m = {m} problems")
+        for t, name, rows in ((out_warm_x, "out_warm_x", (cur.N, cur.Tm)), (out_warm_y, "out_warm_y", (self.site.Mg, cur.Tm))):
+            if t is not None and (t.shape[0] < m or tuple(t.shape[1:]) != rows):
+                raise ValueError(f"{name} needs at least m = {m} rows of shape {rows}")
+        _want(idx, "idx", _I4)
+        _want(flags, "flags", _I4)
+        _want(warm_x, "warm_x", _F8, (cur.B, cur.N, cur.Tm))
+        _want(warm_y, "warm_y", _F8, (cur.B, self.site.Mg, cur.Tm))
+        _want(out_warm_x, "out_warm_x", _F8)
+        _want(out_warm_y, "out_warm_y", _F8)
+        p = _device_problems(cur, warm_x, warm_y)
+        nx = _Next(*[_dptr(getattr(dense, k)) for k in _NEXT_ARRAYS], _dptr(out_warm_x), _dptr(out_warm_y))
+        _check(self._lib.acnqp_select_device(self._h, C.byref(p), cur.N, self.site.Mg, m, _dptr(idx), C.byref(nx), _dptr(dense.s_eq),
+                                             _dptr(flags), C.c_void_p(stream)), "acnqp_select_device")
+
+    def hold_device(self, cur: "DeviceBatch", dense: Optional["DeviceBatch"], pos, m: int, held_x, prev_status, solved, flags, held_y=None,
+                    stream: int = 0) -> None:
+        """acnqp_hold_device: ``cur.x, cur.status, cur.iters`` (and ``cur.y`` when ``held_y`` is given) receive the first ``m``
+        results of ``dense`` where ``pos`` (B,) int32 names a row, and elsewhere the held schedule ``held_x`` (B, N, Tm) clipped
+        into ``cur.lb, cur.ub``, ``held_y`` (B, Mg, Tm), ``prev_status`` (B,) int32 and zero iterations; ``solved`` (B,) uint8,
+        ``flags`` (B,) int32.  ``dense`` may be None when m == 0 (everyone is held).  Asynchronous on ``stream``."""
+        B, N, Tm, Mg = cur.B, cur.N, cur.Tm, self.site.Mg
+        want_y = held_y is not None
+        if want_y and (cur.y is None or (dense is not None and dense.y is None)):
+            raise ValueError("held_y needs the site-row multipliers: DeviceBatch(..., want_y=True)")
+        if dense is None and m != 0:
+            raise ValueError("dense is required when m > 0")
+        if dense is not None and ((dense.N, dense.Tm) != (N, Tm) or dense.B < m):
+            raise ValueError(f"dense must have the shape (N, Tm) of cur and hold at least m = {m} problems")
+        for t, name, dt, shape in ((pos, "pos", _I4, (B,)), (held_x, "held_x", _F8, (B, N, Tm)), (held_y, "held_y", _F8, (B, Mg, Tm)),
+                                   (prev_status, "prev_status", _I4, (B,)), (solved, "solved", _U1, (B,)), (flags, "flags", _I4, (B,))):
+            _want(t, name, dt, shape)
+        p = _Problems(B, Tm, cur.K, lb=_dptr(cur.lb), ub=_dptr(cur.ub))
+        r = _Results() if dense is None else _Results(x=_dptr(dense.x), status=_dptr(dense.status), iters=_dptr(dense.iters),
+                                                      y=_dptr(dense.y) if want_y else None)
+        o = _Results(x=_dptr(cur.x), status=_dptr(cur.status), iters=_dptr(cur.iters), y=_dptr(cur.y) if want_y else None)
+        _check(self._lib.acnqp_hold_device(self._h, C.byref(p), N, Mg, int(m), _dptr(pos), C.byref(r), _dptr(held_x), _dptr(held_y),
+                                           _dptr(prev_status), C.byref(o), _dptr(solved), _dptr(flags), C.c_void_p(stream)),
+               "acnqp_hold_device")
+
+    def select_host(self, cur: dict, idx, warm_x=None, warm_y=None) -> dict:
+        """acnqp_select_host: the dense batch of the problems ``idx`` of the state ``cur`` -- a dict of numpy arrays named as the
+        fields of ``acnqp_problems`` -- as a dict of the same layout with ``flags``, and ``warm_x`` / ``warm_y`` when given."""
+        src = {k: np.ascontiguousarray(cur[k], dt) for k, dt in _PROBLEM_ARRAYS.items() if cur.get(k) is not None and k not in _absent(self.site, peak=True)}
+        idx = _i4(idx)
+        wx, wy = _f8(warm_x), _f8(warm_y)
+        B, N, Tm = src["lb"].shape
+        K, m = src["s_off"].shape[1], len(idx)
+        out = {k: np.empty((m,) + a.shape[1:], a.dtype) for k, a in src.items()}
+        if wx is not None:
+            out["warm_x"] = np.empty((m, N, Tm))
+        if wy is not None:
+            out["warm_y"] = np.empty((m,) + wy.shape[1:])
+        out["flags"] = np.empty(m, np.int32)
+        p = _Problems(B, Tm, K, *[_ptr(src.get(k)) for k in _PROBLEM_ARRAYS], _ptr(wx), _ptr(wy))
+        nx = _Next(*[_ptr(out.get(k)) for k in _NEXT_ARRAYS + _WARM])
+        _check(self._lib.acnqp_select_host(self._h, C.byref(p), N, self.site.Mg, m, _ptr(idx), C.byref(nx), _ptr(out["s_eq"]),
+                                           _ptr(out["flags"])), "acnqp_select_host")
+        return out
+
+    def hold_host(self, pos, m: int, rx, rstatus, riters, held_x, prev_status, lb, ub, ry=None, held_y=None) -> dict:
+        """acnqp_hold_host on numpy arrays, in the argument order of tests/hold_spec.py's ``hold``: a dict of ``x, status,
+        iters, solved, flags`` and, with ``held_y``, ``y``."""
+        pos, rst, rit, pst = _i4(pos), _i4(rstatus), _i4(riters), _i4(prev_status)
+        rx, ry, hx, hy, lb, ub = _f8(rx), _f8(ry), _f8(held_x), _f8(held_y), _f8(lb), _f8(ub)
+        B, N, Tm = hx.shape
+        out = dict(x=np.empty((B, N, Tm)), status=np.empty(B, np.int32), iters=np.empty(B, np.int32), solved=np.empty(B, np.uint8),
+                   flags=np.empty(B, np.int32))
+        if hy is not None:
+            out["y"] = np.empty(hy.shape)
+        nul = lambda a: None if a is None or a.size == 0 else _ptr(a)
+        p = _Problems(B, Tm, 1, lb=_ptr(lb), ub=_ptr(ub))
+        r = _Results(x=nul(rx), status=nul(rst), iters=nul(rit), y=nul(ry))
+        o = _Results(x=_ptr(out["x"]), status=_ptr(out["status"]), iters=_ptr(out["iters"]), y=_ptr(out.get("y")))
+        _check(self._lib.acnqp_hold_host(self._h, C.byref(p), N, self.site.Mg, int(m), _ptr(pos), C.byref(r), _ptr(hx), _ptr(hy), _ptr(pst),
+                                         C.byref(o), _ptr(out["solved"]), _ptr(out["flags"])), "acnqp_hold_host")
+        return out
+
     def _kernel_ms_of_call(self) -> float:
         """Sum of the HIP-event durations of the launches since the previous ``kernel_times`` call; NaN when an event
         could not be read or when the call made more launches than the library's 64-entry event ring holds (the sum
@@ -1147,6 +1263,17 @@ class DeviceBatch:
         for k, dt in _RESULT_ARRAYS.items():
             setattr(self, k, torch.zeros((self.B, self.N, self.Tm) if k == "x" else self.B, dtype=_torch_dtype(dt), device=dev))
         self.y = torch.zeros((self.B, Mg, self.Tm), dtype=torch.float64, device=dev) if want_y else None
+
+    def head(self, m: int) -> "DeviceBatch":
+        """The first ``m`` problems as a ``DeviceBatch`` of their own: views, no copy (every array leads with the problem)."""
+        if not 0 <= m <= self.B:
+            raise ValueError(f"m must be in [0, {self.B}]")
+        view = self.__class__.__new__(self.__class__)
+        view.B, view.N, view.Tm, view.K = int(m), self.N, self.Tm, self.K
+        for k in (*_PROBLEM_ARRAYS, *_RESULT_ARRAYS, "y"):
+            t = getattr(self, k)
+            setattr(view, k, None if t is None else t[:m])
+        return view
 
     @classmethod
     def empty(cls, site: SiteData, B: int, Tm: int, K: int, device, want_y: bool = False, s_eq: int = 0, dfloor: float = 0.0,

@@ -22,6 +22,7 @@
 #include "acn_qp_prepare.hpp"
 #include "acn_qp_plant.hpp"
 #include "acn_qp_estimate.hpp"
+#include "acn_qp_hold.hpp"
 #include "acn_qp_site.hpp"
 
 namespace {

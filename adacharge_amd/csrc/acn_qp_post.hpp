@@ -1,4 +1,4 @@
-// The post-solve entries (dual report, pilot signals, time passes, before the solve, the plant, the estimator): argument checks, _device entries, _host entries.  A
+// The post-solve entries (dual report, pilot signals, time passes, before the solve, the plant, the estimator, select and hold): argument checks, _device entries, _host entries.  A
 // host entry is a TABLE of the arrays it stages and a body that rebuilds the argument structs on staging addresses and
 // calls the _device entry; ONE planner lays the table out and ONE loop (run_staged) moves it.
 // Part 1 (table row, planner, overlap predicate) is plain host code: tests/test_post_stage.py compiles it with the host
@@ -614,6 +614,232 @@ int acnqp_estimate_host(acnqp_handle* h, const acnqp_problems* c, const int32_t*
     cc.s_off = dev(SOFF); cc.s_len = dev(SLEN); cc.lb = dev(LB); cc.ub = dev(UB);
     return acnqp_estimate_device(h, &cc, dev(FRESH), dev(PIL), dev(ACT), dev(STAT), up_threshold, down_threshold, up_increment, dev(EST),
                                  dev(UBO), dev(FLG), h->slot[0].st);
+  });
+}
+
+// ---- select and hold (acn_qp_hold.hpp) -------------------------------------------------------------------------------------
+struct PostSpan { const void* p; size_t n; const char* name; };
+
+// nothing written may overlap anything read or anything else written (the workgroups of a launch run in no order)
+static int check_post_overlap(const PostSpan* in, size_t n_in, const PostSpan* out, size_t n_out, const std::string& w) {
+  for (size_t a = 0; a < n_out; ++a) {
+    for (size_t s = 0; s < n_in; ++s)
+      if (acnqp::spans_meet(out[a].p, out[a].n, in[s].p, in[s].n))
+        return fail(ACNQP_ERR_INVALID, w + ": an output aliases an input (" + out[a].name + " overlaps " + in[s].name + ")");
+    for (size_t b2 = a + 1; b2 < n_out; ++b2)
+      if (acnqp::spans_meet(out[a].p, out[a].n, out[b2].p, out[b2].n))
+        return fail(ACNQP_ERR_INVALID, w + ": two outputs overlap (" + out[a].name + " and " + out[b2].name + ")");
+  }
+  return ACNQP_OK;
+}
+
+static int check_dense_shape(const acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const std::string& w) {
+  if (n_evse != h->shape.N || n_rows != h->shape.Mg)
+    return fail(ACNQP_ERR_INVALID, w + ": the call is for " + std::to_string(n_evse) + " EVSEs and " + std::to_string(n_rows) +
+                                       " site rows, the handle's site has " + std::to_string(h->shape.N) + " and " + std::to_string(h->shape.Mg));
+  if (c->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (c->t_max < 1 || c->t_max > 4096) return fail(ACNQP_ERR_INVALID, w + ": t_max must be in [1, 4096]");
+  if (c->k_sessions < 1 || c->k_sessions > 4096) return fail(ACNQP_ERR_INVALID, w + ": k_sessions must be in [1, 4096]");
+  if (m < 0 || m > c->batch)
+    return fail(ACNQP_ERR_INVALID, w + ": m is " + std::to_string(m) + ", it must be in [0, batch = " + std::to_string(c->batch) + "]");
+  const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, K = (size_t)c->k_sessions;
+  if (B * K * N > ((size_t)1 << 31) || B * N * Tm > ((size_t)1 << 40)) return fail(ACNQP_ERR_INVALID, w + ": batch too large");
+  return ACNQP_OK;
+}
+
+// host_idx: the host entry can read idx, and refuses one that is not strictly increasing
+static int check_select_args(const acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* idx,
+                             const acnqp_next* o, const uint8_t* s_eq, const int32_t* flags, bool host_idx, const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!c || !o) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  const int rc = check_dense_shape(h, c, n_evse, n_rows, m, w);
+  if (rc != ACNQP_OK || m == 0) return rc;
+  if (!c->horizon || !c->lb || !c->ub || !c->q || !c->pdiag || !c->s_off || !c->s_len || !c->s_cap || !c->s_eq || !idx)
+    return fail(ACNQP_ERR_INVALID, w + ": null problem array or idx");
+  if (!o->horizon || !o->lb || !o->ub || !o->q || !o->pdiag || !o->s_off || !o->s_len || !o->s_cap || !s_eq || !flags)
+    return fail(ACNQP_ERR_INVALID, w + ": null output array, s_eq or flags");
+  const bool pk = h->shape.has_peak, fl = h->shape.has_flat, mx = h->shape.has_max;
+  if (pk && (!c->peak || !o->peak)) return fail(ACNQP_ERR_INVALID, w + ": site has a peak row but peak is null");
+  if (fl && (!c->lf || !o->lf)) return fail(ACNQP_ERR_INVALID, w + ": site has a flat row but lf is null");
+  if (mx && (!c->dc || !o->dc || !c->dfloor || !o->dfloor)) return fail(ACNQP_ERR_INVALID, w + ": site has a max row but dc or dfloor is null");
+  const size_t B = (size_t)c->batch, M = (size_t)m, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, K = (size_t)c->k_sessions, Mg = (size_t)h->shape.Mg;
+  if (Mg > 0 && ((o->warm_x != nullptr) != (o->warm_y != nullptr)))
+    return fail(ACNQP_ERR_INVALID, w + ": warm_x and warm_y go together on a site with rows (both or neither)");
+  if ((o->warm_x && !c->warm_x) || (Mg > 0 && o->warm_y && !c->warm_y))
+    return fail(ACNQP_ERR_INVALID, w + ": a warm output is wanted but cur's warm_x or warm_y is null");
+  const bool wx = o->warm_x != nullptr, wy = Mg > 0 && o->warm_y != nullptr;
+  const size_t nv = N * Tm * 8, ns = K * N, ny = Mg * Tm * 8;
+  const PostSpan in[] = {{c->horizon, B * 4, "cur->horizon"}, {c->lb, B * nv, "cur->lb"}, {c->ub, B * nv, "cur->ub"}, {c->q, B * nv, "cur->q"},
+                         {c->pdiag, B * 8, "cur->pdiag"}, {c->s_off, B * ns * 4, "cur->s_off"}, {c->s_len, B * ns * 4, "cur->s_len"},
+                         {c->s_cap, B * ns * 8, "cur->s_cap"}, {c->s_eq, B, "cur->s_eq"}, {pk ? c->peak : nullptr, B * Tm * 8, "cur->peak"},
+                         {fl ? c->lf : nullptr, B * 8, "cur->lf"}, {mx ? c->dc : nullptr, B * 8, "cur->dc"}, {mx ? c->dfloor : nullptr, B * 8, "cur->dfloor"},
+                         {wx ? c->warm_x : nullptr, B * nv, "cur->warm_x"}, {wy ? c->warm_y : nullptr, B * ny, "cur->warm_y"}, {idx, M * 4, "idx"}};
+  const PostSpan out[] = {{o->horizon, M * 4, "horizon"}, {o->lb, M * nv, "lb"}, {o->ub, M * nv, "ub"}, {o->q, M * nv, "q"}, {o->pdiag, M * 8, "pdiag"},
+                          {o->s_off, M * ns * 4, "s_off"}, {o->s_len, M * ns * 4, "s_len"}, {o->s_cap, M * ns * 8, "s_cap"}, {s_eq, M, "s_eq"},
+                          {pk ? o->peak : nullptr, M * Tm * 8, "peak"}, {fl ? o->lf : nullptr, M * 8, "lf"}, {mx ? o->dc : nullptr, M * 8, "dc"},
+                          {mx ? o->dfloor : nullptr, M * 8, "dfloor"}, {wx ? o->warm_x : nullptr, M * nv, "warm_x"},
+                          {wy ? o->warm_y : nullptr, M * ny, "warm_y"}, {flags, M * 4, "flags"}};
+  const int ro = check_post_overlap(in, sizeof(in) / sizeof(in[0]), out, sizeof(out) / sizeof(out[0]), w);
+  if (ro != ACNQP_OK) return ro;
+  if (host_idx)
+    for (size_t j = 1; j < M; ++j)
+      if (idx[j] <= idx[j - 1])
+        return fail(ACNQP_ERR_INVALID, w + ": idx is not strictly increasing (idx[" + std::to_string(j) + "] = " + std::to_string(idx[j]) +
+                                           " after " + std::to_string(idx[j - 1]) + ")");
+  return ACNQP_OK;
+}
+
+static int select_device(acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* idx, acnqp_next* o,
+                         uint8_t* s_eq, int32_t* flags, void* hip_stream, bool checked) {
+  if (!checked) {
+    const int rc = check_select_args(h, c, n_evse, n_rows, m, idx, o, s_eq, flags, false, "acnqp_select_device");
+    if (rc != ACNQP_OK || m == 0) return rc;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  const bool pk = h->shape.has_peak, fl = h->shape.has_flat, mx = h->shape.has_max;
+  acnqp::SelectArgs a;
+  a.B = c->batch; a.m = m; a.N = h->shape.N; a.Tm = c->t_max; a.K = c->k_sessions; a.Mg = h->shape.Mg;
+  a.idx = idx;
+  a.horizon = c->horizon; a.lb = c->lb; a.ub = c->ub; a.q = c->q; a.pdiag = c->pdiag;
+  a.s_off = c->s_off; a.s_len = c->s_len; a.s_cap = c->s_cap; a.s_eq = c->s_eq;
+  a.peak = pk ? c->peak : nullptr; a.lf = fl ? c->lf : nullptr; a.dc = mx ? c->dc : nullptr; a.dfloor = mx ? c->dfloor : nullptr;
+  a.wx = c->warm_x; a.wy = c->warm_y;
+  a.o_horizon = o->horizon; a.o_lb = o->lb; a.o_ub = o->ub; a.o_q = o->q; a.o_pdiag = o->pdiag;
+  a.o_off = o->s_off; a.o_len = o->s_len; a.o_cap = o->s_cap; a.o_eq = s_eq;
+  a.o_peak = pk ? o->peak : nullptr; a.o_lf = fl ? o->lf : nullptr; a.o_dc = mx ? o->dc : nullptr; a.o_dfloor = mx ? o->dfloor : nullptr;
+  a.o_wx = o->warm_x;
+  a.o_wy = h->shape.Mg > 0 ? o->warm_y : nullptr;
+  a.flags = flags;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_select(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("select kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_select_device(acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* idx, acnqp_next* o,
+                        uint8_t* s_eq, int32_t* flags, void* hip_stream) {
+  return select_device(h, c, n_evse, n_rows, m, idx, o, s_eq, flags, hip_stream, false);
+}
+
+int acnqp_select_host(acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* idx, acnqp_next* o,
+                      uint8_t* s_eq, int32_t* flags) {
+  const int rc = check_select_args(h, c, n_evse, n_rows, m, idx, o, s_eq, flags, true, "acnqp_select_host");
+  if (rc != ACNQP_OK || m == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, K = (size_t)c->k_sessions, Mg = (size_t)h->shape.Mg;
+  const bool pk = h->shape.has_peak, fl = h->shape.has_flat, mx = h->shape.has_max;
+  const size_t nv = N * Tm * 8, ns = K * N, nwx = o->warm_x ? nv : 0, nwy = Mg > 0 && o->warm_y ? Mg * Tm * 8 : 0;
+  // the state stays whole on the device (any of its problems may be asked for); the dense batch is staged in chunks
+  enum { HOR, LB, UB, Q, PD, SOFF, SLEN, SCAP, SEQ, PEAK, LF, DC, DFL, WX, WY, IDX,
+         OHOR, OLB, OUB, OQ, OPD, OOFF, OLEN, OCAP, OEQ, OPK, OLF, ODC, ODFL, OWX, OWY, OFLG, NARR };
+  const S arr[NARR] = {
+      S::plan(c->horizon, B * 4), S::plan(c->lb, B * nv), S::plan(c->ub, B * nv), S::plan(c->q, B * nv), S::plan(c->pdiag, B * 8),
+      S::plan(c->s_off, B * ns * 4), S::plan(c->s_len, B * ns * 4), S::plan(c->s_cap, B * ns * 8), S::plan(c->s_eq, B),
+      S::plan(c->peak, pk ? B * Tm * 8 : 0), S::plan(c->lf, fl ? B * 8 : 0), S::plan(c->dc, mx ? B * 8 : 0), S::plan(c->dfloor, mx ? B * 8 : 0),
+      S::plan(c->warm_x, B * nwx), S::plan(c->warm_y, B * nwy), S::in(idx, 4),
+      S::out(o->horizon, 4), S::out(o->lb, nv), S::out(o->ub, nv), S::out(o->q, nv), S::out(o->pdiag, 8), S::out(o->s_off, ns * 4),
+      S::out(o->s_len, ns * 4), S::out(o->s_cap, ns * 8), S::out(s_eq, 1), S::out(o->peak, pk ? Tm * 8 : 0), S::out(o->lf, fl ? 8 : 0),
+      S::out(o->dc, mx ? 8 : 0), S::out(o->dfloor, mx ? 8 : 0), S::out(o->warm_x, nwx), S::out(o->warm_y, nwy), S::out(flags, 4)};
+  return run_staged(h, arr, NARR, (size_t)m, [&](size_t, size_t nb, auto dev) {
+    acnqp_problems cc = *c;
+    cc.horizon = dev(HOR); cc.lb = dev(LB); cc.ub = dev(UB); cc.q = dev(Q); cc.pdiag = dev(PD); cc.s_off = dev(SOFF); cc.s_len = dev(SLEN);
+    cc.s_cap = dev(SCAP); cc.s_eq = dev(SEQ); cc.peak = dev(PEAK); cc.lf = dev(LF); cc.dc = dev(DC); cc.dfloor = dev(DFL);
+    cc.warm_x = dev(WX); cc.warm_y = dev(WY);
+    acnqp_next oc{dev(OHOR), dev(OLB), dev(OUB), dev(OQ), dev(OPD), dev(OOFF), dev(OLEN), dev(OCAP), dev(OPK), dev(OLF), dev(ODC), dev(ODFL),
+                  dev(OWX), dev(OWY)};
+    return select_device(h, &cc, n_evse, n_rows, (int32_t)nb, dev(IDX), &oc, dev(OEQ), dev(OFLG), h->slot[0].st, true);
+  });
+}
+
+// host_pos: the host entry can read pos, and refuses one that is not the inverse of a strictly increasing idx[0:m]
+static int check_hold_args(const acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* pos,
+                           const acnqp_results* r, const double* held_x, const double* held_y, const int32_t* prev_status,
+                           const acnqp_results* o, const uint8_t* solved, const int32_t* flags, bool host_pos, const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!c || !r || !o) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  const int rc = check_dense_shape(h, c, n_evse, n_rows, m, w);
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  if (!c->lb || !c->ub || !pos || !held_x || !prev_status) return fail(ACNQP_ERR_INVALID, w + ": null lb, ub, pos, held_x or prev_status");
+  if (!o->x || !o->status || !o->iters || !solved || !flags) return fail(ACNQP_ERR_INVALID, w + ": null output array, solved or flags");
+  if (m > 0 && (!r->x || !r->status || !r->iters)) return fail(ACNQP_ERR_INVALID, w + ": null x, status or iters of the dense results");
+  const size_t B = (size_t)c->batch, M = (size_t)m, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, Mg = (size_t)h->shape.Mg;
+  const bool wy = Mg > 0 && o->y != nullptr;
+  if (wy && (!held_y || (m > 0 && !r->y))) return fail(ACNQP_ERR_INVALID, w + ": y is wanted but held_y or the dense results' y is null");
+  const size_t nv = N * Tm * 8, ny = Mg * Tm * 8;
+  const PostSpan in[] = {{c->lb, B * nv, "cur->lb"}, {c->ub, B * nv, "cur->ub"}, {pos, B * 4, "pos"}, {r->x, M * nv, "dense->x"},
+                         {r->status, M * 4, "dense->status"}, {r->iters, M * 4, "dense->iters"}, {wy ? r->y : nullptr, M * ny, "dense->y"},
+                         {held_x, B * nv, "held_x"}, {wy ? held_y : nullptr, B * ny, "held_y"}, {prev_status, B * 4, "prev_status"}};
+  const PostSpan out[] = {{o->x, B * nv, "x"}, {o->status, B * 4, "status"}, {o->iters, B * 4, "iters"}, {wy ? o->y : nullptr, B * ny, "y"},
+                          {solved, B, "solved"}, {flags, B * 4, "flags"}};
+  const int ro = check_post_overlap(in, sizeof(in) / sizeof(in[0]), out, sizeof(out) / sizeof(out[0]), w);
+  if (ro != ACNQP_OK) return ro;
+  if (host_pos) {   // the rows inside [0, m) count 0, 1, ... m - 1 as b rises (a row outside [-1, m) is rule H3's)
+    int32_t next = 0;
+    for (size_t b = 0; b < B; ++b)
+      if (pos[b] >= 0 && pos[b] < m) {
+        if (pos[b] != next)
+          return fail(ACNQP_ERR_INVALID, w + ": pos is not the inverse of a strictly increasing idx (pos[" + std::to_string(b) + "] = " +
+                                             std::to_string(pos[b]) + ", the next row is " + std::to_string(next) + ")");
+        ++next;
+      }
+    if (next != m)
+      return fail(ACNQP_ERR_INVALID, w + ": pos is not the inverse of a strictly increasing idx (it names " + std::to_string(next) + " of the " +
+                                         std::to_string(m) + " rows)");
+  }
+  return ACNQP_OK;
+}
+
+static int hold_device(acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* pos,
+                       const acnqp_results* r, const double* held_x, const double* held_y, const int32_t* prev_status, acnqp_results* o,
+                       uint8_t* solved, int32_t* flags, void* hip_stream, bool checked) {
+  if (!checked) {
+    const int rc = check_hold_args(h, c, n_evse, n_rows, m, pos, r, held_x, held_y, prev_status, o, solved, flags, false, "acnqp_hold_device");
+    if (rc != ACNQP_OK || c->batch == 0) return rc;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  const bool wy = h->shape.Mg > 0 && o->y != nullptr;
+  acnqp::HoldArgs a;
+  a.B = c->batch; a.m = m; a.N = h->shape.N; a.Tm = c->t_max; a.Mg = h->shape.Mg;
+  a.pos = pos;
+  a.rx = r->x; a.ry = wy ? r->y : nullptr; a.rstatus = r->status; a.riters = r->iters;
+  a.held_x = held_x; a.held_y = wy ? held_y : nullptr; a.prev_status = prev_status;
+  a.lb = c->lb; a.ub = c->ub;
+  a.x = o->x; a.y = wy ? o->y : nullptr; a.status = o->status; a.iters = o->iters; a.solved = solved; a.flags = flags;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_hold(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("hold kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_hold_device(acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* pos,
+                      const acnqp_results* r, const double* held_x, const double* held_y, const int32_t* prev_status, acnqp_results* o,
+                      uint8_t* solved, int32_t* flags, void* hip_stream) {
+  return hold_device(h, c, n_evse, n_rows, m, pos, r, held_x, held_y, prev_status, o, solved, flags, hip_stream, false);
+}
+
+int acnqp_hold_host(acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, int32_t n_rows, int32_t m, const int32_t* pos,
+                    const acnqp_results* r, const double* held_x, const double* held_y, const int32_t* prev_status, acnqp_results* o,
+                    uint8_t* solved, int32_t* flags) {
+  const int rc = check_hold_args(h, c, n_evse, n_rows, m, pos, r, held_x, held_y, prev_status, o, solved, flags, true, "acnqp_hold_host");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t M = (size_t)m, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, Mg = (size_t)h->shape.Mg;
+  const size_t nv = N * Tm * 8, ny = Mg > 0 && o->y ? Mg * Tm * 8 : 0;
+  // the dense results stay whole on the device (pos names their rows absolutely); the full batch is staged in chunks
+  enum { RX, RY, RST, RIT, POS, HX, HY, PST, LB, UB, OX, OY, OST, OIT, OSV, OFLG, NARR };
+  const S arr[NARR] = {S::plan(r->x, M * nv), S::plan(r->y, M * ny), S::plan(r->status, M * 4), S::plan(r->iters, M * 4),
+                       S::in(pos, 4), S::in(held_x, nv), S::in(held_y, ny), S::in(prev_status, 4), S::in(c->lb, nv), S::in(c->ub, nv),
+                       S::out(o->x, nv), S::out(o->y, ny), S::out(o->status, 4), S::out(o->iters, 4), S::out(solved, 1), S::out(flags, 4)};
+  return run_staged(h, arr, NARR, (size_t)c->batch, [&](size_t, size_t nb, auto dev) {
+    acnqp_problems cc = *c;
+    cc.batch = (int32_t)nb;
+    cc.lb = dev(LB); cc.ub = dev(UB);
+    acnqp_results rc2{}, oc{};
+    rc2.x = dev(RX); rc2.y = dev(RY); rc2.status = dev(RST); rc2.iters = dev(RIT);
+    oc.x = dev(OX); oc.y = dev(OY); oc.status = dev(OST); oc.iters = dev(OIT);
+    return hold_device(h, &cc, n_evse, n_rows, m, dev(POS), &rc2, dev(HX), dev(HY), dev(PST), &oc, dev(OSV), dev(OFLG), h->slot[0].st, true);
   });
 }
 

@@ -6,6 +6,9 @@ site on one stream -- ``acnqp_solve_batch_device -> acnqp_pilots_device -> acnqp
 synchronisation in between -- and copies pilots, statuses and flags back once at the end.
 With a stated ``session_order`` the loop also serves the two settings of the reference that read the session list,
 ``uninterrupted_charging`` and ``reallocate``: ``acnqp_prepare_device`` runs between the advance and the solve.
+With ``resolve="events"`` the loop is the one around the reference's ``schedule()``: a scenario is solved afresh only where
+``FleetTable.resolve_rows(max_recompute)`` says so -- step 0, plug-in and unplug events, every ``max_recompute`` periods --
+and keeps the schedule it holds in between: ``acnqp_select_device -> solve -> acnqp_hold_device`` in place of the solve.
 
 ``FleetTable`` is everything the loop needs that does not depend on what the solver answers, computed once for the whole
 run: the arrival records of every step (the layout of ``acnqp_advance_plan``), the linear cost and the scalars of every
@@ -25,6 +28,7 @@ from .builder import _objective_needs_flat, _objective_needs_max, objective_term
 
 
 START_GAIN = 1e5   # where a cold solve starts a session: Proj(-1e5 q) (kStartGain of the solver kernels, acn_qp_common.hpp)
+RESOLVE_MODES = ("every_step", "events")
 
 
 @dataclass
@@ -43,6 +47,10 @@ class RolloutResult:
     plant_flags: Optional[np.ndarray] = None     # (steps, B) int32 flags of acnqp_plant_device (a fleet carries batteries)
     estimates: Optional[np.ndarray] = None       # (steps, B, N) the bound each solve saw (estimate_max_rate), +inf where no session
     estimate_flags: Optional[np.ndarray] = None  # (steps, B) int32 flags of acnqp_estimate_device (estimate_max_rate)
+    solved: Optional[np.ndarray] = None          # (steps, B) bool: the scenario was solved afresh at the step (resolve="events"); where
+                                                 # False, ``status`` is that of the solve the step's pilots came from and ``iters`` is 0
+    resolve_flags: Optional[np.ndarray] = None   # (steps, B) int32: per scenario, the flags of acnqp_hold_device OR-ed with those of
+                                                 # acnqp_select_device for its row of the step's dense batch (resolve="events")
 
 
 class FleetTable:
@@ -282,6 +290,44 @@ class FleetTable:
             fresh[lo, b, i] = 1
         return fresh
 
+    def resolve_rows(self, max_recompute=None) -> np.ndarray:
+        """(steps, B) bool: the steps at which scenario b is solved afresh under ``resolve="events"`` -- the loop around the
+        reference's ``schedule()`` as SURVEY.md section 3.1 records it: the plant calls the algorithm when an EV plugs in, when
+        one unplugs, or when ``max_recompute`` periods have passed since the last solve, and plays the schedule it holds in
+        between.  Scenario b resolves at step s when
+          E0     s == 0
+          E1/E2  s is the first step or the end step of any record of fleet b (``windows``, inside the run), admitted or not:
+                 the plant raises plug-in and unplug events for every EV
+          E3     ``max_recompute`` is not None and s - (the last step b resolved) >= max_recompute
+        Everything here is known before the run: the mask never depends on what the solver answers."""
+        if max_recompute is not None:
+            if isinstance(max_recompute, (bool, np.bool_)) or not isinstance(max_recompute, (int, np.integer)) or max_recompute < 1:
+                raise ValueError(f"max_recompute must be None or an integer >= 1, not {max_recompute!r}")
+        mask = np.zeros((self.steps, self.B), dtype=bool)
+        mask[0] = True
+        for b, wins in enumerate(self.windows):
+            for _, lo, hi in wins:
+                for s in (lo, hi):
+                    if 0 <= s < self.steps:
+                        mask[s, b] = True
+        if max_recompute is not None:
+            last = np.zeros(self.B, dtype=np.int64)
+            for s in range(1, self.steps):
+                mask[s] |= s - last >= int(max_recompute)
+                last[mask[s]] = s
+        return mask
+
+    def resolve_plan(self, max_recompute=None) -> "backend.ResolvePlan":
+        """the ``backend.ResolvePlan`` of ``resolve_rows(max_recompute)``: per step the scenarios that resolve, ascending,
+        and for every scenario its row in that step's dense batch, or -1"""
+        mask = self.resolve_rows(max_recompute)
+        steps, b = np.nonzero(mask)   # (row-major: ascending b inside a step)
+        sel_seg = np.zeros(self.steps + 1, np.int32)
+        np.cumsum(mask.sum(axis=1), out=sel_seg[1:])
+        pos = np.full((self.steps, self.B), -1, np.int32)
+        pos[steps, b] = np.arange(len(b)) - sel_seg[steps]
+        return backend.ResolvePlan(sel_seg=sel_seg, sel_idx=b.astype(np.int32), pos=pos)
+
     def _refuse_clock_dependence(self, objective, infrastructure, interface, q_now):
         data = getattr(interface, "data", None)
         if not isinstance(data, dict):   # no clock to move: only components known not to read one
@@ -319,8 +365,10 @@ class FleetTable:
 
 
 def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = False, return_schedules: bool = False,
-             observer=None, session_order: Optional[str] = None, prices=None) -> RolloutResult:
+             observer=None, session_order: Optional[str] = None, prices=None, resolve: str = "every_step") -> RolloutResult:
     """``AdaptiveSchedulingAlgorithm.simulate_batch``: see there."""
+    if resolve not in RESOLVE_MODES:
+        raise ValueError(f'resolve must be "every_step" or "events", not {resolve!r}')
     import torch
 
     from .adaptive_charging_optimization import _site_handle
@@ -358,6 +406,20 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
         table.peak_limit is None or np.array_equal(np.asarray(table.peak_limit, float), np.asarray(alg.peak_limit, float)))
     if not same_objective or not same_peak:
         raise ValueError("the FleetTable was built with another objective or peak_limit than the algorithm's")
+    # who is solved afresh at which step: known before the run (arrivals, departures, max_recompute), never read off an answer
+    rplan = counts = None
+    if resolve == "events":
+        mask = table.resolve_rows(alg.max_recompute)
+        if not mask.all():
+            for on, why in ((alg.estimate_max_rate, "estimate_max_rate: the reference's estimator runs inside schedule(), so only at solves, while "
+                                                    "the device rule moves every step; under a held schedule it needs a rule of its own"),
+                            (alg.uninterrupted_charging, "uninterrupted_charging: its minimum-rate step is per solve, a held schedule has none")):
+                if on:
+                    raise ValueError(f'simulate_batch(resolve="events") does not serve {why} (max_recompute=1 solves every step)')
+            rplan = table.resolve_plan(alg.max_recompute)
+            counts = rplan.counts()
+            table_seg = np.asarray(rplan.sel_seg)
+            host_idx = np.asarray(rplan.sel_idx)
     site, handle = _site_handle(infra, alg.constraint_type, table.has_peak, alg.device, with_flat=table.need_flat, with_max=table.need_max)
     opts = dict(alg.solver_options or {})
     if not bool(opts.pop("retry_stalled", True)):
@@ -407,8 +469,18 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
         iters = torch.zeros((steps, B), dtype=torch.int32, device=dev)
         flags = torch.zeros((steps, B), dtype=torch.int32, device=dev)
         xs = torch.zeros((steps, B, N, Tm), dtype=torch.float64, device=dev) if return_schedules else None
-        wx = torch.zeros((B, N, Tm), dtype=torch.float64, device=dev) if want_y else None
+        held = rplan is not None   # some scenario of some step keeps the schedule it holds: the advance's warm_x' is that schedule
+        wx = torch.zeros((B, N, Tm), dtype=torch.float64, device=dev) if want_y or held else None
         wy = torch.zeros((B, site.Mg, Tm), dtype=torch.float64, device=dev) if want_y else None
+        if held:
+            rplan = rplan.to_device(dev)
+            dense = backend.DeviceBatch.empty(site, B, Tm, K, dev, want_y=want_y, s_eq=s_eq, dfloor=table.dfloor0)
+            heads = {m: dense.head(m) for m in set(counts)}
+            dwx = torch.zeros((B, N, Tm), dtype=torch.float64, device=dev) if want_y else None
+            dwy = torch.zeros((B, site.Mg, Tm), dtype=torch.float64, device=dev) if want_y else None
+            solved = torch.ones((steps, B), dtype=torch.uint8, device=dev)
+            sflags = torch.zeros((steps, B), dtype=torch.int32, device=dev)   # row s: entry j is the j-th scenario step s resolves
+            hflags = torch.zeros((steps, B), dtype=torch.int32, device=dev)
         nothing = torch.zeros((B, N), dtype=torch.float64, device=dev)
         # a battery per EV (the plant): what is drawn of the pilots goes to the advance, not the pilots themselves
         actual = plflags = None
@@ -449,7 +521,20 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             state, nxt = bufs[s % 2], bufs[(s + 1) % 2]
             cur = solve_next
             warm = want_y and s > 0   # (a site without rows has no multipliers to carry: it starts cold)
-            handle.solve_device(cur, options, stream=stream, warm_x=wx if warm else None, warm_y=wy if warm else None)
+            if held and counts[s] < B:
+                # only the scenarios with an event are solved: out of the state into a dense batch, and the answers back beside
+                # the held, shifted schedules of everyone else (every size is the plan's: nothing is read off the device)
+                m, lo = counts[s], int(table_seg[s])
+                part = heads[m]
+                if m > 0:
+                    handle.select_device(cur, part, rplan.sel_idx[lo: lo + m], sflags[s], m, warm_x=wx if warm else None,
+                                         warm_y=wy if warm else None, out_warm_x=dwx if warm else None, out_warm_y=dwy if warm else None,
+                                         stream=stream)
+                    handle.solve_device(part, options, stream=stream, warm_x=dwx[:m] if warm else None, warm_y=dwy[:m] if warm else None)
+                handle.hold_device(cur, part, rplan.pos[s], m, wx, status[s - 1], solved[s], hflags[s], held_y=wy if want_y else None,
+                                   stream=stream)
+            else:
+                handle.solve_device(cur, options, stream=stream, warm_x=wx if warm else None, warm_y=wy if warm else None)
             handle.pilots_device(pplan, cur.x, first=pilots[s], visits=visits[s] if realloc else None, stream=stream)
             if actual is not None:
                 handle.plant_device(cur, plplan, pilots[s], bat, room, actual[s], plflags[s], status=cur.status, plug_row=s, stream=stream)
@@ -474,7 +559,16 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             raise ValueError(f"step {s_bad}, scenario {b_bad}: allowable pilots end below a session's cap; the reallocation of the "
                              "rounding loss would never end")
         drawn = p if actual is None else actual.cpu().numpy()   # (the plant draws nothing in a step that did not solve)
+        was_solved = rflags = None
+        if resolve == "events":
+            was_solved, rflags = np.ones((steps, B), dtype=bool), np.zeros((steps, B), np.int32)
+        if held:
+            was_solved, rflags, sf = solved.cpu().numpy().astype(bool), hflags.cpu().numpy(), sflags.cpu().numpy()
+            for s in np.flatnonzero(np.asarray(counts) < B):
+                rows = host_idx[table_seg[s]: table_seg[s + 1]]
+                rflags[s, rows] |= sf[s, : len(rows)]
         return RolloutResult(p, st, iters.cpu().numpy(), flags.cpu().numpy(), table.delivered(drawn),
                              None if xs is None else xs.cpu().numpy(), vis, None if pflags is None else pflags.cpu().numpy(),
                              table.energy_cost(drawn), None if actual is None else drawn, None if plflags is None else plflags.cpu().numpy(),
-                             None if ests is None else ests.cpu().numpy(), None if eflags is None else eflags.cpu().numpy())
+                             None if ests is None else ests.cpu().numpy(), None if eflags is None else eflags.cpu().numpy(),
+                             was_solved, rflags)

@@ -748,6 +748,78 @@ int acnqp_estimate_host(acnqp_handle* h, const acnqp_problems* cur, const int32_
                         const double* actual, const int32_t* status, double up_threshold, double down_threshold,
                         double up_increment, double* est, double* ub_out, int32_t* flags);
 
+/* ---- select and hold (additive to ABI v10: new symbols only, no new struct) ------------------------------------------------
+ * The loop around the reference's schedule() does not solve every period: the plant calls the algorithm when an EV plugs
+ * in, when one unplugs, or when max_recompute periods have passed since the last solve, and plays the rest of the schedule
+ * it holds in between.  Which scenario of a batch resolves at which step follows from arrivals, departures and
+ * max_recompute, all known before the run, so the caller knows the size of every step's solve without reading an answer.
+ * These two entries are the device side of that loop: SELECT takes the resolving problems out of the resident state into a
+ * dense batch of m problems, acnqp_solve_batch_device solves that batch, and HOLD puts the answers back into the full
+ * batch beside the held schedules of everyone else.
+ *
+ * select -- cur: the state, B = cur->batch problems; idx[0:m]; out, s_eq, flags: the dense batch, m problems.  For j in
+ * [0, m) with b = idx[j]:
+ *    S1  0 <= b < B:  every array of acnqp_problems is copied from row b to row j, bit for bit: horizon, lb, ub, q, pdiag,
+ *        s_off, s_len, s_cap, s_eq; peak, lf, dc, dfloor exactly where the site has the row; warm_x and warm_y when wanted
+ *        (out->warm_x / out->warm_y not NULL: then cur->warm_x / cur->warm_y are their sources); flags[j] = 0.
+ *    S2  otherwise:  flags[j] = ACNQP_SELECT_BAD_INDEX and problem j is the empty problem: horizon 1, zeros, peak +inf, no
+ *        live slot, s_eq and dfloor 0, warm arrays 0.  Nothing of cur is read for it.
+ * hold -- cur: the state (batch, t_max, lb and ub are read); pos[0:B]: the row of scenario b in the dense batch, or -1;
+ * dense: the dense results x, status, iters and, when wanted, y (m rows, read only); held_x and, when wanted, held_y: the
+ * schedule every scenario holds -- the warm_x' / warm_y' the advance wrote under its rule 9; prev_status[0:B]; out: x,
+ * status, iters and, when wanted (out->y not NULL on a site with rows), y of all B; solved, flags: [B].  For every b with
+ * j = pos[b]:
+ *    H1  0 <= j < m:  x[b] = dense->x[j], y[b] = dense->y[j], status[b] = dense->status[j], iters[b] = dense->iters[j],
+ *        solved[b] = 1.
+ *    H2  otherwise, for every element v = held_x[b][i][t]:  if v > ub then v = ub, then if v < lb then v = lb -- comparisons
+ *        only, in this order -- and x[b][i][t] = v.  y[b] = held_y[b], status[b] = prev_status[b], iters[b] = 0,
+ *        solved[b] = 0.  The clip gives a held schedule the invariants of a solver output: lb <= x <= ub exactly and exact
+ *        zeros outside live windows (a session the advance retired early has ub = 0 on its window, advance rule 3).
+ *    H3  a j outside [-1, m) is held as in H2 and sets flags[b] = ACNQP_HOLD_BAD_ROW; otherwise flags[b] = 0.
+ * A held schedule is NOT the schedule a fresh solve would give: it does not see that a battery drew less than it was
+ * offered, nor that the tariff has moved.  It is what the reference's user applies between two calls of schedule().
+ * A scenario whose last solve was not accepted keeps that status while it is held: the advance delivers nothing for it
+ * (advance rule 1) until its next scheduled solve.  The mask of who resolves never depends on the answers -- that is what
+ * keeps a loop built on these entries free of host synchronisation.
+ * tests/hold_spec.py states both rule lists in plain loops and the library returns its bits: every element is a copy, a
+ * constant or the outcome of two comparisons.  No atomics; every output element is written whatever the input; a problem's
+ * output does not depend on j, b or m.  Inputs are finite or +inf: the library is built without NaN semantics.          */
+#define ACNQP_SELECT_BAD_INDEX 1   /* flags of select: idx[j] outside [0, batch) (problem j is the empty problem)       */
+#define ACNQP_HOLD_BAD_ROW 1       /* flags of hold: pos[b] outside [-1, m) (scenario b is held)                        */
+
+/* acnqp_select_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns without
+ * synchronising.  cur: all of it is read (warm_x / warm_y only when wanted).  out: the arrays of the dense batch, [m*...]
+ * in the layout of acnqp_problems; s_eq: [m]; flags: [m].  Refused with ACNQP_ERR_INVALID and acnqp_last_error set, before
+ * any device work: a null handle or argument; n_evse or n_rows other than the handle's; a negative batch, t_max or
+ * k_sessions outside [1, 4096], m < 0 or m > batch; a null required array; a site row without its array (in cur or out);
+ * on a site with rows, out->warm_x without out->warm_y or the reverse; a warm output without its source; an output that
+ * overlaps an input or another output.  m == 0 is a valid call and launches nothing.                                   */
+int acnqp_select_device(acnqp_handle* h, const acnqp_problems* cur, int32_t n_evse, int32_t n_rows, int32_t m,
+                        const int32_t* idx, acnqp_next* out, uint8_t* s_eq, int32_t* flags, void* hip_stream);
+
+/* acnqp_select_host -- the same with host pointers, synchronous; the state is uploaded once, a large dense batch is
+ * processed in chunks.  Same bits as the device entry, at any chunking.  Here idx can be read: one that is not strictly
+ * increasing is refused too.                                                                                         */
+int acnqp_select_host(acnqp_handle* h, const acnqp_problems* cur, int32_t n_evse, int32_t n_rows, int32_t m,
+                      const int32_t* idx, acnqp_next* out, uint8_t* s_eq, int32_t* flags);
+
+/* acnqp_hold_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns without
+ * synchronising.  Refused with ACNQP_ERR_INVALID and acnqp_last_error set, before any device work: a null handle or
+ * argument; n_evse or n_rows other than the handle's; a negative batch, t_max or k_sessions outside [1, 4096], m < 0 or
+ * m > batch; a null required array (the dense results are required only when m > 0); y wanted without held_y or, when
+ * m > 0, dense->y; an output (out->x, status, iters, y, solved, flags) that overlaps an input or another output.
+ * batch == 0 returns ACNQP_OK; m == 0 is a valid call and holds everyone.                                              */
+int acnqp_hold_device(acnqp_handle* h, const acnqp_problems* cur, int32_t n_evse, int32_t n_rows, int32_t m,
+                      const int32_t* pos, const acnqp_results* dense, const double* held_x, const double* held_y,
+                      const int32_t* prev_status, acnqp_results* out, uint8_t* solved, int32_t* flags, void* hip_stream);
+
+/* acnqp_hold_host -- the same with host pointers, synchronous; the dense results are uploaded once, a large batch is
+ * processed in chunks.  Same bits as the device entry, at any chunking.  Here pos can be read: one that is not the inverse
+ * of a strictly increasing idx[0:m] -- its entries inside [0, m) count 0, 1, ... m - 1 as b rises -- is refused too.     */
+int acnqp_hold_host(acnqp_handle* h, const acnqp_problems* cur, int32_t n_evse, int32_t n_rows, int32_t m,
+                    const int32_t* pos, const acnqp_results* dense, const double* held_x, const double* held_y,
+                    const int32_t* prev_status, acnqp_results* out, uint8_t* solved, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif
