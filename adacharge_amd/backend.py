@@ -176,6 +176,7 @@ def _abi():
         ("acnqp_polish_stats", rc, [h, P(i64), i32]),
         ("acnqp_accel_columns", i32, [h, i32, i32, i32, i32]),
         ("acnqp_route", i32, [h, i32, i32, i32, P(i32)]),
+        ("acnqp_set_long_polish", rc, [h, i32]),
     ]
     # acnqp_X_host takes these arguments, acnqp_X_device the same and the stream behind them
     for stem, args in (
@@ -598,10 +599,13 @@ def pinned_empty(shape, dtype=np.float64) -> np.ndarray:
 class SiteHandle:
     """One ``acnqp_handle``: a site uploaded to one GPU."""
 
-    def __init__(self, site: SiteData, device: int = 0):
+    def __init__(self, site: SiteData, device: int = 0, polish_long: bool = False):
+        """``polish_long``: the Newton polish also takes over at horizons 33 ... 288 (N <= 64; ``acnqp_set_long_polish``).
+        Off by default: launches then do exactly what they did before there was such a polish."""
         self._lib = load_library()
         self.site = site
         self.device = int(device)
+        self.polish_long = bool(polish_long)
         G = np.ascontiguousarray(site.G, dtype=np.float64)
         lim = np.ascontiguousarray(site.limits, dtype=np.float64)
         desc = _Site(
@@ -613,6 +617,8 @@ class SiteHandle:
         _check(self._lib.acnqp_create(C.byref(desc), self.device, C.byref(h)), "acnqp_create")
         self._h = h
         self._launches_seen = 0
+        if self.polish_long:
+            _check(self._lib.acnqp_set_long_polish(self._h, 1), "acnqp_set_long_polish")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -154,6 +154,7 @@ struct acnqp_handle {
   int32_t* pol_stats = nullptr;   // device counters of the polish kernel, summed over the handle's life (acnqp_polish_stats);
                                   // [16]: problems taken by the launches alongside the solver (acnqp_debug_polish_alongside)
   hipStream_t aux = nullptr;      // the polish launches that run alongside a solver launch (launch_with_polish)
+  bool long_polish = false;       // acnqp_set_long_polish: polish_long_shape routes run the long-horizon polish
   // the post-solve host entries' device staging (acn_qp_post.hpp: the whole-call arrays and one chunk).  ONE buffer for
   // the three: each runs on slot[0].st, synchronises it before reserve() and returns synchronised
   DevBuf post_stage;
@@ -195,9 +196,13 @@ struct Kernels {
 // the polish's system, -1: no polish for this shape.
 int polish_block_doubles(const acnqp_handle* h, const acnqp::Route& rt) {
   static const bool no_polish = std::getenv("ACNQP_NO_POLISH") != nullptr;   // diagnostic
-  if (no_polish || !rt.polish_shape) return -1;
+  if (no_polish) return -1;
   const acnqp::SiteShape& s = h->shape;
   const int nrow_site = s.M + s.has_peak;
+  // the long-horizon polish (acn_qp_polish_long.hpp): the handle's switch; its blocks live in its slab, sized for the worst case
+  if (rt.polish_long_shape)
+    return h->long_polish && acnqp::polish_long_holds(s.N, rt.t_max, rt.k_sessions, s.Mg, nrow_site) ? acnqp::polish_long_block_doubles(rt.t_max, s.Mg) : -1;
+  if (!rt.polish_shape) return -1;
   // LDS of a polish workgroup: where the solver kernel runs two workgroups per CU (the headline shape: one column tile,
   // one row tile, one session slot: 77 KB each) the polish takes no more than one of those slots, so that it starts as
   // soon as ANY solver workgroup of a neighbouring stream's launch ends; elsewhere the whole CU
@@ -587,21 +592,27 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   // (not the two-row-tile route of horizons <= 12, ACNQP_ROUTE_WAVE3: measured a LOSS there -- configs[3] site 3, 1,024
   //  problems: 7.20-7.36 ms without, 8.02-8.18 ms with; two rounds of problems on 512 slots hand half their stragglers over in
   //  mid-launch, and 16 workgroups then work through a list that the serial launch spreads over the chip)
-  const bool alongside = nothing_follows && !no_alongside && rt.wv > 0 && rt.wv != 3 && a.queue != nullptr;
+  // (nor the long-horizon polish, on ACNQP_ROUTE_WAVE5 either: it runs as a serial launch only)
+  const bool lng = rt.polish_long_shape;
+  const bool alongside = nothing_follows && !no_alongside && rt.wv > 0 && rt.wv != 3 && a.queue != nullptr && !lng;
   const acnqp::SiteShape& s = h->shape;
   const acnqp::SiteDev* d = &h->site;
   const int nrow_site = s.M + s.has_peak;
   // [0] queue of the polish kernel, [1] queue of the resume launch, [2] list length; list[B]; multipliers [B][Mg][Tm]
   // unless the caller wants them anyway; then the polish's global scratch for Schur systems beyond its LDS
-  const int pol_max = acnqp::polish_max_rows(nrow_site, p->t_max);
-  const int pol_grid = std::max(1, std::min(p->batch, a.grid_oversub > 1 ? 32 : h->cus));
+  // (the long-horizon polish: tables for the worst case of the shape, so the solver's row count never declines a hand-over)
+  const int pol_max = lng ? acnqp::polish_long_rows(s.Mg, p->t_max) : acnqp::polish_max_rows(nrow_site, p->t_max);
+  const int pol_grid = lng ? acnqp::polish_long_grid(p->batch) : std::max(1, std::min(p->batch, a.grid_oversub > 1 ? 32 : h->cus));
+  const size_t sbytes = lng ? (size_t)acnqp::polish_long_slab_bytes(s.N, p->t_max, p->k_sessions, s.Mg, nrow_site, pol_grid) : 0;
   const size_t ybytes = r->y ? 0 : (size_t)p->batch * s.Mg * p->t_max * sizeof(double);
   const size_t lbytes = ((size_t)p->batch * sizeof(int32_t) + 255) & ~(size_t)255;
-  const size_t need = 256 + lbytes + ybytes;
+  const size_t yb256 = (ybytes + 255) & ~(size_t)255;
+  const size_t need = 256 + lbytes + (lng ? yb256 + sbytes : ybytes);   // (then the long-horizon polish's slabs, one per workgroup)
   HIP_TRY(reserve_behind(st, {{&wk->pol, need}}));
   int32_t* ctr = static_cast<int32_t*>(wk->pol.p);
   int32_t* list = ctr + 64;
   double* ybuf = r->y ? r->y : reinterpret_cast<double*>(static_cast<char*>(wk->pol.p) + 256 + lbytes);
+  double* slab = lng ? reinterpret_cast<double*>(static_cast<char*>(wk->pol.p) + 256 + lbytes + yb256) : nullptr;
   HIP_TRY(hipMemsetAsync(ctr, 0, 256, st));   // ([3]: the solver launch's finished problems, for the polish alongside it)
   if (alongside) {
     HIP_TRY(hipMemsetAsync(list, 0xff, lbytes, st));   // -1: not published
@@ -612,7 +623,7 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   acnqp::TiledArgs a1 = a;
   a1.polish_iters = o->polish_iters - o->polish_iters % std::max(1, o->check_every);   // the exit is taken at a residual check
   if (a1.polish_iters < o->check_every) a1.polish_iters = o->check_every;
-  a1.pol_list = list; a1.pol_count = ctr + 2; a1.y_out = ybuf; a1.pol_rows = pol_max;
+  a1.pol_list = list; a1.pol_count = ctr + 2; a1.y_out = ybuf; a1.pol_rows = lng ? pol_max + 8 : pol_max;   // (polish_fits asks for 8 rows of head room)
   // (measured, wave kernel: the early hand-over takes 5 % off the headline launch and 23 % off configs[3] site 0, and hands
   //  ten times as many problems to the polish -- one 256-batch per call 81 -> 62 k QP/s, the table path 654 -> 580 k: off
   //  by default; options.polish_stall, ABI v9, is the caller's switch, the environment variable the diagnostic one)
@@ -624,7 +635,8 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   if (*e == hipSuccess) {
     acnqp::PolishArgs pa;
     pa.B = p->batch; pa.N = s.N; pa.Tm = p->t_max; pa.K = p->k_sessions; pa.M = s.M; pa.Mg = s.Mg; pa.cone = s.cone;
-    pa.has_peak = s.has_peak; pa.max_rows = pol_max; pa.blk_doubles = pol_blk; pa.max_sess = acnqp::polish_max_sess(s.N, p->k_sessions);
+    pa.has_peak = s.has_peak; pa.max_rows = pol_max; pa.blk_doubles = pol_blk;
+    pa.max_sess = lng ? acnqp::polish_long_sess(s.N, p->k_sessions) : acnqp::polish_max_sess(s.N, p->k_sessions);
     pa.G = d->Gabi; pa.limits = d->limabi;
     pa.horizon = p->horizon; pa.lb = p->lb; pa.ub = p->ub; pa.q = p->q; pa.pdiag = p->pdiag;
     pa.s_off = p->s_off; pa.s_len = p->s_len; pa.s_cap = p->s_cap; pa.s_eq = p->s_eq; pa.peak = s.has_peak ? p->peak : nullptr;
@@ -649,7 +661,7 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
     }
     // (pipelined chunks hand a handful of problems over: few workgroups, so that the launch does not queue for 256 slots
     //  behind the neighbouring streams' solver launches)
-    if (*e == hipSuccess) *e = acnqp::launch_polish(pa, pol_grid, st);
+    if (*e == hipSuccess) *e = acnqp::launch_polish(pa, pol_grid, st, slab);
   }
   if (*e == hipSuccess) {
     acnqp::TiledArgs a3 = a;
@@ -728,6 +740,12 @@ static float event_pair_ms(acnqp_handle* h, long long launch) {
   float ms = -1.0f;
   if (hipEventElapsedTime(&ms, h->ev_start[k], h->ev_stop[k]) != hipSuccess) return -1.0f;
   return ms;
+}
+
+int acnqp_set_long_polish(acnqp_handle* h, int32_t on) {
+  if (!h) return fail(ACNQP_ERR_INVALID, "acnqp_set_long_polish: null handle");
+  h->long_polish = on != 0;
+  return ACNQP_OK;
 }
 
 int64_t acnqp_launch_count(acnqp_handle* h) { return h ? (int64_t)h->launches : 0; }

@@ -13,6 +13,7 @@
 #include "acn_qp_stream.hpp"
 #include "acn_qp_long.hpp"
 #include "acn_qp_polish.hpp"
+#include "acn_qp_polslab.hpp"
 #include "acn_qp_route.hpp"
 
 namespace acnqp {
@@ -115,7 +116,14 @@ hipError_t launch_long(const StreamArgs& sa, hipStream_t st, bool lds_resident);
 int polish_blocks_that_fit(int N, int Tm, int Mg, int nrow, int max_sess, int lds_bytes);   // LDS doubles for the per-period blocks (<= the worst case)
 int polish_max_sess(int N, int K);                                            // session columns the capacitance matrix holds
 int polish_max_rows(int nrow, int Tm);                                        // rows the row tables hold
-hipError_t launch_polish(const PolishArgs& pa, int max_grid, hipStream_t st);
+// (a horizon beyond 32 goes to the long-horizon kernel with `long_slab`, its workgroups' slabs; null there: an error)
+hipError_t launch_polish(const PolishArgs& pa, int max_grid, hipStream_t st, double* long_slab = nullptr);
+// long-horizon polish kernel (acn_qp_polish_long.hpp): horizons 33 ... 288, N <= 64; the state in a slab of global memory per
+// workgroup, tables for the worst case of the shape
+int polish_long_grid(int batch);                                              // workgroups (slabs) of a launch
+long long polish_long_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid);   // bytes of the slabs of `grid` workgroups
+int polish_long_block_doubles(int Tm, int Mg);                                // doubles of the packed per-period blocks (PolishArgs.blk_doubles)
+hipError_t launch_polish_long(const PolishArgs& pa, double* slab, int grid, hipStream_t st);
 // general-shape kernel (acn_qp_general.hpp), `threads` in {256, 512, 1024}
 hipError_t launch_general(const GeneralArgs& ga, int threads, hipStream_t st);
 

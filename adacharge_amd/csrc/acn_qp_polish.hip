@@ -11,7 +11,8 @@ int polish_blocks_that_fit(int N, int Tm, int Mg, int nrow, int max_sess, int ld
   return PolishLds::blocks_that_fit(N, Tm, Mg, nrow, polish_max_rows(nrow, Tm), max_sess, std::min(lds_bytes, kLdsPerCu - 2048));
 }
 
-hipError_t launch_polish(const PolishArgs& pa, int max_grid, hipStream_t st) {
+hipError_t launch_polish(const PolishArgs& pa, int max_grid, hipStream_t st, double* long_slab) {
+  if (pa.Tm > 32) return launch_polish_long(pa, long_slab, max_grid, st);   // acn_qp_polish_long.hpp
   const int nrow = pa.M + (pa.has_peak ? 1 : 0);
   const PolishLds L(pa.N, pa.Tm, pa.Mg, nrow, pa.max_rows, pa.blk_doubles, pa.max_sess);
   const size_t lds = (size_t)L.total * sizeof(double);

@@ -100,6 +100,8 @@ struct Route {
   int wv = 0;         // wave-per-problem variant (0: another family)
   bool tiled = false, stream = false, lng = false, lds = false, on_chip = false;
   bool polish_shape = false;   // the shape's half of the polish decision (the LDS fit and the options: acn_qp_api.hip)
+  bool polish_long_shape = false;   // the shape's half of the LONG-horizon polish decision (acn_qp_polish_long.hpp; the handle's
+                                    // switch acnqp_set_long_polish and the options: acn_qp_api.hip).  Never true with polish_shape.
   SiteShape site;     // what it was decided for
   int t_max = 0, k_sessions = 0;
 
@@ -159,6 +161,10 @@ inline Route route_for(const SiteShape& s, int t_max, int k_sessions, int batch,
   // the polish (acn_qp_polish.hpp): small sites, separable objective, served by an on-chip kernel
   r.polish_shape = r.on_chip && s.N <= 64 && t_max <= 32 && k_sessions <= kRouteMaxK && !s.has_flat && !s.has_max &&
                    s.M + s.has_peak > 0;
+  // the long-horizon polish (acn_qp_polish_long.hpp): the same sites at horizons 33 ... 288, behind the four-wave route and
+  // the long-horizon kernel's workspace variant (not the general kernel's three row tiles)
+  r.polish_long_shape = s.N <= 64 && t_max > 32 && t_max <= 288 && k_sessions <= kRouteMaxK && !s.has_flat && !s.has_max &&
+                        s.M + s.has_peak > 0 && (r.family == ACNQP_ROUTE_WAVE5 || r.family == ACNQP_ROUTE_LONG_WS);
   return r;
 }
 

@@ -367,6 +367,15 @@ int32_t acnqp_accel_columns(acnqp_handle* h, int32_t t_max, int32_t k_sessions, 
  * a null handle or a shape acnqp_solve_batch refuses.  Test plumbing: lets a test assert which kernel it exercises. */
 int32_t acnqp_route(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t batch, int32_t* polish);
 
+/* Additive to ABI v10 (a new symbol; no structure changes): the polish for horizons 33 ... 288 on sites of up to 64 EVSEs
+ * (at most four session slots, no load-flattening or demand-charge row, behind ACNQP_ROUTE_WAVE5 and ACNQP_ROUTE_LONG_WS).
+ * A property of the handle, OFF after acnqp_create: with it off every launch does what it did before there was such a
+ * polish.  on != 0: a cold-started launch of such a shape with 0 < options.polish_iters < options.max_iter hands the
+ * problems that have not converged after polish_iters iterations to the long-horizon polish kernel, and acnqp_route
+ * reports polish = 1 for the shape.  Read on the host when a launch is planned; the decision is a function of the shape,
+ * the options and this switch, never of the batch size.  Returns ACNQP_OK, ACNQP_ERR_INVALID for a null handle.      */
+int acnqp_set_long_polish(acnqp_handle* h, int32_t on);
+
 /* ---- dual report (additive to ABI v10: new symbols only, no existing structure changes) -------------------------------
  * For any answer (x, y) of the library: the multipliers of the energy rows and of the rate bounds, and the KKT
  * residuals of the full primal-dual point, computed on the GPU by one kernel that is independent of the solver loop.
