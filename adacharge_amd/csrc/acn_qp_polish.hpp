@@ -14,58 +14,20 @@
 // EVSE i, TQ = ceil(Tm / 4) <= 8, in registers: a session's sums are two lane exchanges inside the EVSE's quad.  The site
 // rows live in LDS: G, G x, G dx, the rows of the Schur system (normal + tangent row of every tight disc, period-major)
 // and its packed lower triangle.
+//
+// The kernel below reads top to bottom as step 1 ... step 10 of the specification.  What a thread does on its own
+// variables and sessions -- register arrays and bit masks, fully unrolled -- is written out here; every step on the LDS
+// tables is a call into acn_qp_polish_steps.hpp (PolishArgs and the kPol* constants live there too), with the tight rows
+// as PolTightMask and the blocking-constraint codes as PolCode8.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "acn_qp_common.hpp"
 #include "acn_qp_polclaim.hpp"
+#include "acn_qp_polish_steps.hpp"
 
 namespace acnqp {
-
-constexpr int kPolThreads = 256;
-constexpr int kPolMaxRounds = 96;
-constexpr int kPolMaxRows = 256;      // rows of the Schur system at most (row tables; one thread per row in the triangular solves)
-constexpr double kPolTolBound = 1e-7;    // |x - bound| below which the ADMM iterate counts as "on the bound"
-constexpr double kPolTolRow = 1e-9;      // relative size of a site-row multiplier that counts as non-zero
-constexpr double kPolTolStep = 1e-7;     // convergence of a round: |dx|_inf <= tol max(1, |x|_inf) (1e-9 sat below the noise the
-                                         // regularised solve leaves in dx on the degenerate instances: six idle rounds; the KKT check decides)
-constexpr double kPolTolDual = 1e-9;     // a multiplier below -tol max(1, |q|_inf) leaves the working set
-constexpr double kPolTolPrimal = 1e-9;   // accepted violation of a row, relative to max(1, limit)
-constexpr double kPolRegRel = 1e-9;      // dual regularisation of the Schur system, relative to pd ...
-constexpr double kPolRegDiag = 1e-12;    // ... and to the largest |R_a|^2, whichever is larger (oracle/polish_ref.py: REG_DIAG)
-constexpr int kPolStallRounds = 4;       // full steps without progress that count as the noise floor of the regularised solve
-constexpr double kPolTangentMin = 1e-7;  // a disc with a multiplier below tol max(1, |q|_inf) gets no curvature row
-
-struct PolishArgs {
-  int B, N, Tm, K, M, Mg, cone, has_peak;
-  int max_rows;      // rows of the Schur system the row tables hold (<= kPolMaxRows)
-  int blk_doubles;   // LDS doubles for the per-period blocks of the system (phase 5)
-  int max_sess;      // columns of V (tight sessions with free variables) the capacitance matrix holds
-  const double *G, *limits;        // acnqp_site.G [Mg][N] and limits [M] as the caller gave them (no equilibration)
-  const int32_t* horizon;
-  const double *lb, *ub, *q, *pdiag;
-  const int32_t *s_off, *s_len;
-  const double* s_cap;
-  const uint8_t* s_eq;
-  const double* peak;
-  double *x, *y;                   // in: the ADMM iterate (schedule, site-row multipliers in the caller's units); out: the optimum
-  int32_t *status, *iters;
-  double *pri, *dua, *obj;
-  const int32_t *list, *count;     // problems left to the polish by the solver kernel
-  int32_t* queue;                  // launch counter of the work queue
-  int32_t* stats;                  // [0] attempted, [1] succeeded, [2] gave up: rows, [3] pivot, [4] rounds, [5] verification
-  double reg_rel;
-  // -- a launch ALONGSIDE the solver launch that fills `list` (acn_qp_polclaim.hpp): entries are claimed as
-  //    they are published, until the solver's `retired` count reaches `expected` problems or max_polls polls have passed
-  int alongside;                   // 0: the serial launch behind the solver (the list is complete: `count` entries)
-  int expected;
-  const int32_t* retired;
-  long long max_polls;
-  int32_t* taken;                  // problems the launches alongside took (acnqp_debug_polish_alongside)
-};
-
-constexpr int kPolMaxSess = 128;      // tight sessions with free variables (columns of V) at most (PolishArgs.max_sess <= this)
 
 // LDS carve-up in doubles (host: size; device: offsets)
 struct PolishLds {
@@ -106,81 +68,6 @@ struct PolishLds {
   }
 };
 
-// LDS traffic inside ONE wave: writes of some lanes read by others in the next step (the tiled kernel's idiom)
-__device__ inline void pol_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// B_t^-1 applied in place to the rows [a0, a0 + mt) of the LDS vector `v`, by ONE wave: blk = the block's packed L D L'
-// (L unscaled, acn_qp_polish.hpp phase 6a), dinv = 1 / D of its rows.
-__device__ inline void pol_block_solve(const double* blk, const double* dinv, double* v, int mt, int lane) {
-  for (int k = 0; k < mt; ++k) {          // L z = v
-    const double zk = v[k] * dinv[k];
-    for (int r = k + 1 + lane; r < mt; r += 64) v[r] -= blk[r * (r + 1) / 2 + k] * zk;
-    pol_wave_sync();
-  }
-  for (int r = lane; r < mt; r += 64) v[r] *= dinv[r];
-  pol_wave_sync();
-  for (int k = mt - 1; k > 0; --k) {      // L' x = D^-1 z
-    const double xk = v[k];
-    for (int c = lane; c < k; c += 64) v[c] -= blk[k * (k + 1) / 2 + c] * dinv[c] * xk;
-    pol_wave_sync();
-  }
-}
-
-__device__ inline double pol_quad_sum(double v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  return v;
-}
-__device__ inline double pol_wave_max(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-// block-wide max; every thread gets it (two barriers; `red` holds one double per wave)
-__device__ inline double pol_block_max(double v, double* red) {
-  v = pol_wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-__device__ inline double pol_block_sum(double v, double* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-// block-wide minimum with a payload; ties go to the smaller code (deterministic).  code < 0: no candidate.
-__device__ inline void pol_block_argmin(double& v, int& code, double* red) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o);
-    const int oc = __shfl_xor(code, o);
-    const bool take = oc >= 0 && (code < 0 || ov < v || (ov == v && oc < code));
-    v = take ? ov : v;
-    code = take ? oc : code;
-  }
-  int* redi = reinterpret_cast<int*>(red + 4);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = v; redi[threadIdx.x >> 6] = code; }
-  __syncthreads();
-  v = red[0]; code = redi[0];
-  for (int w = 1; w < 4; ++w) {
-    const double ov = red[w];
-    const int oc = redi[w];
-    const bool take = oc >= 0 && (code < 0 || ov < v || (ov == v && oc < code));
-    v = take ? ov : v;
-    code = take ? oc : code;
-  }
-}
-
-// blocking-constraint / release codes: kind in the top bits
-constexpr int kPolLb = 0, kPolUb = 1, kPolSess = 2, kPolRow = 3;
-__device__ inline int pol_code(int kind, int p0, int p1) { return (kind << 24) | (p0 << 8) | p1; }
-
 // kPolTQ: periods per thread, 4 (horizons <= 16) or 8 (<= 32).  Two workgroups per CU: a polish workgroup then takes ONE of
 // the two slots the register-resident solver kernel's workgroups take (256 registers, <= 76 KB of LDS on its shapes) and
 // starts as soon as any of them ends -- at one per CU (362 registers) it needed a CU to itself and, in the pipelined host
@@ -202,19 +89,19 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
   int* RT = RR + A.max_rows;                           // its period
   int* TSTART = RT + A.max_rows;                       // Schur rows of period t: [TSTART[t], TSTART[t + 1])
   int* BOFF = TSTART + Tm + 1;                         // packed block of period t: BLK + BOFF[t]
-  unsigned* RACT = reinterpret_cast<unsigned*>(BOFF + Tm + 1);   // per site row: bit t = tight at period t
-  int* MISC = reinterpret_cast<int*>(RACT + nrow);     // [0] m, [1] fail flag, [2] session columns, [3] bad pivot
+  const PolTightMask RACT{reinterpret_cast<unsigned*>(BOFF + Tm + 1)};   // per site row: bit t = tight at period t
+  int* MISC = reinterpret_cast<int*>(RACT.w + nrow);   // [2] session columns, [3] bad pivot
   int* SI = MISC + 8;                                  // session columns of V: EVSE, slot
   int* SKS = SI + MS;
   signed char* CS = reinterpret_cast<signed char*>(SKS + MS);   // per (i, t): -2 not free, -1 free, k >= 0 free in tight session k
+  const PolRows R{RJ, RR, RT, RC0, RC1, RCA, RDG, LAM};
+  typedef PolCode8 Code;
   __shared__ int q_slot;
 
   const int tid = threadIdx.x;
   const int i = tid >> 2, h = tid & 3;
   const int TQ = (Tm + 3) >> 2;
   const bool iv = i < N;
-  auto row_j = [&](int r) { return r < M ? r : Mg - 1; };
-  auto row_is_disc = [&](int r) { return soc && r < M; };
 
   for (int q_round = 0;; ++q_round) {
     int pos, b;
@@ -228,14 +115,14 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
       b = __builtin_amdgcn_readfirstlane(__hip_atomic_load(A.list + pos, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT));
       if (b < 0 || b >= A.B) continue;   // (never expected: a claimed entry is a published problem)
     } else {
-      const int nlist = *A.count;
-      pos = queue_next(A.queue, nlist < A.B ? nlist : A.B, q_round, &q_slot);
+      pos = pol_next_listed(A, q_round, &q_slot);
       if (pos < 0) break;
       b = A.list[pos];
     }
     if (A.status[b] != kStatusPolish) continue;   // (block-uniform)
     if (tid == 0) atomicAdd(A.stats + 0, 1);
     if (tid == 0 && A.alongside) atomicAdd(A.taken, 1);
+    const PolSite S{N, Tm, M, Mg, nrow, b, soc, A.limits, A.peak};
     const bool eq = A.s_eq[b] != 0;
     const double pd_user = A.pdiag[b];
 
@@ -292,26 +179,14 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
     }
     // ---- site data; first guess of the tight site rows from the ADMM's multipliers ----------------------------------
     for (int k = tid; k < Mg * N; k += kPolThreads) Gs[k] = A.G[k];
-    for (int r = tid; r < nrow; r += kPolThreads) RACT[r] = 0;
-    __syncthreads();
-    for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-      const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-      const double y0 = A.y[((size_t)b * Mg + j) * Tm + t];
-      const double mag = row_is_disc(r) ? hypot(y0, A.y[((size_t)b * Mg + j + M) * Tm + t]) : y0;
-      const double lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-      const bool on = mag > kPolTolRow * qn && lim < 1e299;
-      NU[k] = on ? mag : 0.0;
-      if (on) atomicOr(&RACT[r], 1u << t);
-    }
+    pol_first_guess(S, RACT, A.y, NU, qn, tid);
     __syncthreads();
 
     int why = 4, rounds = 0;   // reason of a failure (index into stats), rounds made
-    int stall = 0;             // full steps in a row without progress (noise floor)
-    double best_step = 1e300;
-    // coarse phase clock (thread 0, 100 MHz ticks summed into stats[8 + phase]): where a polish spends its time
-    unsigned long long tick = wall_clock64();
-    unsigned tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define POL_TICK(ph) do { const unsigned long long _n = wall_clock64(); tacc[ph] += (unsigned)(_n - tick); tick = _n; } while (0)
+    PolStall stall;
+    stall.reset();
+    PolClock clk;
+    clk.start();
     bool success = false;
     double stat_out = 0, prim_out = 0;
     for (int rnd = 0; rnd < kPolMaxRounds; ++rnd) {
@@ -347,86 +222,12 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
       }
       __syncthreads();
       // ---- (2) G x ------------------------------------------------------------------------------------------------------
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) {
-        const int j = k / Tm, t = k - j * Tm;
-        double s = 0;
-        for (int e = 0; e < N; ++e) s += Gs[j * N + e] * Xs[e * Tm + t];
-        U[k] = s;
-      }
+      pol_g_times<int>(Gs, Xs, U, N, Tm, Mg, tid);
       __syncthreads();
       // ---- (3) rows of the Schur system, period-major: pair k = t nrow + r of (period, site row) -> 0 / 1 / 2 rows (a tight
       // disc: its normal row and, with a multiplier worth it, its tangent row); offsets by a block-wide exclusive scan
-      {
-        int base = 0;
-        bool over = false;
-        for (int k0 = 0; k0 < nrow * Tm; k0 += kPolThreads) {
-          const int k = k0 + tid;
-          const bool in = k < nrow * Tm;
-          const int t = in ? k / nrow : 0, r = in ? k - t * nrow : 0, j = row_j(r);
-          int need = 0;
-          double lim = 0, u0 = 0, u1 = 0, val = 0, nu = 0;
-          if (in && ((RACT[r] >> t) & 1u)) {
-            lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-            if (row_is_disc(r)) {
-              u0 = U[j * Tm + t]; u1 = U[(j + M) * Tm + t];
-              val = hypot(u0, u1);
-              nu = NU[r * Tm + t];
-              need = val > 1e-12 ? (nu > kPolTangentMin * qn ? 2 : 1) : 0;
-            } else {
-              need = 1;
-            }
-          }
-          int incl = need;
-          for (int o = 1; o < 64; o <<= 1) { const int nb = __shfl_up(incl, o); incl += (tid & 63) >= o ? nb : 0; }
-          int* WT = reinterpret_cast<int*>(RED);
-          __syncthreads();
-          if ((tid & 63) == 63) WT[tid >> 6] = incl;
-          __syncthreads();
-          int before = base;
-          for (int w = 0; w < (tid >> 6); ++w) before += WT[w];
-          const int total = WT[0] + WT[1] + WT[2] + WT[3];
-          const int m0 = before + incl - need;
-          if (in && r == 0) TSTART[t] = m0;
-          if (base + total > A.max_rows) { over = true; break; }   // (block-uniform)
-          if (need >= 1) {
-            if (row_is_disc(r)) {
-              const double n0 = u0 / val, n1 = u1 / val;
-              RJ[m0] = j; RR[m0] = r; RT[m0] = t; RC0[m0] = n0; RC1[m0] = n1; RCA[m0] = lim - val; RDG[m0] = 0.0;
-              if (need == 2) {
-                RJ[m0 + 1] = j; RR[m0 + 1] = -1 - r; RT[m0 + 1] = t; RC0[m0 + 1] = -n1; RC1[m0 + 1] = n0; RCA[m0 + 1] = 0.0;
-                RDG[m0 + 1] = pd * val / nu;
-              }
-            } else {
-              RJ[m0] = j; RR[m0] = r; RT[m0] = t; RC0[m0] = 1.0; RC1[m0] = 0.0; RCA[m0] = lim - U[j * Tm + t]; RDG[m0] = 0.0;
-            }
-          }
-          base += total;
-        }
-        if (tid == 0) { TSTART[Tm] = base; MISC[0] = base; MISC[1] = over ? 1 : 0; }
-        // session columns of V: the tight sessions with free variables, in (EVSE, slot) order (same scan)
-        int cnt = 0;
-        if (h == 0 && iv) {
-#pragma unroll
-          for (int ks = 0; ks < kMaxK; ++ks) cnt += son[ks] ? 1 : 0;
-        }
-        int incl = cnt;
-        for (int o = 1; o < 64; o <<= 1) { const int nb = __shfl_up(incl, o); incl += (tid & 63) >= o ? nb : 0; }
-        int* WT = reinterpret_cast<int*>(RED);
-        __syncthreads();
-        if ((tid & 63) == 63) WT[tid >> 6] = incl;
-        __syncthreads();
-        int pos = incl - cnt;
-        for (int w = 0; w < (tid >> 6); ++w) pos += WT[w];
-        if (tid == 0) MISC[2] = WT[0] + WT[1] + WT[2] + WT[3];
-        if (h == 0 && iv) {
-#pragma unroll
-          for (int ks = 0; ks < kMaxK; ++ks)
-            if (son[ks]) {
-              if (pos < MS) { SI[pos] = i; SKS[pos] = ks; SISQ[pos] = 1.0 / sqrt(nfree[ks]); }
-              ++pos;
-            }
-        }
-      }
+      pol_step3_rows(S, RACT, R, U, NU, TSTART, A.max_rows, qn, pd, RED, tid);
+      pol_step3_columns(son, nfree, h == 0 && iv, i, MS, SI, SKS, SISQ, MISC + 2, RED, [](int, int) {});
       // ---- (4) gradient on the free variables, v_free = -P g + pd e ---------------------------------------------------------
       double Eg[kMaxK];
 #pragma unroll
@@ -452,89 +253,22 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         if (iv && k < TQ && t < Tm) Ds[i * Tm + t] = -pg + pd * e;
       }
       __syncthreads();
-      const int m = MISC[0], nsa = MISC[2];
-      if (MISC[1] || nsa > MS) { why = 2; break; }
-      if (tid == 0) {   // packed blocks of B, one per period, one after the other
-        int o = 0;
-        for (int t = 0; t < Tm; ++t) { BOFF[t] = o; const int mt = TSTART[t + 1] - TSTART[t]; o += mt * (mt + 1) / 2; }
-        BOFF[Tm] = o;
-        MISC[3] = 0;
-      }
+      const int m = TSTART[Tm], nsa = MISC[2];
+      if (m > A.max_rows || nsa > MS) { why = 2; break; }   // (block-uniform)
+      if (tid == 0) { pol_block_offsets(TSTART, BOFF, Tm); MISC[3] = 0; }
       __syncthreads();
       const int E = BOFF[Tm];
       if (E > A.blk_doubles) { why = 2; break; }
-      POL_TICK(0);
-      // R_a at EVSE e (a row lives on its own period's variables)
-      auto row_at = [&](int a_, int e_) __attribute__((always_inline)) -> double {
-        const int ja = RJ[a_];
-        const double c1 = RC1[a_];
-        return RC0[a_] * Gs[ja * N + e_] + (c1 != 0.0 ? c1 * Gs[(ja + M) * N + e_] : 0.0);
-      };
+      clk.lap(0);
       // ---- (5) rhs = R v_free - pd c_A;  B = R R' + diag + reg I, BLOCK DIAGONAL by period;  C = I ---------------------------
-      // (R P R' + diag + reg I) lam = rhs with R P R' = R R' - V V', V[:, s] = R 1_s / sqrt(n_s) over the tight sessions with free
-      // variables: Woodbury -- lam = y + B^-1 V w, y = B^-1 rhs, (I - V' B^-1 V) w = V' y.  Per-period L D L' factors of <= 2 nrow
-      // rows and one of the size of the tight sessions, instead of one dense factorisation of the size of ALL tight site rows:
-      // the 200-row systems of the horizon-24 stragglers fit, and a round costs what its blocks cost (oracle/polish_ref.py).
-      double dloc = 0;
-      for (int a = tid; a < m; a += kPolThreads) {
-        const int ta = RT[a];
-        const double* g0 = Gs + RJ[a] * N;          // (the row's constants once, not once per EVSE: this loop and the block
-        const double* g1 = g0 + M * N;              //  build below were 20 us of a 79 us round as chains of LDS reads)
-        const double c0 = RC0[a], c1 = RC1[a];
-        const bool two = c1 != 0.0;
-        double sacc = 0, d2 = 0;
-        for (int e = 0; e < N; ++e) {
-          const double ra = c0 * g0[e] + (two ? c1 * g1[e] : 0.0);
-          sacc += ra * Ds[e * Tm + ta];
-          d2 += CS[e * Tm + ta] != -2 ? ra * ra : 0.0;
-        }
-        LAM[a] = sacc - pd * RCA[a];
-        dloc = fmax(dloc, d2);
-      }
-      const double reg = fmax(kPolRegRel * pd, kPolRegDiag * pol_block_max(dloc, RED));
-      {
-        int t = 0;
-        for (int p = tid; p < E; p += kPolThreads) {
-          while (BOFF[t + 1] <= p) ++t;
-          const int q_ = p - BOFF[t];
-          int ar = (int)((sqrt(8.0 * (double)q_ + 1.0) - 1.0) * 0.5);
-          while ((ar + 1) * (ar + 2) / 2 <= q_) ++ar;
-          while (ar * (ar + 1) / 2 > q_) --ar;
-          const int cr = q_ - ar * (ar + 1) / 2;
-          const int a = TSTART[t] + ar, c = TSTART[t] + cr;
-          const double *ga0 = Gs + RJ[a] * N, *ga1 = ga0 + M * N, *gc0 = Gs + RJ[c] * N, *gc1 = gc0 + M * N;
-          const double a0c = RC0[a], a1c = RC1[a], c0c = RC0[c], c1c = RC1[c];
-          const bool atwo = a1c != 0.0, ctwo = c1c != 0.0;
-          double sacc = 0;
-          for (int e = 0; e < N; ++e) {
-            const double ra = a0c * ga0[e] + (atwo ? a1c * ga1[e] : 0.0);
-            const double rc = c0c * gc0[e] + (ctwo ? c1c * gc1[e] : 0.0);
-            sacc += CS[e * Tm + t] != -2 ? ra * rc : 0.0;
-          }
-          BLK[p] = sacc + (a == c ? RDG[a] + reg : 0.0);
-        }
-      }
-      for (int p = tid; p < nsa * (nsa + 1) / 2; p += kPolThreads) CAP[p] = 0.0;
-      __syncthreads();
-      for (int c = tid; c < nsa; c += kPolThreads) CAP[c * (c + 1) / 2 + c] = 1.0;
-      POL_TICK(1);
+      pol_step5<int>(R, Gs, Ds, CS, TSTART, BOFF, BLK, CAP, N, Tm, M, m, E, nsa, pd, RED, tid);
+      clk.lap(1);
       // ---- (6a) L D L' of every block, a wave per block (unit lower L stored unscaled, 1 / D in RDG) ------------------------------
       const int wave_ = tid >> 6, lane_ = tid & 63;
       for (int t = wave_; t < Tm; t += 4) {
         const int mt = TSTART[t + 1] - TSTART[t], a0 = TSTART[t];
         double* blk = BLK + BOFF[t];
-        bool bad = false;
-        for (int k = 0; k < mt && !bad; ++k) {
-          const double piv = blk[k * (k + 1) / 2 + k];
-          if (!(piv > 0.0)) { bad = true; break; }   // (wave-uniform)
-          const double pinv = 1.0 / piv;
-          for (int rr = k + 1 + (lane_ >> 3); rr < mt; rr += 8) {
-            const double lr = blk[rr * (rr + 1) / 2 + k] * pinv;
-            for (int c = k + 1 + (lane_ & 7); c <= rr; c += 8) blk[rr * (rr + 1) / 2 + c] -= lr * blk[c * (c + 1) / 2 + k];
-          }
-          pol_wave_sync();
-        }
-        if (bad) { if (lane_ == 0) MISC[3] = 1; continue; }
+        if (!pol_block_factor(blk, mt, lane_)) { if (lane_ == 0) MISC[3] = 1; continue; }
         for (int k = lane_; k < mt; k += 64) RDG[a0 + k] = 1.0 / blk[k * (k + 1) / 2 + k];
       }
       __syncthreads();
@@ -551,7 +285,7 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         double z = 0;
         for (int t = 0; t < Tm; ++t)
           if (CS[ic * Tm + t] == ks)
-            for (int a = TSTART[t]; a < TSTART[t + 1]; ++a) z += row_at(a, ic) * LAM[a];
+            for (int a = TSTART[t]; a < TSTART[t + 1]; ++a) z += R.at(Gs, N, M, a, ic) * LAM[a];
         ZV[c] = z * SISQ[c];
       }
       for (int t = 0; t < Tm; ++t) {
@@ -561,7 +295,7 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         for (int idx = tid; idx < mt * nsa; idx += kPolThreads) {
           const int k = idx / nsa, c = idx - k * nsa;
           const int ic = SI[c];
-          ZB[k * MS + c] = CS[ic * Tm + t] == SKS[c] ? row_at(a0 + k, ic) * SISQ[c] : 0.0;
+          ZB[k * MS + c] = CS[ic * Tm + t] == SKS[c] ? R.at(Gs, N, M, a0 + k, ic) * SISQ[c] : 0.0;
         }
         __syncthreads();
         for (int c = tid; c < nsa; c += kPolThreads) {
@@ -573,9 +307,7 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         }
         __syncthreads();
         for (int p = tid; p < nsa * (nsa + 1) / 2; p += kPolThreads) {
-          int c = (int)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-          while ((c + 1) * (c + 2) / 2 <= p) ++c;
-          while (c * (c + 1) / 2 > p) --c;
+          const int c = pol_tri_row(p);
           const int c2 = p - c * (c + 1) / 2;
           if (CS[SI[c] * Tm + t] != SKS[c] || CS[SI[c2] * Tm + t] != SKS[c2]) continue;
           double sacc = 0;
@@ -584,49 +316,16 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         }
         __syncthreads();
       }
-      POL_TICK(2);
+      clk.lap(2);
       // ---- (6d) C = L D L' (packed, one barrier per column), C w = V' y ----------------------------------------------------------------
-      bool bad_pivot = false;
-      for (int k = 0; k < nsa; ++k) {
-        __syncthreads();
-        const double piv = CAP[k * (k + 1) / 2 + k];
-        if (!(piv > 0.0)) { bad_pivot = true; break; }   // (uniform: every thread reads the same entry)
-        const double pinv = 1.0 / piv;
-        for (int rr = k + 1 + (tid >> 4); rr < nsa; rr += 16) {
-          const double lr = CAP[rr * (rr + 1) / 2 + k] * pinv;
-          double* row = CAP + rr * (rr + 1) / 2;
-          for (int c = k + 1 + (tid & 15); c <= rr; c += 16) row[c] -= lr * CAP[c * (c + 1) / 2 + k];
-        }
-      }
-      if (bad_pivot) { why = 3; break; }
-      {
-        __syncthreads();
-        double* DI = ZB;   // 1 / D of C (the Z buffer is free now)
-        for (int k = tid; k < nsa; k += kPolThreads) DI[k] = 1.0 / CAP[k * (k + 1) / 2 + k];
-        __syncthreads();
-        double acc = tid < nsa ? ZV[tid] : 0.0;   // forward: L z = V' y (thread r owns z_r)
-        for (int k = 0; k < nsa; ++k) {
-          if (tid == k) ZV[k] = acc;
-          __syncthreads();
-          if (tid > k && tid < nsa) acc -= CAP[tid * (tid + 1) / 2 + k] * DI[k] * ZV[k];
-        }
-        __syncthreads();
-        acc = tid < nsa ? ZV[tid] * DI[tid] : 0.0;   // backward: L' w = D^-1 z
-        const double dme = tid < nsa ? DI[tid] : 0.0;
-        for (int k = nsa - 1; k >= 0; --k) {
-          if (tid == k) ZV[k] = acc;
-          __syncthreads();
-          if (tid < k) acc -= CAP[k * (k + 1) / 2 + tid] * dme * ZV[k];
-        }
-        __syncthreads();
-      }
+      if (!pol_step6d(CAP, ZV, ZB, nsa, tid)) { why = 3; break; }   // (1 / D of C goes into the Z buffer, free now)
       // ---- (6e) lam = y + B^-1 (V w) ---------------------------------------------------------------------------------------------------
       for (int a = tid; a < m; a += kPolThreads) {
         const int ta = RT[a];
         double sacc = 0;
         for (int c = 0; c < nsa; ++c) {
           const int ic = SI[c];
-          if (CS[ic * Tm + ta] == SKS[c]) sacc += row_at(a, ic) * SISQ[c] * ZV[c];
+          if (CS[ic * Tm + ta] == SKS[c]) sacc += R.at(Gs, N, M, a, ic) * SISQ[c] * ZV[c];
         }
         RCA[a] = sacc;
       }
@@ -638,7 +337,7 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
       __syncthreads();
       for (int a = tid; a < m; a += kPolThreads) LAM[a] += RCA[a];
       __syncthreads();
-      POL_TICK(3);
+      clk.lap(3);
       // ---- (7) the step ---------------------------------------------------------------------------------------------------------
       double rl[kPolTQ];   // (R' lam)(i, t), and of the NORMAL rows alone (the multipliers' part of the gradient)
       double rn[kPolTQ];
@@ -677,14 +376,9 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         if (iv && k < TQ && t < Tm) Ds[i * Tm + t] = dv[k];
       }
       __syncthreads();
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) {
-        const int j = k / Tm, t = k - j * Tm;
-        double s = 0;
-        for (int e = 0; e < N; ++e) s += Gs[j * N + e] * Ds[e * Tm + t];
-        DU[k] = s;
-      }
+      pol_g_times<int>(Gs, Ds, DU, N, Tm, Mg, tid);
       __syncthreads();
-      POL_TICK(4);
+      clk.lap(4);
       // ---- (8) ratio test against everything outside the working set ---------------------------------------------------------------
       double alpha = 1.0;
       int block = -1;
@@ -695,10 +389,10 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         const double d = dv[k];
         if (d < -1e-14) {
           const double a_ = fmax((lbv[k] - xv[k]) / d, 0.0);
-          if (a_ < alpha) { alpha = a_; block = pol_code(kPolLb, i, t); }
+          if (a_ < alpha) { alpha = a_; block = Code::make(kPolLb, i, t); }
         } else if (d > 1e-14) {
           const double a_ = fmax((ubv[k] - xv[k]) / d, 0.0);
-          if (a_ < alpha) { alpha = a_; block = pol_code(kPolUb, i, t); }
+          if (a_ < alpha) { alpha = a_; block = Code::make(kPolUb, i, t); }
         }
       }
 #pragma unroll
@@ -709,47 +403,22 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         const double de = pol_quad_sum(s);
         if (h == 0 && shas[ks] && !sact[ks] && de > 1e-14) {
           const double a_ = fmax(cE[ks] / de, 0.0);
-          if (a_ < alpha) { alpha = a_; block = pol_code(kPolSess, i, ks); }
+          if (a_ < alpha) { alpha = a_; block = Code::make(kPolSess, i, ks); }
         }
       }
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-        if ((RACT[r] >> t) & 1u) continue;
-        const double lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-        if (!(lim < 1e299)) continue;
-        if (row_is_disc(r)) {
-          const double u0 = U[j * Tm + t], u1 = U[(j + M) * Tm + t], d0 = DU[j * Tm + t], d1 = DU[(j + M) * Tm + t];
-          const double aa = d0 * d0 + d1 * d1, bb = 2.0 * (u0 * d0 + u1 * d1), cc = u0 * u0 + u1 * u1 - lim * lim;
-          if (aa > 1e-28 && (bb > 0 || cc > 0)) {
-            const double dsc = bb * bb - 4.0 * aa * cc;
-            if (dsc >= 0) {
-              const double a_ = fmax((-bb + sqrt(dsc)) / (2.0 * aa), 0.0);
-              if (a_ < alpha) { alpha = a_; block = pol_code(kPolRow, r, t); }
-            }
-          }
-        } else {
-          const double du = DU[j * Tm + t];
-          if (du > 1e-14) {
-            const double a_ = fmax((lim - U[j * Tm + t]) / du, 0.0);
-            if (a_ < alpha) { alpha = a_; block = pol_code(kPolRow, r, t); }
-          }
-        }
-      }
+      pol_step8_rows<PolTightMask, Code>(S, RACT, U, DU, alpha, block, tid);
       pol_block_argmin(alpha, block, RED);
       if (block < 0) alpha = 1.0;
-      POL_TICK(5);
+      clk.lap(5);
       // ---- (9) move; the new multipliers; the blocking constraint joins the working set ------------------------------------------------
       double xm = 0;
 #pragma unroll
       for (int k = 0; k < kPolTQ; ++k) { xv[k] += alpha * dv[k]; xm = fmax(xm, fabs(xv[k])); }
       const double step = pol_block_max(stepl, RED);
       const double xmax = pol_block_max(xm, RED);
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) NU[k] = 0.0;
-      __syncthreads();
-      for (int a = tid; a < m; a += kPolThreads)
-        if (RR[a] >= 0) NU[RR[a] * Tm + RT[a]] = LAM[a];
+      pol_step9_multipliers(R, NU, m, nrow, Tm, tid);
       if (block >= 0) {
-        const int kind = block >> 24, p0 = (block >> 8) & 0xffff, p1 = block & 0xff;
+        const int kind = Code::kind(block), p0 = Code::p0(block), p1 = Code::p1(block);
         if (kind == kPolLb || kind == kPolUb) {
           if (p0 == i && p1 >= h * TQ && p1 < h * TQ + TQ) {
             const int k = p1 - h * TQ;
@@ -765,21 +434,13 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
             for (int ks = 0; ks < kMaxK; ++ks) if (ks == p1) sact[ks] = true;
           }
         } else if (tid == 0) {
-          RACT[p0] |= 1u << p1;
+          RACT.set(p0, p1, Tm);
         }
       }
       __syncthreads();
-      // noise floor (oracle/polish_ref.py): full steps that have stopped shrinking go to the multiplier test and the KKT check
-      // like a converged one; the check decides, and a failure there ends the polish instead of burning the round limit
-      if (block < 0) {
-        stall = step >= 0.5 * best_step ? stall + 1 : 0;
-        best_step = fmin(best_step, step);
-      } else {
-        stall = 0; best_step = 1e300;
-      }
-      const bool floor_hit = block < 0 && stall >= kPolStallRounds && step <= 1e-3;
-      const bool conv = block < 0 && (step <= kPolTolStep * fmax(1.0, xmax) || floor_hit);
-      POL_TICK(6);
+      stall.update(block, step);
+      const bool conv = stall.converged(block, step, xmax);
+      clk.lap(6);
       if (!conv) continue;
       // ---- (10) multipliers of the whole working set: the most negative one leaves; none: verify and finish ---------------------------------
       double worst = -kPolTolDual * qn;
@@ -795,21 +456,18 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         if (!((validm >> k) & 1u)) continue;
         if ((freem >> k) & 1u) { statl = fmax(statl, fabs(gr)); continue; }
         if ((fixedm >> k) & 1u) continue;
-        if (((atlb >> k) & 1u) && gr < worst) { worst = gr; who = pol_code(kPolLb, i, t); }
-        if (((atub >> k) & 1u) && -gr < worst) { worst = -gr; who = pol_code(kPolUb, i, t); }
+        if (((atlb >> k) & 1u) && gr < worst) { worst = gr; who = Code::make(kPolLb, i, t); }
+        if (((atub >> k) & 1u) && -gr < worst) { worst = -gr; who = Code::make(kPolUb, i, t); }
       }
       if (!eq && h == 0) {
 #pragma unroll
         for (int ks = 0; ks < kMaxK; ++ks)
-          if (sact[ks] && smu[ks] < worst) { worst = smu[ks]; who = pol_code(kPolSess, i, ks); }
+          if (sact[ks] && smu[ks] < worst) { worst = smu[ks]; who = Code::make(kPolSess, i, ks); }
       }
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm;
-        if (((RACT[r] >> t) & 1u) && NU[k] < worst) { worst = NU[k]; who = pol_code(kPolRow, r, t); }
-      }
+      pol_step10_rows<PolTightMask, Code>(RACT, NU, nrow, Tm, worst, who, tid);
       pol_block_argmin(worst, who, RED);
       if (who >= 0) {
-        const int kind = who >> 24, p0 = (who >> 8) & 0xffff, p1 = who & 0xff;
+        const int kind = Code::kind(who), p0 = Code::p0(who), p1 = Code::p1(who);
         if (kind == kPolLb || kind == kPolUb) {
           if (p0 == i && p1 >= h * TQ && p1 < h * TQ + TQ) {
             const int k = p1 - h * TQ;
@@ -821,10 +479,10 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
             for (int ks = 0; ks < kMaxK; ++ks) if (ks == p1) sact[ks] = false;
           }
         } else if (tid == 0) {
-          RACT[p0] &= ~(1u << p1);
+          RACT.clear(p0, p1, Tm);
           NU[p0 * Tm + p1] = 0.0;
         }
-        stall = 0; best_step = 1e300;
+        stall.reset();
         __syncthreads();
         continue;
       }
@@ -845,20 +503,9 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         if (iv && k < TQ && t < Tm) Xs[i * Tm + t] = xv[k];
       }
       __syncthreads();
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) {
-        const int j = k / Tm, t = k - j * Tm;
-        double s = 0;
-        for (int e = 0; e < N; ++e) s += Gs[j * N + e] * Xs[e * Tm + t];
-        U[k] = s;
-      }
+      pol_g_times<int>(Gs, Xs, U, N, Tm, Mg, tid);
       __syncthreads();
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-        const double lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-        if (!(lim < 1e299)) continue;
-        const double val = row_is_disc(r) ? hypot(U[j * Tm + t], U[(j + M) * Tm + t]) : U[j * Tm + t];
-        pvl = fmax(pvl, (val - lim) / fmax(1.0, lim));
-      }
+      pol_kkt_rows(S, U, pvl, tid);
       statl = 0;
 #pragma unroll
       for (int k = 0; k < kPolTQ; ++k) {
@@ -870,8 +517,8 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
         for (int r = 0; r < nrow; ++r) {
           const double nu = NU[r * Tm + t];
           if (nu == 0.0) continue;
-          const int j = row_j(r);
-          if (row_is_disc(r)) {
+          const int j = S.row_j(r);
+          if (S.is_disc(r)) {
             const double u0 = U[j * Tm + t], u1 = U[(j + M) * Tm + t], val = hypot(u0, u1);
             gr += nu * (u0 * Gs[j * N + i] + u1 * Gs[(j + M) * N + i]) / val;
           } else {
@@ -888,14 +535,10 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
       break;
     }
     // ---- results -----------------------------------------------------------------------------------------------------------------------------------
-    POL_TICK(7);
-    if (tid == 0) {
-      for (int ph = 0; ph < 8; ++ph) atomicAdd(A.stats + 8 + ph, (int)tacc[ph]);
-      atomicAdd(A.stats + 6, rounds);
-    }
-#undef POL_TICK
+    clk.lap(7);
+    if (tid == 0) clk.flush(A.stats, rounds);
+    double ol = 0;
     if (success) {
-      double ol = 0;
 #pragma unroll
       for (int k = 0; k < kPolTQ; ++k) {
         const int t = h * TQ + k;
@@ -904,37 +547,8 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void polish_kerne
           ol += (0.5 * pd_user * xv[k] + qv[k]) * xv[k];
         }
       }
-      const double o = pol_block_sum(ol, RED);
-      // site-row multipliers in the caller's units (a disc's pair: nu times its outward normal, at the final x: U is current)
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) A.y[(size_t)b * Mg * Tm + k] = 0.0;
-      __syncthreads();
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-        const double nu = NU[k];
-        if (nu == 0.0) continue;
-        if (row_is_disc(r)) {
-          const double u0 = U[j * Tm + t], u1 = U[(j + M) * Tm + t], val = hypot(u0, u1);
-          if (val > 0) {
-            A.y[((size_t)b * Mg + j) * Tm + t] = nu * u0 / val;
-            A.y[((size_t)b * Mg + j + M) * Tm + t] = nu * u1 / val;
-          }
-        } else {
-          A.y[((size_t)b * Mg + j) * Tm + t] = nu;
-        }
-      }
-      if (tid == 0) {
-        A.status[b] = 1;
-        A.iters[b] += rounds;
-        A.pri[b] = fmax(prim_out, 0.0);
-        A.dua[b] = stat_out;
-        A.obj[b] = o;
-        atomicAdd(A.stats + 1, 1);
-      }
-    } else if (tid == 0) {
-      A.iters[b] += rounds;
-      atomicAdd(A.stats + why, 1);
     }
-    __syncthreads();
+    pol_results(A, S, NU, U, success, ol, rounds, why, prim_out, stat_out, RED, tid);
   }
 }
 

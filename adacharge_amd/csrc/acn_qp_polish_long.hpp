@@ -1,7 +1,8 @@
-// Device-side polish for horizons 33 ... 288 on sites of up to 64 EVSEs: the method of acn_qp_polish.hpp (oracle/polish_ref.py
-// is the executable specification of both, line by line: same working-set rules and tolerances -- the kPol* constants of
-// that header --, same per-period L D L' blocks plus Woodbury over the tight sessions, same regularisation, ratio test with
-// deterministic ties, release rule, stall rule, 96 rounds and final KKT check) with the storage such horizons need.
+// Device-side polish for horizons 33 ... 288 on sites of up to 64 EVSEs: the method of oracle/polish_ref.py (the executable
+// specification) with the storage such horizons need.  Every step on the tables -- the rules, tolerances and arithmetic the
+// short kernel uses too -- is a call into acn_qp_polish_steps.hpp, with the tight rows as PolTightBytes and the
+// blocking-constraint codes as PolCode12; what is written out below is what a thread does on its own strip, and the
+// staging of steps 6a ... 6e.
 //
 // polish_kernel<4 | 8> keeps a thread's periods in registers and a period's flags in 32-bit masks, and everything else in
 // LDS.  Here nothing is sized by the horizon in registers and no mask holds periods: thread (i = tid / 4, h = tid % 4) still
@@ -17,9 +18,9 @@
 //   - the capacitance matrix is accumulated from the columns that TOUCH a period (at most one per EVSE: the windows of an
 //     EVSE's sessions are disjoint), listed per period in EVSE order, not from all pairs of columns;
 //   - a block is factored and its first solve is done while it sits in the wave's LDS (same arithmetic, one pass);
-//   - pol_code_long gives a period 12 bits (ties still go to the smaller code, ordered like (kind, p0, p1)).
+//   - a code gives a period 12 bits (ties still go to the smaller code, ordered like (kind, p0, p1)).
 #pragma once
-#include "acn_qp_polish.hpp"
+#include "acn_qp_polish_steps.hpp"
 #include "acn_qp_polslab.hpp"
 
 namespace acnqp {
@@ -49,7 +50,9 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
   int* RT = RR + MR;                                   // its period
   unsigned char* ST = reinterpret_cast<unsigned char*>(sl + L.btab);   // per (i, t): 1 at lb, 2 at ub, 4 lb == ub
   signed char* CS = reinterpret_cast<signed char*>(ST + (size_t)N * Tm);   // per (i, t): -2 not free, -1 free, k >= 0 free in tight session k
-  unsigned char* RACT = reinterpret_cast<unsigned char*>(CS + (size_t)N * Tm);   // per (site row, t): tight
+  const PolTightBytes RACT{reinterpret_cast<unsigned char*>(CS + (size_t)N * Tm)};   // per (site row, t): tight
+  const PolRows R{RJ, RR, RT, RC0, RC1, RCA, RDG, LAM};
+  typedef PolCode12 Code;
   // ---- LDS ----------------------------------------------------------------------------------------------------------------
   double *Gs = sm + L.gs, *ZB = sm + L.zb, *ZV = sm + L.zv, *SISQ = sm + L.sisq, *DI = sm + L.di, *RED = sm + L.red;
   double* CAP = L.cap_in_lds ? sm + L.lcap : sl + L.cap;   // C = I - V' B^-1 V, packed lower
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
   int* COLOF = S1 + MS;                                // column of (EVSE, slot)
   int* ACT = COLOF + 4 * N;                            // the columns that touch the period in work, in EVSE order; their EVSEs
   int* ACTI = ACT + kPolLongActive;
-  int* MISC = ACTI + kPolLongActive;                   // [0] m, [2] session columns, [3] bad pivot, [4] columns of the period in work
+  int* MISC = ACTI + kPolLongActive;                   // [2] session columns, [3] bad pivot, [4] columns of the period in work
   __shared__ int q_slot;
 
   const int tid = threadIdx.x;
@@ -75,17 +78,15 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
   double* WB = sm + L.wblk + wave_ * L.blk_one;        // the wave's block in work, its right-hand side, 1 / D
   double* WV = sm + L.wvec + wave_ * 2 * L.mt_max;
   double* WD = WV + L.mt_max;
-  auto row_j = [&](int r) { return r < M ? r : Mg - 1; };
-  auto row_is_disc = [&](int r) { return soc && r < M; };
 
   for (int q_round = 0;; ++q_round) {
-    const int nlist = *A.count;
-    const int pos = queue_next(A.queue, nlist < A.B ? nlist : A.B, q_round, &q_slot);
+    const int pos = pol_next_listed(A, q_round, &q_slot);
     if (pos < 0) break;
     const int b = A.list[pos];
     if (b < 0 || b >= A.B) continue;              // (never expected)
     if (A.status[b] != kStatusPolish) continue;   // (block-uniform)
     if (tid == 0) atomicAdd(A.stats + 0, 1);
+    const PolSite S{N, Tm, M, Mg, nrow, b, soc, A.limits, A.peak};
     const bool eq = A.s_eq[b] != 0;
     const double pd_user = A.pdiag[b];
 
@@ -128,24 +129,14 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
     }
     // ---- site data; first guess of the tight site rows from the ADMM's multipliers ----------------------------------
     for (int k = tid; k < Mg * N; k += kPolThreads) Gs[k] = A.G[k];
-    for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-      const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-      const double y0 = A.y[((size_t)b * Mg + j) * Tm + t];
-      const double mag = row_is_disc(r) ? hypot(y0, A.y[((size_t)b * Mg + j + M) * Tm + t]) : y0;
-      const double lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-      const bool on = mag > kPolTolRow * qn && lim < 1e299;
-      NU[k] = on ? mag : 0.0;
-      RACT[k] = on ? 1 : 0;
-    }
+    pol_first_guess(S, RACT, A.y, NU, qn, tid);
     __syncthreads();
 
     int why = 4, rounds = 0;   // reason of a failure (index into stats), rounds made
-    int stall = 0;             // full steps in a row without progress (noise floor)
-    double best_step = 1e300;
-    // coarse phase clock (thread 0, 100 MHz ticks summed into stats[8 + phase]): where a polish spends its time
-    unsigned long long tick = wall_clock64();
-    unsigned tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define POL_TICK(ph) do { const unsigned long long _n = wall_clock64(); tacc[ph] += (unsigned)(_n - tick); tick = _n; } while (0)
+    PolStall stall;
+    stall.reset();
+    PolClock clk;
+    clk.start();
     bool success = false;
     double stat_out = 0, prim_out = 0;
     for (int rnd = 0; rnd < kPolMaxRounds; ++rnd) {
@@ -172,87 +163,15 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
       }
       __syncthreads();
       // ---- (2) G x ------------------------------------------------------------------------------------------------------
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) {
-        const int j = k / Tm, t = k - j * Tm;
-        double s = 0;
-        for (int e = 0; e < N; ++e) s += Gs[j * N + e] * X[(size_t)e * Tm + t];
-        U[k] = s;
-      }
+      pol_g_times<size_t>(Gs, X, U, N, Tm, Mg, tid);
       __syncthreads();
       // ---- (3) rows of the Schur system, period-major: pair k = t nrow + r of (period, site row) -> 0 / 1 / 2 rows (a tight
       // disc: its normal row and, with a multiplier worth it, its tangent row); offsets by a block-wide exclusive scan
-      {
-        int base = 0;
-        for (int k0 = 0; k0 < nrow * Tm; k0 += kPolThreads) {
-          const int k = k0 + tid;
-          const bool in = k < nrow * Tm;
-          const int t = in ? k / nrow : 0, r = in ? k - t * nrow : 0, j = row_j(r);
-          int need = 0;
-          double lim = 0, u0 = 0, u1 = 0, val = 0, nu = 0;
-          if (in && RACT[r * Tm + t]) {
-            lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-            if (row_is_disc(r)) {
-              u0 = U[j * Tm + t]; u1 = U[(j + M) * Tm + t];
-              val = hypot(u0, u1);
-              nu = NU[r * Tm + t];
-              need = val > 1e-12 ? (nu > kPolTangentMin * qn ? 2 : 1) : 0;
-            } else {
-              need = 1;
-            }
-          }
-          int incl = need;
-          for (int o = 1; o < 64; o <<= 1) { const int nb = __shfl_up(incl, o); incl += (tid & 63) >= o ? nb : 0; }
-          int* WT = reinterpret_cast<int*>(RED);
-          __syncthreads();
-          if ((tid & 63) == 63) WT[tid >> 6] = incl;
-          __syncthreads();
-          int before = base;
-          for (int w = 0; w < (tid >> 6); ++w) before += WT[w];
-          const int total = WT[0] + WT[1] + WT[2] + WT[3];
-          const int m0 = before + incl - need;
-          if (in && r == 0) TSTART[t] = m0;
-          if (need >= 1 && m0 + need <= MR) {   // (the tables hold every pair's rows: the bound is never the reason)
-            if (row_is_disc(r)) {
-              const double n0 = u0 / val, n1 = u1 / val;
-              RJ[m0] = j; RR[m0] = r; RT[m0] = t; RC0[m0] = n0; RC1[m0] = n1; RCA[m0] = lim - val; RDG[m0] = 0.0;
-              if (need == 2) {
-                RJ[m0 + 1] = j; RR[m0 + 1] = -1 - r; RT[m0 + 1] = t; RC0[m0 + 1] = -n1; RC1[m0 + 1] = n0; RCA[m0 + 1] = 0.0;
-                RDG[m0 + 1] = pd * val / nu;
-              }
-            } else {
-              RJ[m0] = j; RR[m0] = r; RT[m0] = t; RC0[m0] = 1.0; RC1[m0] = 0.0; RCA[m0] = lim - U[j * Tm + t]; RDG[m0] = 0.0;
-            }
-          }
-          base += total;
-        }
-        if (tid == 0) { TSTART[Tm] = base; MISC[0] = base; }
-        // session columns of V: the tight sessions with free variables, in (EVSE, slot) order (same scan)
-        int cnt = 0;
-        if (h == 0 && iv) {
-#pragma unroll
-          for (int ks = 0; ks < kMaxK; ++ks) cnt += son[ks] ? 1 : 0;
-        }
-        int incl = cnt;
-        for (int o = 1; o < 64; o <<= 1) { const int nb = __shfl_up(incl, o); incl += (tid & 63) >= o ? nb : 0; }
-        int* WT = reinterpret_cast<int*>(RED);
-        __syncthreads();
-        if ((tid & 63) == 63) WT[tid >> 6] = incl;
-        __syncthreads();
-        int cpos = incl - cnt;
-        for (int w = 0; w < (tid >> 6); ++w) cpos += WT[w];
-        if (tid == 0) MISC[2] = WT[0] + WT[1] + WT[2] + WT[3];
-        if (h == 0 && iv) {
-#pragma unroll
-          for (int ks = 0; ks < kMaxK; ++ks)
-            if (son[ks]) {
-              if (cpos < MS) {
-                SI[cpos] = i; SKS[cpos] = ks; S0[cpos] = soff[ks]; S1[cpos] = send[ks]; SISQ[cpos] = 1.0 / sqrt(nfree[ks]);
-                COLOF[i * 4 + ks] = cpos;
-              }
-              ++cpos;
-            }
-        }
-      }
+      pol_step3_rows(S, RACT, R, U, NU, TSTART, MR, qn, pd, RED, tid);
+      pol_step3_columns(son, nfree, h == 0 && iv, i, MS, SI, SKS, SISQ, MISC + 2, RED, [&](int c, int ks) {
+        S0[c] = soff[ks]; S1[c] = send[ks];   // the column's window, and the column of (EVSE, slot)
+        COLOF[i * 4 + ks] = c;
+      });
       // ---- (4) gradient on the free variables, v_free = -P g + pd e ---------------------------------------------------------
       double Eg[kMaxK];
 #pragma unroll
@@ -279,68 +198,16 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         D[vi + t] = -pg + pd * e;
       }
       __syncthreads();
-      const int m = MISC[0], nsa = MISC[2];
+      const int m = TSTART[Tm], nsa = MISC[2];
       if (m > MR || nsa > MS) { why = 2; break; }   // (block-uniform; never expected: the tables hold the worst case)
-      if (tid == 0) {   // packed blocks of B, one per period, one after the other
-        int o = 0;
-        for (int t = 0; t < Tm; ++t) { BOFF[t] = o; const int mt = TSTART[t + 1] - TSTART[t]; o += mt * (mt + 1) / 2; }
-        BOFF[Tm] = o;
-        MISC[3] = 0;
-      }
+      if (tid == 0) { pol_block_offsets(TSTART, BOFF, Tm); MISC[3] = 0; }
       __syncthreads();
       const int E = BOFF[Tm];
       if (E > A.blk_doubles) { why = 2; break; }    // (as above)
-      POL_TICK(0);
-      // R_a at EVSE e (a row lives on its own period's variables)
-      auto row_at = [&](int a_, int e_) __attribute__((always_inline)) -> double {
-        const int ja = RJ[a_];
-        const double c1 = RC1[a_];
-        return RC0[a_] * Gs[ja * N + e_] + (c1 != 0.0 ? c1 * Gs[(ja + M) * N + e_] : 0.0);
-      };
+      clk.lap(0);
       // ---- (5) rhs = R v_free - pd c_A;  B = R R' + diag + reg I, BLOCK DIAGONAL by period;  C = I ---------------------------
-      double dloc = 0;
-      for (int a = tid; a < m; a += kPolThreads) {
-        const int ta = RT[a];
-        const double* g0 = Gs + RJ[a] * N;
-        const double* g1 = g0 + M * N;
-        const double c0 = RC0[a], c1 = RC1[a];
-        const bool two = c1 != 0.0;
-        double sacc = 0, d2 = 0;
-        for (int e = 0; e < N; ++e) {
-          const double ra = c0 * g0[e] + (two ? c1 * g1[e] : 0.0);
-          sacc += ra * D[(size_t)e * Tm + ta];
-          d2 += CS[(size_t)e * Tm + ta] != -2 ? ra * ra : 0.0;
-        }
-        LAM[a] = sacc - pd * RCA[a];
-        dloc = fmax(dloc, d2);
-      }
-      const double reg = fmax(kPolRegRel * pd, kPolRegDiag * pol_block_max(dloc, RED));
-      {
-        int t = 0;
-        for (int p = tid; p < E; p += kPolThreads) {
-          while (BOFF[t + 1] <= p) ++t;
-          const int q_ = p - BOFF[t];
-          int ar = (int)((sqrt(8.0 * (double)q_ + 1.0) - 1.0) * 0.5);
-          while ((ar + 1) * (ar + 2) / 2 <= q_) ++ar;
-          while (ar * (ar + 1) / 2 > q_) --ar;
-          const int cr = q_ - ar * (ar + 1) / 2;
-          const int a = TSTART[t] + ar, c = TSTART[t] + cr;
-          const double *ga0 = Gs + RJ[a] * N, *ga1 = ga0 + M * N, *gc0 = Gs + RJ[c] * N, *gc1 = gc0 + M * N;
-          const double a0c = RC0[a], a1c = RC1[a], c0c = RC0[c], c1c = RC1[c];
-          const bool atwo = a1c != 0.0, ctwo = c1c != 0.0;
-          double sacc = 0;
-          for (int e = 0; e < N; ++e) {
-            const double ra = a0c * ga0[e] + (atwo ? a1c * ga1[e] : 0.0);
-            const double rc = c0c * gc0[e] + (ctwo ? c1c * gc1[e] : 0.0);
-            sacc += CS[(size_t)e * Tm + t] != -2 ? ra * rc : 0.0;
-          }
-          BLK[p] = sacc + (a == c ? RDG[a] + reg : 0.0);
-        }
-      }
-      for (int p = tid; p < nsa * (nsa + 1) / 2; p += kPolThreads) CAP[p] = 0.0;
-      __syncthreads();
-      for (int c = tid; c < nsa; c += kPolThreads) CAP[c * (c + 1) / 2 + c] = 1.0;
-      POL_TICK(1);
+      pol_step5<size_t>(R, Gs, D, CS, TSTART, BOFF, BLK, CAP, N, Tm, M, m, E, nsa, pd, RED, tid);
+      clk.lap(1);
       // ---- (6a, 6b) L D L' of every block and y = B^-1 rhs, a wave per block, the block in the wave's LDS (unit lower L stored
       // unscaled, 1 / D in RDG) ---------------------------------------------------------------------------------------------------
       for (int t = wave_; t < Tm; t += 4) {
@@ -350,18 +217,7 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         for (int p = lane_; p < mt * (mt + 1) / 2; p += 64) WB[p] = gblk[p];
         for (int k = lane_; k < mt; k += 64) WV[k] = LAM[a0 + k];
         pol_wave_sync();
-        bool bad = false;
-        for (int k = 0; k < mt && !bad; ++k) {
-          const double piv = WB[k * (k + 1) / 2 + k];
-          if (!(piv > 0.0)) { bad = true; break; }   // (wave-uniform)
-          const double pinv = 1.0 / piv;
-          for (int rr = k + 1 + (lane_ >> 3); rr < mt; rr += 8) {
-            const double lr = WB[rr * (rr + 1) / 2 + k] * pinv;
-            for (int c = k + 1 + (lane_ & 7); c <= rr; c += 8) WB[rr * (rr + 1) / 2 + c] -= lr * WB[c * (c + 1) / 2 + k];
-          }
-          pol_wave_sync();
-        }
-        if (bad) { if (lane_ == 0) MISC[3] = 1; pol_wave_sync(); continue; }
+        if (!pol_block_factor(WB, mt, lane_)) { if (lane_ == 0) MISC[3] = 1; pol_wave_sync(); continue; }
         for (int k = lane_; k < mt; k += 64) WD[k] = 1.0 / WB[k * (k + 1) / 2 + k];
         pol_wave_sync();
         pol_block_solve(WB, WD, WV, mt, lane_);
@@ -378,7 +234,7 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         double z = 0;
         for (int t = S0[c]; t < S1[c]; ++t)
           if (CS[(size_t)ic * Tm + t] == ks)
-            for (int a = TSTART[t]; a < TSTART[t + 1]; ++a) z += row_at(a, ic) * LAM[a];
+            for (int a = TSTART[t]; a < TSTART[t + 1]; ++a) z += R.at(Gs, N, M, a, ic) * LAM[a];
         ZV[c] = z * SISQ[c];
       }
       if (nsa > 0) {   // (block-uniform)
@@ -405,7 +261,7 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
           if (na > 0) {   // (block-uniform)
             for (int idx = tid; idx < mt * na; idx += kPolThreads) {
               const int k = idx / na, p = idx - k * na;
-              ZB[k * kPolLongActive + p] = row_at(a0 + k, ACTI[p]) * SISQ[ACT[p]];
+              ZB[k * kPolLongActive + p] = R.at(Gs, N, M, a0 + k, ACTI[p]) * SISQ[ACT[p]];
             }
             __syncthreads();
             if (tid < na) {
@@ -416,9 +272,7 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
             }
             __syncthreads();
             for (int p = tid; p < na * (na + 1) / 2; p += kPolThreads) {
-              int pr = (int)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-              while ((pr + 1) * (pr + 2) / 2 <= p) ++pr;
-              while (pr * (pr + 1) / 2 > p) --pr;
+              const int pr = pol_tri_row(p);
               const int pc = p - pr * (pr + 1) / 2;
               double sacc = 0;
               for (int k = 0; k < mt; ++k) sacc += ZB[k * kPolLongActive + pr] * TD[k] * ZB[k * kPolLongActive + pc];
@@ -429,48 +283,16 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
           __syncthreads();
         }
       }
-      POL_TICK(2);
+      clk.lap(2);
       // ---- (6d) C = L D L' (packed, one barrier per column), C w = V' y ----------------------------------------------------------------
-      bool bad_pivot = false;
-      for (int k = 0; k < nsa; ++k) {
-        __syncthreads();
-        const double piv = CAP[k * (k + 1) / 2 + k];
-        if (!(piv > 0.0)) { bad_pivot = true; break; }   // (uniform: every thread reads the same entry)
-        const double pinv = 1.0 / piv;
-        for (int rr = k + 1 + (tid >> 4); rr < nsa; rr += 16) {
-          const double lr = CAP[rr * (rr + 1) / 2 + k] * pinv;
-          double* row = CAP + rr * (rr + 1) / 2;
-          for (int c = k + 1 + (tid & 15); c <= rr; c += 16) row[c] -= lr * CAP[c * (c + 1) / 2 + k];
-        }
-      }
-      if (bad_pivot) { why = 3; break; }
-      {
-        __syncthreads();
-        for (int k = tid; k < nsa; k += kPolThreads) DI[k] = 1.0 / CAP[k * (k + 1) / 2 + k];
-        __syncthreads();
-        double acc = tid < nsa ? ZV[tid] : 0.0;   // forward: L z = V' y (thread r owns z_r)
-        for (int k = 0; k < nsa; ++k) {
-          if (tid == k) ZV[k] = acc;
-          __syncthreads();
-          if (tid > k && tid < nsa) acc -= CAP[tid * (tid + 1) / 2 + k] * DI[k] * ZV[k];
-        }
-        __syncthreads();
-        acc = tid < nsa ? ZV[tid] * DI[tid] : 0.0;   // backward: L' w = D^-1 z
-        const double dme = tid < nsa ? DI[tid] : 0.0;
-        for (int k = nsa - 1; k >= 0; --k) {
-          if (tid == k) ZV[k] = acc;
-          __syncthreads();
-          if (tid < k) acc -= CAP[k * (k + 1) / 2 + tid] * dme * ZV[k];
-        }
-        __syncthreads();
-      }
+      if (!pol_step6d(CAP, ZV, DI, nsa, tid)) { why = 3; break; }
       // ---- (6e) lam = y + B^-1 (V w) ---------------------------------------------------------------------------------------------------
       for (int a = tid; a < m; a += kPolThreads) {
         const int ta = RT[a];
         double sacc = 0;
         for (int e = 0; e < N; ++e) {   // (EVSE order is column order)
           const int cs = CS[(size_t)e * Tm + ta];
-          if (cs >= 0) { const int c = COLOF[e * 4 + cs]; sacc += row_at(a, e) * SISQ[c] * ZV[c]; }
+          if (cs >= 0) { const int c = COLOF[e * 4 + cs]; sacc += R.at(Gs, N, M, a, e) * SISQ[c] * ZV[c]; }
         }
         RCA[a] = sacc;
       }
@@ -487,7 +309,7 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         pol_wave_sync();
       }
       __syncthreads();
-      POL_TICK(3);
+      clk.lap(3);
       // ---- (7) the step: (R' lam)(i, t), and of the NORMAL rows alone (the multipliers' part of the gradient) ------------------------------
       double Ev[kMaxK];
 #pragma unroll
@@ -523,14 +345,9 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         D[vi + t] = dv;
       }
       __syncthreads();
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) {
-        const int j = k / Tm, t = k - j * Tm;
-        double s = 0;
-        for (int e = 0; e < N; ++e) s += Gs[j * N + e] * D[(size_t)e * Tm + t];
-        DU[k] = s;
-      }
+      pol_g_times<size_t>(Gs, D, DU, N, Tm, Mg, tid);
       __syncthreads();
-      POL_TICK(4);
+      clk.lap(4);
       // ---- (8) ratio test against everything outside the working set ---------------------------------------------------------------
       double alpha = 1.0;
       int block = -1;
@@ -544,10 +361,10 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         if ((ST[vi + t] & 3) != 0) continue;
         if (d < -1e-14) {
           const double a_ = fmax((LB[vi + t] - X[vi + t]) / d, 0.0);
-          if (a_ < alpha) { alpha = a_; block = pol_code_long(kPolLb, i, t); }
+          if (a_ < alpha) { alpha = a_; block = Code::make(kPolLb, i, t); }
         } else if (d > 1e-14) {
           const double a_ = fmax((UB[vi + t] - X[vi + t]) / d, 0.0);
-          if (a_ < alpha) { alpha = a_; block = pol_code_long(kPolUb, i, t); }
+          if (a_ < alpha) { alpha = a_; block = Code::make(kPolUb, i, t); }
         }
       }
 #pragma unroll
@@ -555,35 +372,13 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         const double des = pol_quad_sum(de[ks]);
         if (h == 0 && shas[ks] && !sact[ks] && des > 1e-14) {
           const double a_ = fmax(cE[ks] / des, 0.0);
-          if (a_ < alpha) { alpha = a_; block = pol_code_long(kPolSess, i, ks); }
+          if (a_ < alpha) { alpha = a_; block = Code::make(kPolSess, i, ks); }
         }
       }
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-        if (RACT[k]) continue;
-        const double lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-        if (!(lim < 1e299)) continue;
-        if (row_is_disc(r)) {
-          const double u0 = U[j * Tm + t], u1 = U[(j + M) * Tm + t], d0 = DU[j * Tm + t], d1 = DU[(j + M) * Tm + t];
-          const double aa = d0 * d0 + d1 * d1, bb = 2.0 * (u0 * d0 + u1 * d1), cc = u0 * u0 + u1 * u1 - lim * lim;
-          if (aa > 1e-28 && (bb > 0 || cc > 0)) {
-            const double dsc = bb * bb - 4.0 * aa * cc;
-            if (dsc >= 0) {
-              const double a_ = fmax((-bb + sqrt(dsc)) / (2.0 * aa), 0.0);
-              if (a_ < alpha) { alpha = a_; block = pol_code_long(kPolRow, r, t); }
-            }
-          }
-        } else {
-          const double du = DU[j * Tm + t];
-          if (du > 1e-14) {
-            const double a_ = fmax((lim - U[j * Tm + t]) / du, 0.0);
-            if (a_ < alpha) { alpha = a_; block = pol_code_long(kPolRow, r, t); }
-          }
-        }
-      }
+      pol_step8_rows<PolTightBytes, Code>(S, RACT, U, DU, alpha, block, tid);
       pol_block_argmin(alpha, block, RED);
       if (block < 0) alpha = 1.0;
-      POL_TICK(5);
+      clk.lap(5);
       // ---- (9) move; the new multipliers; the blocking constraint joins the working set ------------------------------------------------
       double xm = 0;
       for (int t = t0; t < t1; ++t) {
@@ -593,12 +388,9 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
       }
       const double step = pol_block_max(stepl, RED);
       const double xmax = pol_block_max(xm, RED);
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) NU[k] = 0.0;
-      __syncthreads();
-      for (int a = tid; a < m; a += kPolThreads)
-        if (RR[a] >= 0) NU[RR[a] * Tm + RT[a]] = LAM[a];
+      pol_step9_multipliers(R, NU, m, nrow, Tm, tid);
       if (block >= 0) {
-        const int kind = pol_code_long_kind(block), p0 = pol_code_long_p0(block), p1 = pol_code_long_p1(block);
+        const int kind = Code::kind(block), p0 = Code::p0(block), p1 = Code::p1(block);
         if (kind == kPolLb || kind == kPolUb) {
           if (iv && p0 == i && p1 >= t0 && p1 < t1) {
             if (kind == kPolLb) { ST[vi + p1] |= 1; X[vi + p1] = LB[vi + p1]; } else { ST[vi + p1] |= 2; X[vi + p1] = UB[vi + p1]; }
@@ -609,21 +401,13 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
             for (int ks = 0; ks < kMaxK; ++ks) if (ks == p1) sact[ks] = true;
           }
         } else if (tid == 0) {
-          RACT[p0 * Tm + p1] = 1;
+          RACT.set(p0, p1, Tm);
         }
       }
       __syncthreads();
-      // noise floor (oracle/polish_ref.py): full steps that have stopped shrinking go to the multiplier test and the KKT check
-      // like a converged one; the check decides, and a failure there ends the polish instead of burning the round limit
-      if (block < 0) {
-        stall = step >= 0.5 * best_step ? stall + 1 : 0;
-        best_step = fmin(best_step, step);
-      } else {
-        stall = 0; best_step = 1e300;
-      }
-      const bool floor_hit = block < 0 && stall >= kPolStallRounds && step <= 1e-3;
-      const bool conv = block < 0 && (step <= kPolTolStep * fmax(1.0, xmax) || floor_hit);
-      POL_TICK(6);
+      stall.update(block, step);
+      const bool conv = stall.converged(block, step, xmax);
+      clk.lap(6);
       if (!conv) continue;
       // ---- (10) multipliers of the whole working set: the most negative one leaves; none: verify and finish ---------------------------------
       double worst = -kPolTolDual * qn;
@@ -634,21 +418,18 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         double gr = pd * X[vi + t] + Q[vi + t] + RN[vi + t];
 #pragma unroll
         for (int ks = 0; ks < kMaxK; ++ks) gr += (t >= soff[ks] && t < send[ks]) ? smu[ks] : 0.0;
-        if ((st & 1) && gr < worst) { worst = gr; who = pol_code_long(kPolLb, i, t); }
-        if ((st & 2) && -gr < worst) { worst = -gr; who = pol_code_long(kPolUb, i, t); }
+        if ((st & 1) && gr < worst) { worst = gr; who = Code::make(kPolLb, i, t); }
+        if ((st & 2) && -gr < worst) { worst = -gr; who = Code::make(kPolUb, i, t); }
       }
       if (!eq && h == 0) {
 #pragma unroll
         for (int ks = 0; ks < kMaxK; ++ks)
-          if (sact[ks] && smu[ks] < worst) { worst = smu[ks]; who = pol_code_long(kPolSess, i, ks); }
+          if (sact[ks] && smu[ks] < worst) { worst = smu[ks]; who = Code::make(kPolSess, i, ks); }
       }
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm;
-        if (RACT[k] && NU[k] < worst) { worst = NU[k]; who = pol_code_long(kPolRow, r, t); }
-      }
+      pol_step10_rows<PolTightBytes, Code>(RACT, NU, nrow, Tm, worst, who, tid);
       pol_block_argmin(worst, who, RED);
       if (who >= 0) {
-        const int kind = pol_code_long_kind(who), p0 = pol_code_long_p0(who), p1 = pol_code_long_p1(who);
+        const int kind = Code::kind(who), p0 = Code::p0(who), p1 = Code::p1(who);
         if (kind == kPolLb || kind == kPolUb) {
           if (iv && p0 == i && p1 >= t0 && p1 < t1) ST[vi + p1] &= (unsigned char)(kind == kPolLb ? ~1 : ~2);
         } else if (kind == kPolSess) {
@@ -657,10 +438,10 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
             for (int ks = 0; ks < kMaxK; ++ks) if (ks == p1) sact[ks] = false;
           }
         } else if (tid == 0) {
-          RACT[p0 * Tm + p1] = 0;
+          RACT.clear(p0, p1, Tm);
           NU[p0 * Tm + p1] = 0.0;
         }
-        stall = 0; best_step = 1e300;
+        stall.reset();
         __syncthreads();
         continue;
       }
@@ -675,20 +456,9 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         if (shas[ks]) pvl = fmax(pvl, (eq ? fabs(d) : d) / fmax(1.0, fabs(scap[ks])));
       }
       __syncthreads();
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) {
-        const int j = k / Tm, t = k - j * Tm;
-        double s = 0;
-        for (int e = 0; e < N; ++e) s += Gs[j * N + e] * X[(size_t)e * Tm + t];
-        U[k] = s;
-      }
+      pol_g_times<size_t>(Gs, X, U, N, Tm, Mg, tid);
       __syncthreads();
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-        const double lim = r < M ? A.limits[r] : A.peak[(size_t)b * Tm + t];
-        if (!(lim < 1e299)) continue;
-        const double val = row_is_disc(r) ? hypot(U[j * Tm + t], U[(j + M) * Tm + t]) : U[j * Tm + t];
-        pvl = fmax(pvl, (val - lim) / fmax(1.0, lim));
-      }
+      pol_kkt_rows(S, U, pvl, tid);
       double statl = 0;
       for (int t = t0; t < t1; ++t) {
         if ((ST[vi + t] & 3) != 0) continue;
@@ -698,8 +468,8 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
         for (int r = 0; r < nrow; ++r) {
           const double nu = NU[r * Tm + t];
           if (nu == 0.0) continue;
-          const int j = row_j(r);
-          if (row_is_disc(r)) {
+          const int j = S.row_j(r);
+          if (S.is_disc(r)) {
             const double u0 = U[j * Tm + t], u1 = U[(j + M) * Tm + t], val = hypot(u0, u1);
             gr += nu * (u0 * Gs[j * N + i] + u1 * Gs[(j + M) * N + i]) / val;
           } else {
@@ -716,50 +486,17 @@ __global__ __launch_bounds__(kPolThreads, 1) void polish_long_kernel(const Polis
       break;
     }
     // ---- results -----------------------------------------------------------------------------------------------------------------------------------
-    POL_TICK(7);
-    if (tid == 0) {
-      for (int ph = 0; ph < 8; ++ph) atomicAdd(A.stats + 8 + ph, (int)tacc[ph]);
-      atomicAdd(A.stats + 6, rounds);
-    }
-#undef POL_TICK
+    clk.lap(7);
+    if (tid == 0) clk.flush(A.stats, rounds);
+    double ol = 0;
     if (success) {
-      double ol = 0;
       for (int t = t0; t < t1; ++t) {
         const double xx = X[vi + t];
         A.x[((size_t)b * N + i) * Tm + t] = xx;
         ol += (0.5 * pd_user * xx + Q[vi + t]) * xx;
       }
-      const double o = pol_block_sum(ol, RED);
-      // site-row multipliers in the caller's units (a disc's pair: nu times its outward normal, at the final x: U is current)
-      for (int k = tid; k < Mg * Tm; k += kPolThreads) A.y[(size_t)b * Mg * Tm + k] = 0.0;
-      __syncthreads();
-      for (int k = tid; k < nrow * Tm; k += kPolThreads) {
-        const int r = k / Tm, t = k - r * Tm, j = row_j(r);
-        const double nu = NU[k];
-        if (nu == 0.0) continue;
-        if (row_is_disc(r)) {
-          const double u0 = U[j * Tm + t], u1 = U[(j + M) * Tm + t], val = hypot(u0, u1);
-          if (val > 0) {
-            A.y[((size_t)b * Mg + j) * Tm + t] = nu * u0 / val;
-            A.y[((size_t)b * Mg + j + M) * Tm + t] = nu * u1 / val;
-          }
-        } else {
-          A.y[((size_t)b * Mg + j) * Tm + t] = nu;
-        }
-      }
-      if (tid == 0) {
-        A.status[b] = 1;
-        A.iters[b] += rounds;
-        A.pri[b] = fmax(prim_out, 0.0);
-        A.dua[b] = stat_out;
-        A.obj[b] = o;
-        atomicAdd(A.stats + 1, 1);
-      }
-    } else if (tid == 0) {
-      A.iters[b] += rounds;
-      atomicAdd(A.stats + why, 1);
     }
-    __syncthreads();
+    pol_results(A, S, NU, U, success, ol, rounds, why, prim_out, stat_out, RED, tid);
   }
 }
 

@@ -6,6 +6,11 @@ agree BIT FOR BIT between the two libraries.  The `warm` group feeds the one inp
 tests/warm_cases.py on every family they reach, from every kind of warm point after 60 plain iterations and from the
 perturbed point as shipped.  One child process per library and pool group (ACNQP_LIBRARY selects the
 library), one at a time, each under its own time limit; the first non-zero exit ends the run.
+The `polish` and `polish_long` groups hand work to the Newton polish on purpose: every case of tests/polish_cases.py at its
+pool's own shape (and at t_max = 17 where the pool's is <= 16: polish_kernel<4> becomes <8> there) and every case of
+tests/polish_long_cases.py at its shapes on a polish_long handle, with polish_iters = the case's hand-over point and no
+retry passes; besides the outputs, what each launch adds to the polish counters (attempted, solved, the four give-up
+reasons, rounds) must be equal.
 
     python tools/gpu_ab_library.py child <group> <out.npz>          one library (ACNQP_LIBRARY), one group of pools
     python tools/gpu_ab_library.py <other.so> [record.json]         both libraries, compared; the record holds the
@@ -16,7 +21,8 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 KEYS = ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")
-GROUPS = ("routes", "verdicts_a", "verdicts_b", "max_iter", "warm")
+GROUPS = ("routes", "verdicts_a", "verdicts_b", "max_iter", "warm", "polish", "polish_long")
+POLISH_COUNTERS = ("attempted", "solved", "gave_up_rows", "gave_up_pivot", "gave_up_rounds", "gave_up_kkt", "rounds")
 CHILD_TIMEOUT = 900   # seconds per child
 
 
@@ -55,6 +61,24 @@ def runs(group):
                     for kind, run in [(kind, "m60") for kind in WC.kinds_of(name, t)] + [("perturbed", "shipped")]:
                         yield f"warm/{name}/{fam}/{kind}/{run}", h, H.pad_batch(pool, t, k), default_options(**WC.RUNS[run]), WC.warm(name, kind, t)
             h.close()
+    elif group == "polish":
+        from tests import polish_cases as PC
+
+        for case, (name, P, *_) in PC.CASES.items():
+            pool = PC.pool(name)
+            h = SiteHandle(pool.site, 0)
+            for t in [pool.Tm] + ([17] if pool.Tm <= 16 else []):
+                yield f"polish/{case}/t{t}", h, H.pad_batch(pool, t, pool.K), default_options(polish_iters=P, retry_passes=0), None
+            h.close()
+    elif group == "polish_long":
+        from tests import polish_long_cases as LC
+
+        for case, (name, P, *_) in LC.CASES.items():
+            pool = LC.pool(name)
+            h = SiteHandle(pool.site, 0, polish_long=True)
+            for t, k in LC.shapes(case):
+                yield f"polish_long/{case}/t{t}k{k}", h, H.pad_batch(pool, t, k), default_options(polish_iters=P, retry_passes=0), None
+            h.close()
     else:
         for name in G.MAX_ITER_POOLS:
             pool = ProblemBatch.concatenate(G._filler(G.POOLS[name], np.random.default_rng(77), 24))
@@ -69,9 +93,13 @@ def child(group, path):
 
     res = {}
     for tag, h, padded, opts, warm in runs(group):
+        s0 = h.polish_stats() if group.startswith("polish") else None
         out = H.launch_poisoned(h, padded, opts, warm=warm)
         for k in KEYS:
             res[f"{tag}/{k}"] = out[k]
+        if s0 is not None:
+            s1 = h.polish_stats()
+            res[f"{tag}/polish_counters"] = np.array([s1[c] - s0[c] for c in POLISH_COUNTERS], np.int64)
     np.savez(path, **res)
 
 
