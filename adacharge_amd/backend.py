@@ -177,6 +177,7 @@ def _abi():
         ("acnqp_accel_columns", i32, [h, i32, i32, i32, i32]),
         ("acnqp_route", i32, [h, i32, i32, i32, P(i32)]),
         ("acnqp_set_long_polish", rc, [h, i32]),
+        ("acnqp_set_wide_polish", rc, [h, i32]),
     ]
     # acnqp_X_host takes these arguments, acnqp_X_device the same and the stream behind them
     for stem, args in (
@@ -599,13 +600,16 @@ def pinned_empty(shape, dtype=np.float64) -> np.ndarray:
 class SiteHandle:
     """One ``acnqp_handle``: a site uploaded to one GPU."""
 
-    def __init__(self, site: SiteData, device: int = 0, polish_long: bool = False):
+    def __init__(self, site: SiteData, device: int = 0, polish_long: bool = False, polish_wide: bool = False):
         """``polish_long``: the Newton polish also takes over at horizons 33 ... 288 (N <= 64; ``acnqp_set_long_polish``).
-        Off by default: launches then do exactly what they did before there was such a polish."""
+        ``polish_wide``: on sites of 65 ... 1,024 EVSEs (horizons <= 48) the Newton polish runs behind the solver launch on
+        what it ended MAX_ITER or SOLVED_INACCURATE (``acnqp_set_wide_polish``).
+        Both off by default: launches then do exactly what they did before there was such a polish."""
         self._lib = load_library()
         self.site = site
         self.device = int(device)
         self.polish_long = bool(polish_long)
+        self.polish_wide = bool(polish_wide)
         G = np.ascontiguousarray(site.G, dtype=np.float64)
         lim = np.ascontiguousarray(site.limits, dtype=np.float64)
         desc = _Site(
@@ -619,6 +623,8 @@ class SiteHandle:
         self._launches_seen = 0
         if self.polish_long:
             _check(self._lib.acnqp_set_long_polish(self._h, 1), "acnqp_set_long_polish")
+        if self.polish_wide:
+            _check(self._lib.acnqp_set_wide_polish(self._h, 1), "acnqp_set_wide_polish")
 
     def close(self):
         if getattr(self, "_h", None):

@@ -155,6 +155,7 @@ struct acnqp_handle {
                                   // [16]: problems taken by the launches alongside the solver (acnqp_debug_polish_alongside)
   hipStream_t aux = nullptr;      // the polish launches that run alongside a solver launch (launch_with_polish)
   bool long_polish = false;       // acnqp_set_long_polish: polish_long_shape routes run the long-horizon polish
+  bool wide_polish = false;       // acnqp_set_wide_polish: polish_wide_shape routes run the wide-site polish behind the solver launch
   // the post-solve host entries' device staging (acn_qp_post.hpp: the whole-call arrays and one chunk).  ONE buffer for
   // the three: each runs on slot[0].st, synchronises it before reserve() and returns synchronised
   DevBuf post_stage;
@@ -215,6 +216,14 @@ int polish_block_doubles(const acnqp_handle* h, const acnqp::Route& rt) {
   return blk < 2 * nrow_site * (2 * nrow_site + 1) / 2 ? -1 : blk;   // not even one full block
 }
 
+// The wide-site polish (acn_qp_polish_wide.hpp) runs for this route: the shape (Route::polish_wide_shape), the handle's
+// switch and the kernel's own tables agree.  (The options' half -- polish_iters > 0 -- is the launch's.)
+bool wide_polish_route(const acnqp_handle* h, const acnqp::Route& rt) {
+  static const bool no_polish = std::getenv("ACNQP_NO_POLISH") != nullptr;   // diagnostic
+  const acnqp::SiteShape& s = h->shape;
+  return !no_polish && h->wide_polish && rt.polish_wide_shape && acnqp::polish_wide_holds(s.N, rt.t_max, rt.k_sessions, s.Mg, s.M + s.has_peak);
+}
+
 // acnqp_solve_batch_device with the pipeline's knowledge of what comes after the launch (nothing_follows: launch_with_polish)
 // and of where the schedules go (x_host: TiledArgs::x_host, a device array; null: r->x only)
 int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows,
@@ -235,6 +244,7 @@ int32_t acnqp_route(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t 
   acnqp_options o;   // (the polish flag: what a launch with the DEFAULT options does)
   acnqp_default_options(&o);
   if (polish) *polish = (polish_block_doubles(h, r) >= 0 && o.polish_iters > 0 && o.polish_iters < o.max_iter) ? 1 : 0;
+  if (polish && wide_polish_route(h, r) && o.polish_iters > 0) *polish = 1;
   return r.family;
 }
 
@@ -683,6 +693,54 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   return ACNQP_OK;
 }
 
+// ---- the wide-site polish (acn_qp_polish_wide.hpp): 64 < N <= 1,024 behind the large-site kernel -------------------------
+// solver kernel (unchanged; it writes x and the site-row multipliers of its best pass together, into the caller's y or a
+// scratch buffer) -> list kernel (what ended MAX_ITER or SOLVED_INACCURATE: status saved, marked, listed) -> polish kernel
+// over the list -> restore kernel (the saved status back where the polish gave up).  Four launches on the caller's
+// stream, no host synchronisation, the last three nearly empty as a rule; cold or warm-started alike; by shape, options
+// and switch, never by batch size.  It runs BEHIND the last pass, not from polish_iters on: a wide site's working set
+// changes by one constraint per round, and only the ADMM's final iterate is within the 96 rounds.
+int launch_wide_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route& rt, const acnqp::TiledArgs& a, const Workspace& ws,
+                       const acnqp_problems* p, const acnqp_options* o, const acnqp_results* r, hipStream_t st, hipError_t* e) {
+  const acnqp::SiteShape& s = h->shape;
+  const acnqp::SiteDev* d = &h->site;
+  const int nrow_site = s.M + s.has_peak;
+  // [0] queue of the polish kernel, [2] list length; list[B]; saved status [B]; multipliers [B][Mg][Tm] unless the caller
+  // wants them anyway; then the slabs, one per workgroup
+  const int grid = acnqp::polish_wide_grid(p->batch);
+  const size_t sbytes = (size_t)acnqp::polish_wide_slab_bytes(s.N, p->t_max, p->k_sessions, s.Mg, nrow_site, grid);
+  const size_t lbytes = ((size_t)p->batch * sizeof(int32_t) + 255) & ~(size_t)255;
+  const size_t ybytes = r->y ? 0 : (((size_t)p->batch * s.Mg * p->t_max * sizeof(double) + 255) & ~(size_t)255);
+  HIP_TRY(reserve_behind(st, {{&wk->pol, 256 + 2 * lbytes + ybytes + sbytes}}));
+  char* base = static_cast<char*>(wk->pol.p);
+  int32_t* ctr = reinterpret_cast<int32_t*>(base);
+  int32_t* list = reinterpret_cast<int32_t*>(base + 256);
+  int32_t* saved = reinterpret_cast<int32_t*>(base + 256 + lbytes);
+  double* ybuf = r->y ? r->y : reinterpret_cast<double*>(base + 256 + 2 * lbytes);
+  double* slab = reinterpret_cast<double*>(base + 256 + 2 * lbytes + ybytes);
+  HIP_TRY(hipMemsetAsync(ctr, 0, 256, st));
+  acnqp::TiledArgs a1 = a;
+  a1.y_out = ybuf;
+  *e = launch_solver(h, rt, a1, ws, st);
+  if (*e == hipSuccess) *e = acnqp::launch_polish_wide_list(r->status, saved, list, ctr + 2, p->batch, st);
+  if (*e == hipSuccess) {
+    acnqp::PolishArgs pa;
+    pa.B = p->batch; pa.N = s.N; pa.Tm = p->t_max; pa.K = p->k_sessions; pa.M = s.M; pa.Mg = s.Mg; pa.cone = s.cone;
+    pa.has_peak = s.has_peak; pa.max_rows = acnqp::polish_long_rows(s.Mg, p->t_max);
+    pa.blk_doubles = acnqp::polish_wide_block_doubles(p->t_max, s.Mg);
+    pa.max_sess = acnqp::polish_long_sess(s.N, p->k_sessions);
+    pa.G = d->Gabi; pa.limits = d->limabi;
+    pa.horizon = p->horizon; pa.lb = p->lb; pa.ub = p->ub; pa.q = p->q; pa.pdiag = p->pdiag;
+    pa.s_off = p->s_off; pa.s_len = p->s_len; pa.s_cap = p->s_cap; pa.s_eq = p->s_eq; pa.peak = s.has_peak ? p->peak : nullptr;
+    pa.x = r->x; pa.y = ybuf; pa.status = r->status; pa.iters = r->iters; pa.pri = r->pri_res; pa.dua = r->dua_res; pa.obj = r->obj;
+    pa.list = list; pa.count = ctr + 2; pa.queue = ctr + 0; pa.stats = h->pol_stats; pa.reg_rel = o->reg_rel;
+    pa.alongside = 0; pa.expected = p->batch; pa.retired = nullptr; pa.max_polls = 0; pa.taken = nullptr;
+    *e = acnqp::launch_polish_wide(pa, slab, grid, st);
+  }
+  if (*e == hipSuccess) *e = acnqp::launch_polish_wide_restore(r->status, saved, list, ctr + 2, p->batch, st);
+  return ACNQP_OK;
+}
+
 int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows,
                        double* const* x_host) {
   int rc = check_problem_shapes(h, p, o, r);
@@ -709,6 +767,8 @@ int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_opt
   hipError_t e = hipSuccess;
   if (pol_blk >= 0) {
     if ((rc = launch_with_polish(h, wk, rt, a, ws, pol_blk, p, o, r, st, nothing_follows, &e)) != ACNQP_OK) return rc;
+  } else if (o->polish_iters > 0 && wide_polish_route(h, rt)) {   // (cold or warm-started: it starts from the launch's last iterate)
+    if ((rc = launch_wide_polish(h, wk, rt, a, ws, p, o, r, st, &e)) != ACNQP_OK) return rc;
   } else {
     e = launch_solver(h, rt, a, ws, st);
   }
@@ -745,6 +805,12 @@ static float event_pair_ms(acnqp_handle* h, long long launch) {
 int acnqp_set_long_polish(acnqp_handle* h, int32_t on) {
   if (!h) return fail(ACNQP_ERR_INVALID, "acnqp_set_long_polish: null handle");
   h->long_polish = on != 0;
+  return ACNQP_OK;
+}
+
+int acnqp_set_wide_polish(acnqp_handle* h, int32_t on) {
+  if (!h) return fail(ACNQP_ERR_INVALID, "acnqp_set_wide_polish: null handle");
+  h->wide_polish = on != 0;
   return ACNQP_OK;
 }
 

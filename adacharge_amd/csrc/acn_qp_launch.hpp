@@ -14,6 +14,7 @@
 #include "acn_qp_long.hpp"
 #include "acn_qp_polish.hpp"
 #include "acn_qp_polslab.hpp"
+#include "acn_qp_polwide.hpp"
 #include "acn_qp_route.hpp"
 
 namespace acnqp {
@@ -124,6 +125,16 @@ int polish_long_grid(int batch);                                              //
 long long polish_long_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid);   // bytes of the slabs of `grid` workgroups
 int polish_long_block_doubles(int Tm, int Mg);                                // doubles of the packed per-period blocks (PolishArgs.blk_doubles)
 hipError_t launch_polish_long(const PolishArgs& pa, double* slab, int grid, hipStream_t st);
+// wide-site polish kernel (acn_qp_polish_wide.hpp): 64 < N <= 1,024, horizons <= 48, behind the large-site kernel's launch;
+// the state in a slab of global memory per workgroup (acn_qp_polwide.hpp), tables for the worst case of the shape.  The list
+// kernel saves the status of every problem that ended MAX_ITER or SOLVED_INACCURATE in saved[B], marks it and lists it; the
+// restore kernel gives the saved status back to what the polish did not solve.
+int polish_wide_grid(int batch);                                              // workgroups (slabs) of a launch
+long long polish_wide_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid);   // bytes of the slabs of `grid` workgroups
+int polish_wide_block_doubles(int Tm, int Mg);                                // doubles of the packed per-period blocks (PolishArgs.blk_doubles)
+hipError_t launch_polish_wide_list(int32_t* status, int32_t* saved, int32_t* list, int32_t* count, int B, hipStream_t st);
+hipError_t launch_polish_wide(const PolishArgs& pa, double* slab, int grid, hipStream_t st);
+hipError_t launch_polish_wide_restore(int32_t* status, const int32_t* saved, const int32_t* list, const int32_t* count, int B, hipStream_t st);
 // general-shape kernel (acn_qp_general.hpp), `threads` in {256, 512, 1024}
 hipError_t launch_general(const GeneralArgs& ga, int threads, hipStream_t st);
 

@@ -102,6 +102,8 @@ struct Route {
   bool polish_shape = false;   // the shape's half of the polish decision (the LDS fit and the options: acn_qp_api.hip)
   bool polish_long_shape = false;   // the shape's half of the LONG-horizon polish decision (acn_qp_polish_long.hpp; the handle's
                                     // switch acnqp_set_long_polish and the options: acn_qp_api.hip).  Never true with polish_shape.
+  bool polish_wide_shape = false;   // the shape's half of the WIDE-site polish decision (acn_qp_polish_wide.hpp; the handle's switch
+                                    // acnqp_set_wide_polish and the options: acn_qp_api.hip).  Never true with the other two.
   SiteShape site;     // what it was decided for
   int t_max = 0, k_sessions = 0;
 
@@ -165,6 +167,11 @@ inline Route route_for(const SiteShape& s, int t_max, int k_sessions, int batch,
   // the long-horizon kernel's workspace variant (not the general kernel's three row tiles)
   r.polish_long_shape = s.N <= 64 && t_max > 32 && t_max <= 288 && k_sessions <= kRouteMaxK && !s.has_flat && !s.has_max &&
                         s.M + s.has_peak > 0 && (r.family == ACNQP_ROUTE_WAVE5 || r.family == ACNQP_ROUTE_LONG_WS);
+  // the wide-site polish (acn_qp_polish_wide.hpp): behind the large-site kernel's launch, sites of up to 1,024 EVSEs whose
+  // session slots make at most 1,024 columns (8 ceil(N K / 8): the capacitance matrix's tables) and whose site has at most
+  // 48 rows at the ABI
+  r.polish_wide_shape = r.family == ACNQP_ROUTE_STREAM && s.N > 64 && s.N <= 1024 && t_max <= 48 && k_sessions <= kRouteMaxK &&
+                        8 * ((s.N * k_sessions + 7) / 8) <= 1024 && s.Mg <= 48 && !s.has_flat && !s.has_max && s.M + s.has_peak > 0;
   return r;
 }
 

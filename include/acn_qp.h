@@ -376,6 +376,18 @@ int32_t acnqp_route(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t 
  * the options and this switch, never of the batch size.  Returns ACNQP_OK, ACNQP_ERR_INVALID for a null handle.      */
 int acnqp_set_long_polish(acnqp_handle* h, int32_t on);
 
+/* Additive to ABI v10 (a new symbol; no structure changes): the polish for sites of 65 ... 1,024 EVSEs at horizons <= 48
+ * (ACNQP_ROUTE_STREAM; at most four session slots and 8 ceil(N k_sessions / 8) <= 1,024 session columns, at most 48 rows
+ * of acnqp_site.G, no load-flattening or demand-charge row).  A property of the handle, OFF after acnqp_create: with it
+ * off every launch does what it did before there was such a polish.  on != 0: a launch of such a shape with
+ * options.polish_iters > 0, cold or warm-started, is followed on the same stream by the wide-site polish kernel over the
+ * problems the solver kernel ended ACNQP_MAX_ITER or ACNQP_SOLVED_INACCURATE, from the schedule and multipliers it wrote
+ * for them: a problem the polish solves ends ACNQP_SOLVED with iters = the solver's iterations plus the Newton rounds and
+ * the final check's residuals in pri_res / dua_res; one it gives up keeps every result the solver gave it.  acnqp_route
+ * reports polish = 1 for the shape.  Read on the host when a launch is planned; the decision is a function of the shape,
+ * the options and this switch, never of the batch size.  Returns ACNQP_OK, ACNQP_ERR_INVALID for a null handle.      */
+int acnqp_set_wide_polish(acnqp_handle* h, int32_t on);
+
 /* ---- dual report (additive to ABI v10: new symbols only, no existing structure changes) -------------------------------
  * For any answer (x, y) of the library: the multipliers of the energy rows and of the rate bounds, and the KKT
  * residuals of the full primal-dual point, computed on the GPU by one kernel that is independent of the solver loop.
