@@ -199,6 +199,7 @@ def _abi():
     introspection = [
         ("acnqp_debug_polish_alongside", i64, [h]),
         ("acnqp_debug_direct_x", i64, [h]),
+        ("acnqp_debug_direct_in", i64, [h]),
         ("acnqp_debug_wave_rank", rc, [h, P(i32)]),
         ("acnqp_debug_wave_evse_extent", rc, [h, P(i32)]),
         ("acnqp_debug_order_keys", rc, [h, P(_Problems), P(i32)]),
@@ -1221,6 +1222,11 @@ class SiteHandle:
         """Problems of this handle's last host-entry call whose schedule the kernel stored straight into the caller's pinned
         result array instead of a copy (acnqp_debug_direct_x: introspection, not part of the ABI)."""
         return int(self._lib.acnqp_debug_direct_x(self._h))
+
+    def direct_in(self) -> int:
+        """Problems of this handle's last host-entry call whose lb, ub and q the kernel loaded straight from the caller's
+        pinned arrays instead of a copy (acnqp_debug_direct_in: introspection, not part of the ABI)."""
+        return int(self._lib.acnqp_debug_direct_in(self._h))
 
     def ordered_launches(self) -> int:
         """Launches of this handle whose queue order was sorted by a key (acnqp_ordered_launch_count)."""

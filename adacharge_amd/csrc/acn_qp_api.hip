@@ -86,6 +86,7 @@ struct acnqp_handle {
   hipEvent_t ev_start[kEvRing] = {}, ev_stop[kEvRing] = {};
   long long launches = 0, reported = 0;           // launches recorded / already handed out by acnqp_kernel_times
   long long ordered_launches = 0;                 // launches whose queue order was sorted by launch_order_keys' key (acnqp_ordered_launch_count)
+  long long direct_in_last = 0;                   // ... whose lb / ub / q the kernel loaded from the caller's arrays (acnqp_debug_direct_in)
   long long direct_x_last = 0;                    // problems of the last host-entry call whose x the kernel stored into the caller's array (acnqp_debug_direct_x)
   // host-buffer entry points: kSlots pipeline slots, each with its own stream and device staging, so that the
   // H2D copies, the kernel and the D2H copies of successive chunks of a call overlap
@@ -225,9 +226,16 @@ bool wide_polish_route(const acnqp_handle* h, const acnqp::Route& rt) {
 }
 
 // acnqp_solve_batch_device with the pipeline's knowledge of what comes after the launch (nothing_follows: launch_with_polish)
-// and of where the schedules go (x_host: TiledArgs::x_host, a device array; null: r->x only)
+// and of the direct paths (ht: device arrays of host addresses -- x: TiledArgs::x_host, where the schedules go besides r->x;
+// lb, ub, q: TiledArgs::lb_host ..., where the kernel finds the inputs that p->lb / ub / q do not hold yet)
+struct HostTables {
+  double* const* x = nullptr;
+  const double* const* lb = nullptr;   // (all three, or none)
+  const double* const* ub = nullptr;
+  const double* const* q = nullptr;
+};
 int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows,
-                       double* const* x_host = nullptr);
+                       const HostTables& ht = HostTables());
 
 }  // namespace
 
@@ -432,6 +440,7 @@ acnqp::TiledArgs tiled_args(const acnqp_handle* h, const acnqp_problems* p, cons
   a.grid_oversub = own ? 4 : 1;
   a.polish_iters = 0; a.polish_stall = 0; a.resume = 0; a.y_for_polish_only = 0; a.pol_rows = 0; a.pol_list = nullptr; a.pol_count = nullptr; a.pol_retired = nullptr; a.count_dev = nullptr;
   a.x_host = nullptr;
+  a.lb_host = nullptr; a.ub_host = nullptr; a.q_host = nullptr;
   return a;
 }
 
@@ -448,13 +457,15 @@ acnqp::TiledArgs tiled_args(const acnqp_handle* h, const acnqp_problems* p, cons
 //  * of the four-wave route (two row tiles x horizon 13-24), the one ordered leg that measured a LOSS under the
 //    congestion key (jpl52 x 24 x 4,096, five runs each: 43.52-43.69 ms by sessions, 43.77-43.99 ms by congestion;
 //    profiles/order_key_ab.json),
-//  * under ACNQP_ORDER_KEY=sessions (diagnostic, read once per process; `overload` names the default).
-// By shape and route, never by batch.
-hipError_t launch_order_keys(acnqp_handle* h, const acnqp::Route& rt, const acnqp_problems* p, hipStream_t st, int32_t* keys) {
+//  * under ACNQP_ORDER_KEY=sessions (diagnostic, read once per process; `overload` names the default),
+//  * of a launch whose lb / ub / q are not on the device when the key kernel would run (small_only: the direct path for
+//    the inputs, acn_qp_pipeline.hpp): the congestion key reads ub.
+// By shape, route and where the inputs are, never by batch.
+hipError_t launch_order_keys(acnqp_handle* h, const acnqp::Route& rt, const acnqp_problems* p, hipStream_t st, int32_t* keys, bool small_only = false) {
   static const bool by_sessions = [] { const char* e = std::getenv("ACNQP_ORDER_KEY"); return e && std::strcmp(e, "sessions") == 0; }();
   const acnqp::SiteShape& s = h->shape;
   const int g_rows = s.cone == ACNQP_CONE_SOC ? 2 * s.M : s.M;
-  const int waves = by_sessions || rt.family == ACNQP_ROUTE_WAVE4 ? 0 : order_key_waves((size_t)s.N, (size_t)p->t_max, (size_t)g_rows);
+  const int waves = by_sessions || small_only || rt.family == ACNQP_ROUTE_WAVE4 ? 0 : order_key_waves((size_t)s.N, (size_t)p->t_max, (size_t)g_rows);
   if (waves == 0) {
     hipLaunchKernelGGL(session_keys_kernel, dim3((p->batch + 3) / 4), dim3(256), 0, st, p->s_len, p->k_sessions * s.N, p->batch, keys);
     return hipGetLastError();
@@ -490,7 +501,7 @@ int schedule_launch(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route&
     if (want_order) {
       int32_t* keys = static_cast<int32_t*>(wk->ord.p) + 64;
       int32_t* order = keys + p->batch;
-      HIP_TRY(launch_order_keys(h, rt, p, st, keys));
+      HIP_TRY(launch_order_keys(h, rt, p, st, keys, a->lb_host != nullptr));
       hipLaunchKernelGGL(order_sort_kernel, dim3(1), dim3(kOrderKeys), 0, st, keys, p->batch, order);
       a->order = order;
       h->ordered_launches++;
@@ -681,6 +692,7 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
     // tight rows than the polish holds: from scratch the launch took 93 ms against 61 ms without a polish.
     a3.warm_x = r->x; a3.warm_y = ybuf;
     a3.x_host = nullptr;   // (the listed problems' schedules go to the host below, whoever had the last word on them)
+    a3.lb_host = nullptr; a3.ub_host = nullptr; a3.q_host = nullptr;   // (the first launch has completed the device copy)
     a3.ws_by_slot = 1; a3.grid_cap = std::min(p->batch, a.grid_oversub > 1 ? 64 : 2 * h->cus);   // (<= the grid the workspace was sized for)
     if (!a.ws_by_slot) a3.grid_cap = std::min(a3.grid_cap, a.grid_cap);
     *e = launch_solver(h, rt, a3, ws, st);
@@ -742,7 +754,7 @@ int launch_wide_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
 }
 
 int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, acnqp_results* r, hipStream_t st, bool nothing_follows,
-                       double* const* x_host) {
+                       const HostTables& ht) {
   int rc = check_problem_shapes(h, p, o, r);
   if (rc != ACNQP_OK) return rc;
   if (p->batch == 0) return ACNQP_OK;
@@ -756,8 +768,10 @@ int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_opt
   const int evk = (int)(h->launches % acnqp_handle::kEvRing);
   HIP_TRY(hipEventRecord(h->ev_start[evk], st));
   const acnqp::Route rt = route_of(h, p->t_max, p->k_sessions, p->batch);
-  if (x_host != nullptr && !rt.direct_x()) return fail(ACNQP_ERR_INVALID, "direct x on a route that cannot store it");   // (run_call asks the same table)
-  a.x_host = x_host;
+  if (ht.x != nullptr && !rt.direct_x()) return fail(ACNQP_ERR_INVALID, "direct x on a route that cannot store it");   // (run_call asks the same table)
+  if (ht.lb != nullptr && !rt.direct_in()) return fail(ACNQP_ERR_INVALID, "direct inputs on a route that cannot load them");
+  a.x_host = ht.x;
+  a.lb_host = ht.lb; a.ub_host = ht.ub; a.q_host = ht.q;
   acnqp_handle::Work* wk = h->work_for(st);
   if ((rc = schedule_launch(h, wk, rt, p, st, &a)) != ACNQP_OK) return rc;
   Workspace ws;
@@ -841,6 +855,10 @@ extern "C" int64_t acnqp_debug_polish_alongside(acnqp_handle* h) {
 // (acnqp_solve_batch / _batches / _table) whose schedule the kernel stored straight into the caller's result array
 // (the direct path, acn_qp_pipeline.hpp) instead of a copy; 0 where every x was copied, -1 without a handle.
 extern "C" int64_t acnqp_debug_direct_x(acnqp_handle* h) { return h ? (int64_t)h->direct_x_last : -1; }
+
+// ... whose lb, ub and q the kernel loaded straight from the caller's arrays (the direct path for the inputs,
+// acn_qp_pipeline.hpp) instead of a copy; 0 where every input was copied, -1 without a handle.
+extern "C" int64_t acnqp_debug_direct_in(acnqp_handle* h) { return h ? (int64_t)h->direct_in_last : -1; }
 
 // Introspection outside include/acn_qp.h (every build): out[0] = live eigenpairs of the site's G G', out[1] = the MFMA
 // k-steps that hold them once compacted (acn_qp_rank.hpp), out[2] = the eigen extent in k-steps of the wave kernel's

@@ -84,6 +84,10 @@ struct TiledArgs {
   double* const* x_host;      // null, or (wave kernel, one wave per problem: Route::direct_x) [B] device-addressable HOST destinations
                               // of the problems' schedules (null entry: none): the wave that gives problem b its verdict also
                               // stores x there, in flat order -- the host entries then copy no x back
+  const double* const* lb_host;   // null, or (wave kernel, one wave per problem: Route::direct_in) [B] device-addressable HOST sources of
+  const double* const* ub_host;   // the problems' lb / ub / q (the three entries of a problem are set together; null entries: read the
+  const double* const* q_host;    // device copy as ever): the wave that starts problem b in pass 0 loads them from there in flat order
+                                  // and stores them into lb / ub / q, which the host entry then has not copied
   int ws_by_slot;  // 1: a streaming kernel's workspace belongs to the workgroup slot (work-queue launches), 0: to the problem
   int grid_oversub; // host side only: workgroups of a work-queue launch per resident slot (1: fully persistent; the pipelined
                     // host entries use 4, so that slots come free while a launch runs and the next stream's small launches --

@@ -36,8 +36,12 @@ inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 // A chunk of `cn` problems carries 16 input arrays (slot.in) and 7 result arrays (slot.out).  Each is one row below, and
 // the layout, the device views, the copies in and out and the scatter of the small results all walk the rows: a new
 // array is one row (and its name in the enum).  Rows stand in DEVICE order, every array on a 256-byte line.
-struct ChunkShape { size_t N, Tm, K, Mg; bool peak, flat, max, warm, want_y, direct; };
-enum class Per : uint8_t { One, NT, KN, T, MgT };                          // elements per problem
+struct ChunkShape {
+  size_t N, Tm, K, Mg;
+  bool peak, flat, max, warm, want_y, direct;
+  bool direct_in = false;   // the chunk carries the host sources of its problems' lb / ub / q beside the destinations (row kXh)
+};
+enum class Per : uint8_t { One, NT, KN, T, MgT, Ptrs };                    // elements per problem
 enum class When : uint8_t { Always, Peak, Flat, Max, Warm, WantY, Direct };  // the shapes that have the array
 // Large: a copy per piece.  Small: rides in the call's pinned mirror, ONE copy per chunk and side (run_call), so the small
 // rows of a side must stand together (static_assert below).
@@ -61,8 +65,10 @@ constexpr ArrayRow kIn[kInRows] = {
     {offsetof(acnqp_problems, lf), 8, Per::One, When::Flat, Size::Small},
     {offsetof(acnqp_problems, dc), 8, Per::One, When::Max, Size::Small},
     {offsetof(acnqp_problems, dfloor), 8, Per::One, When::Max, Size::Small},
-    // xh, the direct path: where the kernel stores each problem's schedule (one double* per problem, filled by fill_dense)
-    {kNoField, sizeof(double*), Per::One, When::Direct, Size::Small},
+    // xh, the direct paths: where the kernel stores each problem's schedule (one double* per problem, filled by fill_dense)
+    // and, in a chunk whose inputs the kernel loads itself (ChunkShape::direct_in), three more tables of cn pointers behind
+    // that one: where it finds each problem's lb, ub and q (kHostLb ...: table k starts k * cn pointers into the row)
+    {kNoField, sizeof(double*), Per::Ptrs, When::Direct, Size::Small},
     {offsetof(acnqp_problems, warm_x), 8, Per::NT, When::Warm, Size::Large},
     {offsetof(acnqp_problems, warm_y), 8, Per::MgT, When::Warm, Size::Large},
 };
@@ -77,11 +83,11 @@ constexpr ArrayRow kOut[kOutRows] = {   // (acnqp_results::x_dev is a destinatio
 };
 
 constexpr bool present(const ArrayRow& r, const ChunkShape& s) {
-  const bool on[] = {true, s.peak, s.flat, s.max, s.warm, s.want_y, s.direct};   // (the order of When)
+  const bool on[] = {true, s.peak, s.flat, s.max, s.warm, s.want_y, s.direct || s.direct_in};   // (the order of When)
   return on[(int)r.when];
 }
 constexpr size_t bytes_per_problem(const ArrayRow& r, const ChunkShape& s) {
-  const size_t n[] = {1, s.N * s.Tm, s.K * s.N, s.Tm, s.Mg * s.Tm};   // (the order of Per)
+  const size_t n[] = {1, s.N * s.Tm, s.K * s.N, s.Tm, s.Mg * s.Tm, s.direct_in ? (size_t)4 : (size_t)1};   // (the order of Per)
   return r.elem * n[(int)r.per];
 }
 // the small rows of a side: [first, end), or {n, n} if they do not stand together
@@ -94,6 +100,7 @@ constexpr RowRange small_rows(const ArrayRow* rows, int n) {
     if (rows[k].size == Size::Small) return {n, n};
   return {first, end};
 }
+enum HostTable { kHostX, kHostLb, kHostUb, kHostQ };   // the tables of row kXh
 constexpr RowRange kSmallIn = small_rows(kIn, kInRows), kSmallOut = small_rows(kOut, kOutRows);
 static_assert(kSmallIn.first < kSmallIn.end && kSmallOut.first < kSmallOut.end, "the small rows of a side are one contiguous run: the pinned mirror is one copy");
 
@@ -103,7 +110,8 @@ struct ChunkLayout {
   ChunkShape shape;
   size_t cn, in[kInRows + 1], out[kOutRows + 1];
   bool direct;   // the chunk carries the host destinations of its problems' schedules (kXh)
-  ChunkLayout(size_t cn_, const ChunkShape& s) : shape(s), cn(cn_), direct(s.direct) {
+  bool direct_in;   // ... and the host sources of their lb / ub / q
+  ChunkLayout(size_t cn_, const ChunkShape& s) : shape(s), cn(cn_), direct(s.direct), direct_in(s.direct_in) {
     auto lay = [&](const ArrayRow* rows, int n, size_t* off) {
       off[0] = 0;
       for (int k = 0; k < n; ++k) off[k + 1] = off[k] + al256(present(rows[k], s) ? cn * bytes_per_problem(rows[k], s) : 0);
@@ -116,6 +124,7 @@ struct ChunkLayout {
   size_t mirror_in_bytes() const { return in[kSmallIn.end] - in[kSmallIn.first]; }
   size_t mirror_out() const { return out[kSmallOut.first]; }
   size_t mirror_out_bytes() const { return out[kSmallOut.end] - out[kSmallOut.first]; }
+  size_t host_table(HostTable k) const { return in[kXh] + (size_t)k * cn * sizeof(double*); }   // (k > kHostX: direct_in chunks only)
 };
 
 // ---- the session-table staging: ONE table -------------------------------------------------------------------------------
@@ -166,6 +175,9 @@ struct PlanEnv {
   bool ramp = true;             // ACNQP_NO_RAMP unset
   bool direct = false;          // not a variable: the kernel stores every schedule of the call into the caller's host arrays
                                 // (Route::direct_x, run_call), so no copy of x stands behind the last launch
+  bool direct_in = false;       // not a variable: the kernel loads lb / ub / q of the call's first problems from the caller's host
+                                // arrays (Route::direct_in, run_call), so the first launch waits for the small arrays only.  Under
+                                // this flag alone may a plan differ from the one without it; none does today
 };
 
 // inputs + results staged per problem -- every one of the kSlots pipeline slots holds a chunk of each, so a chunk is
@@ -428,6 +440,9 @@ struct Call {
   std::vector<ChunkLayout> layout; // [chunk], as run_call reaches them
   std::vector<Scatter> scatter;    // dense entry with staged small arrays
   std::vector<double*> xdst;       // [nb] the direct path: R[g].x as the device addresses it (null: batch g keeps its copies)
+  struct HostIn { const double *lb = nullptr, *ub = nullptr, *q = nullptr; };
+  std::vector<HostIn> isrc;        // [nb] the direct path for the inputs: P[g].lb / ub / q as the device addresses them (all
+                                   // three, or none: batch g keeps its copies); asked of the leading chunk's batches only
 };
 
 // ---- the direct path for x ---------------------------------------------------------------------------------------------
@@ -446,6 +461,29 @@ double* direct_destination(const double* x) {
     return nullptr;
   }
   return at.type == hipMemoryTypeHost ? static_cast<double*>(at.devicePointer) : nullptr;
+}
+
+// ---- the direct path for lb / ub / q --------------------------------------------------------------------------------------
+// The mirror image, for the call's LEADING chunk only: nothing overlaps the copy of the first chunk's inputs, and the
+// wave kernel reads every value of lb / ub / q exactly once, at problem start.  Where the route can do that
+// (Route::direct_in; TiledArgs::lb_host ...) and a batch's lb, ub and q are ALL in device-addressable host memory, the
+// chunk loop queues no copy of the three for that batch's piece of chunk 0 -- in a call of several chunks; a call of one
+// chunk keeps its copies (run_call) --: the first launch starts once the small arrays have landed, its waves fetch the values over the link and complete the chunk's device copy as they go (the retry
+// passes, the polish, the resume launch and the dual report read it), and the next chunk's copies start at once beside
+// it.  The sources ride with the chunk's small inputs (row kXh, tables kHostLb ...), so only the dense entry with its
+// pinned mirrors takes the path; decided per piece, so a call may mix pinned and pageable batches.  The chunk takes the
+// session-count launch order: the congestion key reads ub, which is not on the device when it would run.  Every later
+// chunk, the table entry and the device entry are as they were.
+// ACNQP_NO_DIRECT_IN=1 (diagnostic, read once per process): the copies everywhere.
+const double* direct_source(const double* a) {
+  static const bool off = std::getenv("ACNQP_NO_DIRECT_IN") != nullptr;
+  if (off || a == nullptr) return nullptr;
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, a) != hipSuccess) {   // (memory the runtime does not know: pageable)
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return at.type == hipMemoryTypeHost ? static_cast<const double*>(at.devicePointer) : nullptr;
 }
 
 // the pointer member at byte `field` of an ABI struct (every member the tables name is a pointer to objects)
@@ -486,6 +524,7 @@ std::vector<std::vector<Piece>> split_call(const acnqp_handle* h, const std::vec
           const acnqp::Route rt = acnqp::route_for(h->shape, b.t_max, b.k_sessions, (int)std::min<long long>(total, acnqp::kRouteAnyBatch), route_switches());
           acnqp::PlanEnv e = env;   // (env.direct: every batch of the call has a direct destination)
           e.direct = env.direct && rt.direct_x();
+          e.direct_in = env.direct_in && rt.direct_in();
           caps = acnqp::plan_chunk_caps(total, rt.chunk_want(), acnqp::chunk_cap_by_memory((size_t)h->shape.N, (size_t)b.t_max, (size_t)b.k_sessions),
                                         rt.wv > 0, uniform, e);
         }
@@ -502,12 +541,14 @@ std::vector<std::vector<Piece>> split_call(const acnqp_handle* h, const std::vec
 // ---- fill: a chunk's inputs reach the slot's staging ------------------------------------------------------------------------
 // Problems [lo, lo + n) of the host arrays `src` to [pos, pos + n) of the chunk, row by row: a large row is a copy on st,
 // a small row goes into the pinned mirror hs (hs + L.in[k] mirrors di + L.in[k]; null: no mirror, a copy each).  A row
-// without a source (kXh; the arrays that table_expand_kernel forms) is not the caller's to copy.
-hipError_t upload_piece(const ChunkLayout& L, const acnqp_problems& src, size_t lo, size_t n, size_t pos, char* di, char* hs, hipStream_t st) {
+// without a source (kXh; the arrays that table_expand_kernel forms) is not the caller's to copy, and `loaded` says that the
+// kernel loads this piece's lb / ub / q itself (the direct path for the inputs).
+hipError_t upload_piece(const ChunkLayout& L, const acnqp_problems& src, size_t lo, size_t n, size_t pos, char* di, char* hs, hipStream_t st,
+                        bool loaded = false) {
   hipError_t e = hipSuccess;
   for (int k = 0; k < kInRows && e == hipSuccess; ++k) {
     const char* from = kIn[k].field != kNoField && present(kIn[k], L.shape) ? member(&src, kIn[k].field) : nullptr;
-    if (!from) continue;
+    if (!from || (loaded && (k == kLb || k == kUb || k == kQ))) continue;
     const size_t per = bytes_per_problem(kIn[k], L.shape);
     if (hs && kIn[k].size == Size::Small) std::memcpy(hs + L.in[k] + pos * per, from + lo * per, n * per);
     else e = hipMemcpyAsync(di + L.in[k] + pos * per, from + lo * per, n * per, hipMemcpyHostToDevice, st);
@@ -525,11 +566,21 @@ int fill_dense(acnqp_handle* h, const Call& call, size_t c, const std::vector<Pi
   if (chain && c > 0) HIP_TRY(hipStreamWaitEvent(S.st, h->h2d_done[(c - 1) % acnqp_handle::kSlots], 0));
   for (const Piece& pc : pcs) {
     const size_t lo = (size_t)pc.lo, n = (size_t)pc.n, pos = (size_t)pc.pos;
-    HIP_TRY(upload_piece(L, call.P[pc.g], lo, n, pos, di, hs, S.st));
-    if (hs && L.direct) {   // where the kernel stores each problem's schedule (null: this piece is copied)
-      double** tab = reinterpret_cast<double**>(hs + L.in[kXh]) + pos;
-      double* const dst = call.xdst[pc.g];
-      for (size_t i = 0; i < n; ++i) tab[i] = dst ? dst + (lo + i) * L.shape.N * L.shape.Tm : nullptr;
+    const Call::HostIn in = hs && L.direct_in ? call.isrc[pc.g] : Call::HostIn();   // (all three, or none)
+    HIP_TRY(upload_piece(L, call.P[pc.g], lo, n, pos, di, hs, S.st, in.lb != nullptr));
+    const size_t nv = L.shape.N * L.shape.Tm;
+    if (hs && (L.direct || L.direct_in)) {   // where the kernel stores each problem's schedule (null: this piece is copied)
+      double** tab = reinterpret_cast<double**>(hs + L.host_table(kHostX)) + pos;
+      double* const dst = L.direct ? call.xdst[pc.g] : nullptr;
+      for (size_t i = 0; i < n; ++i) tab[i] = dst ? dst + (lo + i) * nv : nullptr;
+    }
+    if (hs && L.direct_in) {   // where it finds each problem's lb, ub and q (null: this piece was copied)
+      const double* const from[] = {in.lb, in.ub, in.q};
+      const HostTable which[] = {kHostLb, kHostUb, kHostQ};
+      for (int k = 0; k < 3; ++k) {
+        const double** tab = reinterpret_cast<const double**>(hs + L.host_table(which[k])) + pos;
+        for (size_t i = 0; i < n; ++i) tab[i] = from[k] ? from[k] + (lo + i) * nv : nullptr;
+      }
     }
   }
   if (hs) HIP_TRY(hipMemcpyAsync(di + L.mirror_in(), hs + L.mirror_in(), L.mirror_in_bytes(), hipMemcpyHostToDevice, S.st));
@@ -584,7 +635,37 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
     call.xdst[g] = call.bs[g].batch > 0 ? direct_destination(call.R[g].x) : nullptr;
     env.direct = env.direct && (call.xdst[g] != nullptr || call.bs[g].batch == 0);
   }
+  // the direct path for the inputs: the sources of a batch, asked once per batch and call and only of the batches that
+  // reach into the leading chunk (all three arrays, or the batch keeps its copies)
+  h->direct_in_last = 0;
+  call.isrc.assign(call.bs.size(), Call::HostIn());
+  std::vector<char> asked(call.bs.size(), 0);
+  auto sources = [&](int g) {
+    if (!asked[g]) {
+      asked[g] = 1;
+      const acnqp_problems& P = call.P[g];
+      Call::HostIn in;
+      in.lb = direct_source(P.lb);
+      if (in.lb) in.ub = direct_source(P.ub);
+      if (in.ub) in.q = direct_source(P.q);
+      if (in.q) call.isrc[g] = in;
+    }
+    return call.isrc[g].lb != nullptr;
+  };
+  for (size_t g = 0; g < call.bs.size() && !table; ++g)   // the planner's flag: the call's first problem comes that way
+    if (call.bs[g].batch > 0) { env.direct_in = sources((int)g); break; }
   const std::vector<std::vector<Piece>> chunks = split_call(h, call.bs, env);
+  // chunk 0 of a call of several chunks, where its launch's route can load from the host and one of its pieces has sources.
+  // (A call of ONE chunk keeps its copies: nothing runs beside its first launch that the fetch could make room for, and 256
+  // waves fetching 4 MB measured slower than the copy -- the strict batch-256 call 2.852-2.864 -> 2.911-2.930 ms, a loss by
+  // the rule, profiles/direct_in_ab_one_chunk_calls.json.)
+  bool direct_in = false;
+  if (!table && chunks.size() > 1) {
+    const std::vector<Piece>& pcs = chunks[0];
+    const BatchShape& b = call.bs[pcs[0].g];
+    if (route_of(h, b.t_max, b.k_sessions, (int)(pcs.back().pos + pcs.back().n)).direct_in())
+      for (const Piece& pc : pcs) direct_in = sources(pc.g) || direct_in;
+  }
   // a chunk is direct if its launch's route can store to the host and one of its pieces has a destination
   std::vector<char> direct(chunks.size(), 0);
   for (size_t c = 0; c < chunks.size() && !table; ++c) {
@@ -597,7 +678,8 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
     const std::vector<Piece>& pcs = chunks[c];
     const BatchShape& b = call.bs[pcs[0].g];
     return ChunkLayout((size_t)(pcs.back().pos + pcs.back().n),
-                       ChunkShape{N, (size_t)b.t_max, (size_t)b.k_sessions, Mg, s.has_peak != 0, s.has_flat != 0, s.has_max != 0, b.warm, b.want_y, direct[c] != 0});
+                       ChunkShape{N, (size_t)b.t_max, (size_t)b.k_sessions, Mg, s.has_peak != 0, s.has_flat != 0, s.has_max != 0, b.warm, b.want_y, direct[c] != 0,
+                                  direct_in && c == 0});
   };
   // Dense entry only: pinned mirrors of the chunks' SMALL arrays (ChunkLayout::mirror_in / mirror_out: the small rows of
   // the table), whole call -- one H2D and one D2H per chunk instead of nine and five per piece; beyond kSmallCap the per-batch
@@ -618,7 +700,8 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
     HIP_TRY(h->small_in.reserve(in_sum));
     HIP_TRY(h->small_out.reserve(out_sum));
   } else {
-    std::fill(direct.begin(), direct.end(), 0);   // (the destinations ride in the mirror)
+    std::fill(direct.begin(), direct.end(), 0);   // (the destinations and the sources ride in the mirror)
+    direct_in = false;
   }
   for (size_t c = 0; c < chunks.size(); ++c) {
     acnqp_handle::Slot& S = h->slot[c % acnqp_handle::kSlots];
@@ -638,8 +721,14 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
     acnqp_problems dp;
     acnqp_results dr;
     device_views(L, di, dq, b, &dp, &dr);
-    double* const* x_host = L.direct ? reinterpret_cast<double* const*>(di + L.in[kXh]) : nullptr;
-    rc = solve_batch_device(h, &dp, o, &dr, S.st, c + 1 == chunks.size(), x_host);   // (the last chunk: nothing follows its launch)
+    HostTables ht;
+    if (L.direct) ht.x = reinterpret_cast<double* const*>(di + L.host_table(kHostX));
+    if (L.direct_in) {
+      ht.lb = reinterpret_cast<const double* const*>(di + L.host_table(kHostLb));
+      ht.ub = reinterpret_cast<const double* const*>(di + L.host_table(kHostUb));
+      ht.q = reinterpret_cast<const double* const*>(di + L.host_table(kHostQ));
+    }
+    rc = solve_batch_device(h, &dp, o, &dr, S.st, c + 1 == chunks.size(), ht);   // (the last chunk: nothing follows its launch)
     if (rc != ACNQP_OK) return rc;
     if (staged) HIP_TRY(hipMemcpyAsync(ho + L.mirror_out(), dq + L.mirror_out(), L.mirror_out_bytes(), hipMemcpyDeviceToHost, S.st));
     for (const Piece& pc : pcs) {
@@ -647,6 +736,7 @@ int run_call(acnqp_handle* h, Call& call, const acnqp_options* o) {
       const size_t lo = (size_t)pc.lo, n = (size_t)pc.n, pos = (size_t)pc.pos;
       const bool stored = L.direct && call.xdst[pc.g];   // (the kernel has stored this piece's x, or will have)
       if (stored) h->direct_x_last += (long long)n;
+      if (L.direct_in && call.isrc[pc.g].lb) h->direct_in_last += (long long)n;
       for (int k = 0; k < kOutRows; ++k) {   // a copy each, but: x of a stored piece, the small rows of a staged call
         if (!present(kOut[k], L.shape) || (k == kX && stored) || (staged && kOut[k].size == Size::Small)) continue;
         const size_t per = bytes_per_problem(kOut[k], L.shape);

@@ -122,6 +122,11 @@ struct Route {
   // with one wave per problem.  By shape alone.
   bool direct_x() const { return wv == 1; }
 
+  // The kernel can load a problem's lb / ub / q straight from device-addressable host arrays (TiledArgs::lb_host ...; the
+  // dense host entry then copies none of the three for the call's leading chunk, acn_qp_pipeline.hpp): the wave kernel
+  // with one wave per problem, and nothing else.  By shape alone.
+  bool direct_in() const { return wv == 1; }
+
   // Anderson columns the family can hold (acnqp_accel_columns = min(requested, this)); `Kn`: the kernels' own numbers
   template <class Kn> int accel_cap() const {
     if (wv > 0) return Kn::wave_accel();

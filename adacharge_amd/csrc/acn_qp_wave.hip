@@ -20,14 +20,15 @@ static_assert(kRouteWaveTS == kWaveTS, "acn_qp_route.hpp restates the period slo
 // EK: the eigen extent of the instantiation (0: all k-steps, on the eigenbasis every kernel shares; otherwise the site's
 // arrays in the compacted eigenbasis replace them in this launch's copy of the arguments)
 // NE: the EVSE extent of P = Ghat r0 (0: all 16 k-steps), this unit's
-template <int NPW, int TSV, int MT, bool PROX, int EK, int NE = ACNQP_WAVE_NE>
+// HIN: the launch carries host sources of lb / ub / q (TiledArgs::lb_host, the direct path for the inputs)
+template <int NPW, int TSV, int MT, bool PROX, int EK, bool HIN = false, int NE = ACNQP_WAVE_NE>
 static hipError_t launch_wave_prox(const TiledArgs& a_in, const WaveSite& ws, hipStream_t st) {
   TiledArgs a = a_in;
   if (EK > 0) { a.Ghat = ws.Ghat; a.lam = ws.lam; a.fragQ = ws.fragQ; }
   a.accel_mem = std::min(a.accel_mem, kWaveAM);
   const WaveLds L(a.accel_mem, NPW, MT, TSV);
   const size_t lds = (size_t)L.total * 8;
-  auto kern = &admm_wave_kernel<kWaveAM, NPW, TSV, MT, PROX, EK, NE>;
+  auto kern = &admm_wave_kernel<kWaveAM, NPW, TSV, MT, PROX, EK, NE, HIN>;
   if (lds > 64 * 1024) {
     hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
     if (e != hipSuccess) return e;
@@ -56,6 +57,12 @@ static hipError_t launch_wave_prox(const TiledArgs& a_in, const WaveSite& ws, hi
 // (sites without a prox row run the instantiation that carries no prox code)
 template <int NPW, int TSV, int MT, int EK>
 static hipError_t launch_wave_ek(const TiledArgs& a, const WaveSite& ws, hipStream_t st) {
+  if (a.lb_host != nullptr) {   // (Route::direct_in: one wave per problem, and the host entry asks the route first)
+    if constexpr (NPW == 1)
+      return a.lf != nullptr || a.dc != nullptr ? launch_wave_prox<NPW, TSV, MT, true, EK, true>(a, ws, st) : launch_wave_prox<NPW, TSV, MT, false, EK, true>(a, ws, st);
+    else
+      return hipErrorInvalidValue;
+  }
   return a.lf != nullptr || a.dc != nullptr ? launch_wave_prox<NPW, TSV, MT, true, EK>(a, ws, st) : launch_wave_prox<NPW, TSV, MT, false, EK>(a, ws, st);
 }
 // (the eigen extent: wave_eig_extent, acn_qp_rank.hpp -- a function of the site, decided once at acnqp_create)

@@ -126,9 +126,37 @@ __device__ __attribute__((always_inline)) inline void wave_x_to_host(const doubl
   }
 }
 
-template <int AM, int NPW, int TSV, int MT, bool PROX, int EK = 0, int NE = 0>
+// The direct path for lb / ub / q (TiledArgs::lb_host ...), the mirror image: the n = N * Tm doubles of each
+// of the three arrays of one problem come from the caller's host arrays in FLAT order -- lane i loads elements i, i + 64,
+// ..., 512 contiguous bytes per load instruction (the lane = EVSE layout of the device path would be up to 64 requests of
+// 8 bytes, Tm doubles apart, per instruction over the link) -- and go, in the same flat order, into the problem's place in
+// the chunk's device arrays, which the host entry has not filled: a problem's values stand there exactly as they stand in
+// the caller's array.  The fence behind the stores makes them visible to the wave's own loads that follow (the device path,
+// unchanged: another wave of this CU may have pulled a line that two problems share into the vector cache) and to every
+// later reader of the device copy.  Four steps unrolled: twelve loads in flight (a load from the host takes microseconds,
+// and nothing else of the wave runs meanwhile) at 24 registers.  Inlined for the reason given at wave_x_to_host; the
+// values never stand in more registers than that, which is why they do not go through the transpose scratch into the
+// lanes' rows directly: that kept 72 more values live at problem start and took the headline instantiation from 18
+// spilled registers to 183.
+__device__ __attribute__((always_inline)) inline void wave_in_from_host(int n, const double* lh, const double* uh, const double* qh,
+                                                                        double* lb, double* ub, double* q) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll 4
+  for (int k = lane; k < n; k += 64) {
+    const double l = lh[k], u = uh[k], c = qh[k];
+    lb[k] = l; ub[k] = u; q[k] = c;
+  }
+  __threadfence();
+}
+
+// HIN: the instantiation of the launches that carry host sources (TiledArgs::lb_host; one wave per problem only).  A flag of
+// its own, as PROX is: with the load compiled into every instantiation the headline one went from 18 spilled registers
+// and 80 bytes of scratch to 27 and 112 (profiles/direct_in_kernel_resources.md), and all launches but a call's first run
+// without host tables -- they run the kernel they ran before.
+template <int AM, int NPW, int TSV, int MT, bool PROX, int EK = 0, int NE = 0, bool HIN = false>
 __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledArgs A_kernarg) {
   static_assert(NPW == 1 || NPW == 2 || NPW == 4, "one, two or four waves per problem");
+  static_assert(!HIN || NPW == 1, "host sources: one wave per problem");
   static_assert((TSV == 12 && MT == 1) || (TSV == 6 && MT == 2 && NPW >= 2), "instantiated: 12 periods x one row tile, 6 periods x two row tiles");
   using M = Mfma<double>;
   using vec4 = typename M::vec4;
@@ -400,6 +428,17 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
   // ---- problem data -> registers (EVSE layout) ------------------------------------------------------------------------
   const bool act = lane < N;
   real x[TS], z1[TS], y1[TS], qv[TS], lbv[TS], ubv[TS];
+  // The direct path for the inputs (wave-uniform; TiledArgs::lb_host): pass 0 of a problem whose lb / ub / q the host entry
+  // has NOT copied fetches them from the caller's host arrays and completes the device copy first -- the loads below, the
+  // retry passes, the polish, the resume launch and the dual report read A.lb / A.ub / A.q.  A cold path: 15.5 KB over the
+  // link and 15.5 KB of plain vector stores per problem of 54 x 12.
+  if constexpr (HIN) {
+    const real* const lh = pass == 0 && A.lb_host != nullptr ? A.lb_host[b] : nullptr;
+    if (lh != nullptr) {
+      const size_t at = (size_t)b * N * Tm;
+      wave_in_from_host(N * Tm, lh, A.ub_host[b], A.q_host[b], const_cast<real*>(A.lb) + at, const_cast<real*>(A.ub) + at, const_cast<real*>(A.q) + at);
+    }
+  }
 #pragma unroll
   for (int t = 0; t < TS; ++t) {
     const bool ok = act && tb + t < Tm;
@@ -1224,6 +1263,8 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
     // A hand-over may be consumed while this launch still runs (the polish launched alongside): every lane
     // of every part makes its x / y_out stores visible to the whole device (the XCDs' L2s) BEFORE the group's last mailbox
     // exchange, and part 0 publishes the problem after it.  Wave-uniform, and the same in every part.
+    // (The fence covers the direct path for the inputs too: the stores that completed A.lb / A.ub / A.q at problem start
+    //  lie before the solver loop, so the polish alongside reads the problem's bounds and costs after them.)
     if (status == kStatusPolish) __threadfence();
     ol = wave_sum<real>(ol);
     { real o1[1] = {ol}; pu_sum(o1, 1); ol = o1[0]; }

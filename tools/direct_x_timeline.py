@@ -11,6 +11,9 @@ last `--steps` of them are the timed ones.  Per build, medians over those steps,
   last_solver_launch_start                 start of the step's last solver launch, from the step's first activity
   step_activity                            first to last activity
   d2h_copies, d2h_copy_ms                  device-to-host copies per step and the sum of their durations
+  h2d_copies, h2d_copy_ms                  host-to-device copies per step and the sum of their durations (the trace has no
+                                           size column: the copies' time at the link's rate is what tells their bytes)
+  last_input_copy_end                      end of the step's last host-to-device copy, from the step's first activity
   d2h_bytes                                the trace has no size column: 5,184 + 32 bytes per problem where x is copied
                                            back (more than 8 device-to-host copies in a step), 32 where only the small
                                            result arrays are"""
@@ -57,7 +60,7 @@ def solver_launches(step):
 def describe(d, n_steps):
     steps = [s for s in steps_of(events(d)) if len(solver_launches(s)) >= 4][-n_steps:]
     rows = {k: [] for k in ("first_input_copy_to_first_solver_start", "last_solver_end_to_last_activity", "last_solver_launch_start",
-                            "step_activity", "d2h_copies", "d2h_copy_ms")}
+                            "step_activity", "d2h_copies", "d2h_copy_ms", "h2d_copies", "h2d_copy_ms", "last_input_copy_end")}
     for s in steps:
         t0, t1 = s[0][0], max(e[1] for e in s)
         sol = solver_launches(s)
@@ -69,6 +72,9 @@ def describe(d, n_steps):
         rows["step_activity"].append((t1 - t0) / 1e6)
         rows["d2h_copies"].append(len(d2h))
         rows["d2h_copy_ms"].append(sum(e[1] - e[0] for e in d2h) / 1e6)
+        rows["h2d_copies"].append(len(h2d))
+        rows["h2d_copy_ms"].append(sum(e[1] - e[0] for e in h2d) / 1e6)
+        rows["last_input_copy_end"].append((max(e[1] for e in h2d) - t0) / 1e6)
     out = {k: round(statistics.median(v), 3) for k, v in rows.items()}
     out["steps"] = len(steps)
     out["solver_launches_per_step"] = statistics.median(len(solver_launches(s)) for s in steps)
