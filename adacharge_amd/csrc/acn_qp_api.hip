@@ -16,6 +16,7 @@
 
 #include "acn_qp.h"
 #include "acn_qp_launch.hpp"
+#include "acn_qp_polplan.hpp"
 #include "acn_qp_duals.hpp"
 #include "acn_qp_pilots.hpp"
 #include "acn_qp_advance.hpp"
@@ -194,35 +195,14 @@ struct Kernels {
   static long long long_workspace(int NP, int t_max, int K, int MT, int accel) { return acnqp::long_workspace(NP, acnqp::long_tiles(t_max), K, MT, accel); }
 };
 
-// The polish unit's half of the polish decision (the shape's half: Route::polish_shape): LDS doubles for the blocks of
-// the polish's system, -1: no polish for this shape.
-int polish_block_doubles(const acnqp_handle* h, const acnqp::Route& rt) {
-  static const bool no_polish = std::getenv("ACNQP_NO_POLISH") != nullptr;   // diagnostic
-  if (no_polish) return -1;
-  const acnqp::SiteShape& s = h->shape;
-  const int nrow_site = s.M + s.has_peak;
-  // the long-horizon polish (acn_qp_polish_long.hpp): the handle's switch; its blocks live in its slab, sized for the worst case
-  if (rt.polish_long_shape)
-    return h->long_polish && acnqp::polish_long_holds(s.N, rt.t_max, rt.k_sessions, s.Mg, nrow_site) ? acnqp::polish_long_block_doubles(rt.t_max, s.Mg) : -1;
-  if (!rt.polish_shape) return -1;
-  // LDS of a polish workgroup: where the solver kernel runs two workgroups per CU (the headline shape: one column tile,
-  // one row tile, one session slot: 77 KB each) the polish takes no more than one of those slots, so that it starts as
-  // soon as ANY solver workgroup of a neighbouring stream's launch ends; elsewhere the whole CU
-  const bool two_per_cu = rt.tiled && rt.t_max <= 16 && s.MR == 16 && rt.k_sessions == 1;
-  const int blk = acnqp::polish_blocks_that_fit(s.N, rt.t_max, s.Mg, nrow_site, acnqp::polish_max_sess(s.N, rt.k_sessions),
-                                                two_per_cu ? 76 * 1024 : 160 * 1024);
-  // (never a function of the launch size: a problem's result must not depend on what it is batched with, DESIGN.md
-  //  2.3 -- tests/test_batch_invariance.py.  The polish phase runs behind the solver launch; on throughput-bound
-  //  launches it adds its rounds to the launch's end, DESIGN.md 2.3 has the price)
-  return blk < 2 * nrow_site * (2 * nrow_site + 1) / 2 ? -1 : blk;   // not even one full block
-}
-
-// The wide-site polish (acn_qp_polish_wide.hpp) runs for this route: the shape (Route::polish_wide_shape), the handle's
-// switch and the kernel's own tables agree.  (The options' half -- polish_iters > 0 -- is the launch's.)
-bool wide_polish_route(const acnqp_handle* h, const acnqp::Route& rt) {
-  static const bool no_polish = std::getenv("ACNQP_NO_POLISH") != nullptr;   // diagnostic
-  const acnqp::SiteShape& s = h->shape;
-  return !no_polish && h->wide_polish && rt.polish_wide_shape && acnqp::polish_wide_holds(s.N, rt.t_max, rt.k_sessions, s.Mg, s.M + s.has_peak);
+// The polish of a launch (acn_qp_polplan.hpp: whether, by which kernel, with which tables) under the options' polish_iters and
+// max_iter, cold or warm-started.  ACNQP_NO_POLISH (diagnostic, read once per process): none.  (The polish phase runs behind
+// the solver launch; on throughput-bound launches it adds its rounds to the launch's end, DESIGN.md 2.3 has the price.)
+acnqp::PolishPlan polish_plan_of(const acnqp_handle* h, const acnqp::Route& rt, int polish_iters, int max_iter, bool warm) {
+  static const bool no_polish = std::getenv("ACNQP_NO_POLISH") != nullptr;
+  acnqp::PolishSwitches sw;
+  sw.no_polish = no_polish; sw.long_polish = h->long_polish; sw.wide_polish = h->wide_polish;
+  return acnqp::polish_plan(rt, sw, polish_iters, max_iter, warm);
 }
 
 // acnqp_solve_batch_device with the pipeline's knowledge of what comes after the launch (nothing_follows: launch_with_polish)
@@ -251,8 +231,7 @@ int32_t acnqp_route(acnqp_handle* h, int32_t t_max, int32_t k_sessions, int32_t 
   const acnqp::Route r = route_of(h, t_max, k_sessions, batch);
   acnqp_options o;   // (the polish flag: what a launch with the DEFAULT options does)
   acnqp_default_options(&o);
-  if (polish) *polish = (polish_block_doubles(h, r) >= 0 && o.polish_iters > 0 && o.polish_iters < o.max_iter) ? 1 : 0;
-  if (polish && wide_polish_route(h, r) && o.polish_iters > 0) *polish = 1;
+  if (polish) *polish = polish_plan_of(h, r, o.polish_iters, o.max_iter, false).kind != acnqp::PolishKind::none ? 1 : 0;
   return r.family;
 }
 
@@ -580,11 +559,55 @@ __global__ __launch_bounds__(256) void pol_x_to_host_kernel(const int32_t* list,
   }
 }
 
+// The scratch of a polished launch (PolishScratch, acn_qp_polplan.hpp) in this stream's buffer, reserved behind the stream's
+// earlier launches, its counters cleared on `st`: the regions as pointers (saved: the wide kind's; y: the caller's array
+// where it gives one; slab: the long-horizon and wide kinds') and the polish launch's grid.
+struct PolishBuffers { int32_t *ctr, *list, *saved; double *y, *slab; size_t list_bytes; int grid; };
+int reserve_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::PolishPlan& pl, const acnqp::TiledArgs& a, const acnqp_problems* p,
+                   const acnqp_results* r, hipStream_t st, PolishBuffers* pb) {
+  const acnqp::SiteShape& s = h->shape;
+  pb->grid = acnqp::polish_grid(pl.kind, p->batch, a.grid_oversub > 1, h->cus);
+  const acnqp::PolishScratch sc(pl.kind, p->batch, s.Mg, p->t_max, r->y != nullptr,
+                                acnqp::polish_slab_bytes(pl.kind, s, p->t_max, p->k_sessions, pb->grid));
+  HIP_TRY(reserve_behind(st, {{&wk->pol, sc.total}}));
+  char* base = static_cast<char*>(wk->pol.p);
+  pb->ctr = reinterpret_cast<int32_t*>(base + sc.ctr);
+  pb->list = reinterpret_cast<int32_t*>(base + sc.list);
+  pb->saved = reinterpret_cast<int32_t*>(base + sc.saved);
+  pb->y = r->y ? r->y : reinterpret_cast<double*>(base + sc.y);
+  pb->slab = pl.kind == acnqp::PolishKind::on_chip ? nullptr : reinterpret_cast<double*>(base + sc.slab);
+  pb->list_bytes = sc.list_bytes;
+  HIP_TRY(hipMemsetAsync(pb->ctr, 0, acnqp::PolishScratch::kCtrBytes, st));
+  return ACNQP_OK;
+}
+
+// The arguments of the polish kernel of plan `pl` over the list in `pb`, as a serial launch behind the solver (the
+// launch alongside sets its own: alongside, retired, max_polls, taken).
+// (expected: the problems the FIRST launch serves -- its queue_length is the batch, count_dev being null there; only the
+//  resume launch runs over a shorter list.  A first launch over fewer problems would leave the launch alongside polling
+//  until its bound)
+acnqp::PolishArgs polish_args(const acnqp_handle* h, const acnqp::PolishPlan& pl, const PolishBuffers& pb, const acnqp_problems* p,
+                              const acnqp_options* o, const acnqp_results* r) {
+  const acnqp::SiteShape& s = h->shape;
+  const acnqp::SiteDev* d = &h->site;
+  acnqp::PolishArgs pa;
+  pa.B = p->batch; pa.N = s.N; pa.Tm = p->t_max; pa.K = p->k_sessions; pa.M = s.M; pa.Mg = s.Mg; pa.cone = s.cone;
+  pa.has_peak = s.has_peak; pa.max_rows = pl.max_rows; pa.blk_doubles = pl.blk_doubles; pa.max_sess = pl.max_sess;
+  pa.G = d->Gabi; pa.limits = d->limabi;
+  pa.horizon = p->horizon; pa.lb = p->lb; pa.ub = p->ub; pa.q = p->q; pa.pdiag = p->pdiag;
+  pa.s_off = p->s_off; pa.s_len = p->s_len; pa.s_cap = p->s_cap; pa.s_eq = p->s_eq; pa.peak = s.has_peak ? p->peak : nullptr;
+  pa.x = r->x; pa.y = pb.y; pa.status = r->status; pa.iters = r->iters; pa.pri = r->pri_res; pa.dua = r->dua_res; pa.obj = r->obj;
+  pa.list = pb.list; pa.count = pb.ctr + acnqp::kPolCtrListLength; pa.queue = pb.ctr + acnqp::kPolCtrPolishQueue;
+  pa.stats = h->pol_stats; pa.reg_rel = o->reg_rel;
+  pa.alongside = 0; pa.expected = p->batch; pa.retired = nullptr; pa.max_polls = 0; pa.taken = nullptr;
+  return pa;
+}
+
 // ---- the polish (acn_qp_polish.hpp): small sites, separable objective, served by an on-chip kernel ------------------
 // solver kernel (pass 0 up to polish_iters iterations; what has not converged by then is listed) -> polish kernel over
 // the list -> solver kernel again over the list for what the polish gave up on (from scratch, with the retry passes:
 // the answer it had before there was a polish).  Three launches on the stream, the last two nearly empty as a rule.
-// pol_blk: polish_block_doubles of the shape.
+// pl: the launch's plan, on_chip or long_horizon (acn_qp_polish_long.hpp: the same sequence with that kernel).
 //
 // The problems that are handed over are the launch's longest-running ones, and the chip thins out for milliseconds before
 // its last straggler ends: where NOTHING FOLLOWS the launch (a caller's stream; the last chunk of a pipelined call) a
@@ -595,8 +618,8 @@ __global__ __launch_bounds__(256) void pol_x_to_host_kernel(const int32_t* list,
 // of a pipelined call do without: their serial polish already runs under the next chunk's solver, and spinning workgroups
 // would hold CUs that chunk wants.  ACNQP_NO_POLISH_ALONGSIDE=1 (diagnostic, once per process): never.
 int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route& rt, const acnqp::TiledArgs& a, const Workspace& ws,
-                       int pol_blk, const acnqp_problems* p, const acnqp_options* o, const acnqp_results* r, hipStream_t st, bool nothing_follows,
-                       hipError_t* e) {
+                       const acnqp::PolishPlan& pl, const acnqp_problems* p, const acnqp_options* o, const acnqp_results* r, hipStream_t st,
+                       bool nothing_follows, hipError_t* e) {
   static const bool no_alongside = std::getenv("ACNQP_NO_POLISH_ALONGSIDE") != nullptr;
   // looks at the list a workgroup alongside makes per claim (an empty one costs about a microsecond: the default outlasts
   // every launch the project times by seconds); 0: every one of them leaves at once, without a look
@@ -614,29 +637,15 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   //  problems: 7.20-7.36 ms without, 8.02-8.18 ms with; two rounds of problems on 512 slots hand half their stragglers over in
   //  mid-launch, and 16 workgroups then work through a list that the serial launch spreads over the chip)
   // (nor the long-horizon polish, on ACNQP_ROUTE_WAVE5 either: it runs as a serial launch only)
-  const bool lng = rt.polish_long_shape;
+  const bool lng = pl.kind == acnqp::PolishKind::long_horizon;
   const bool alongside = nothing_follows && !no_alongside && rt.wv > 0 && rt.wv != 3 && a.queue != nullptr && !lng;
-  const acnqp::SiteShape& s = h->shape;
-  const acnqp::SiteDev* d = &h->site;
-  const int nrow_site = s.M + s.has_peak;
-  // [0] queue of the polish kernel, [1] queue of the resume launch, [2] list length; list[B]; multipliers [B][Mg][Tm]
-  // unless the caller wants them anyway; then the polish's global scratch for Schur systems beyond its LDS
-  // (the long-horizon polish: tables for the worst case of the shape, so the solver's row count never declines a hand-over)
-  const int pol_max = lng ? acnqp::polish_long_rows(s.Mg, p->t_max) : acnqp::polish_max_rows(nrow_site, p->t_max);
-  const int pol_grid = lng ? acnqp::polish_long_grid(p->batch) : std::max(1, std::min(p->batch, a.grid_oversub > 1 ? 32 : h->cus));
-  const size_t sbytes = lng ? (size_t)acnqp::polish_long_slab_bytes(s.N, p->t_max, p->k_sessions, s.Mg, nrow_site, pol_grid) : 0;
-  const size_t ybytes = r->y ? 0 : (size_t)p->batch * s.Mg * p->t_max * sizeof(double);
-  const size_t lbytes = ((size_t)p->batch * sizeof(int32_t) + 255) & ~(size_t)255;
-  const size_t yb256 = (ybytes + 255) & ~(size_t)255;
-  const size_t need = 256 + lbytes + (lng ? yb256 + sbytes : ybytes);   // (then the long-horizon polish's slabs, one per workgroup)
-  HIP_TRY(reserve_behind(st, {{&wk->pol, need}}));
-  int32_t* ctr = static_cast<int32_t*>(wk->pol.p);
-  int32_t* list = ctr + 64;
-  double* ybuf = r->y ? r->y : reinterpret_cast<double*>(static_cast<char*>(wk->pol.p) + 256 + lbytes);
-  double* slab = lng ? reinterpret_cast<double*>(static_cast<char*>(wk->pol.p) + 256 + lbytes + yb256) : nullptr;
-  HIP_TRY(hipMemsetAsync(ctr, 0, 256, st));   // ([3]: the solver launch's finished problems, for the polish alongside it)
+  PolishBuffers pb;
+  const int rc = reserve_polish(h, wk, pl, a, p, r, st, &pb);
+  if (rc != ACNQP_OK) return rc;
+  int32_t* const list = pb.list;
+  int32_t* const count = pb.ctr + acnqp::kPolCtrListLength;
   if (alongside) {
-    HIP_TRY(hipMemsetAsync(list, 0xff, lbytes, st));   // -1: not published
+    HIP_TRY(hipMemsetAsync(list, 0xff, pb.list_bytes, st));   // -1: not published
     if (!wk->fork) HIP_TRY(hipEventCreateWithFlags(&wk->fork, hipEventDisableTiming));
     if (!wk->join) HIP_TRY(hipEventCreateWithFlags(&wk->join, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(wk->fork, st));   // counters and list are set: from here on the launch alongside may run
@@ -644,29 +653,18 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
   acnqp::TiledArgs a1 = a;
   a1.polish_iters = o->polish_iters - o->polish_iters % std::max(1, o->check_every);   // the exit is taken at a residual check
   if (a1.polish_iters < o->check_every) a1.polish_iters = o->check_every;
-  a1.pol_list = list; a1.pol_count = ctr + 2; a1.y_out = ybuf; a1.pol_rows = lng ? pol_max + 8 : pol_max;   // (polish_fits asks for 8 rows of head room)
+  a1.pol_list = list; a1.pol_count = count; a1.y_out = pb.y; a1.pol_rows = pl.rows_for_solver;
   // (measured, wave kernel: the early hand-over takes 5 % off the headline launch and 23 % off configs[3] site 0, and hands
   //  ten times as many problems to the polish -- one 256-batch per call 81 -> 62 k QP/s, the table path 654 -> 580 k: off
   //  by default; options.polish_stall, ABI v9, is the caller's switch, the environment variable the diagnostic one)
   static const int early = std::getenv("ACNQP_EARLY_HANDOVER") ? std::atoi(std::getenv("ACNQP_EARLY_HANDOVER")) : 0;   // diagnostic: the window (1: polish_iters / 4)
   a1.polish_stall = early > 1 ? early : (early == 1 ? std::max(o->check_every, a1.polish_iters / 4) : o->polish_stall);
   a1.y_for_polish_only = r->y ? 0 : 1;
-  a1.pol_retired = alongside ? ctr + 3 : nullptr;
+  a1.pol_retired = alongside ? pb.ctr + acnqp::kPolCtrRetired : nullptr;
   *e = launch_solver(h, rt, a1, ws, st);
   if (*e == hipSuccess) {
-    acnqp::PolishArgs pa;
-    pa.B = p->batch; pa.N = s.N; pa.Tm = p->t_max; pa.K = p->k_sessions; pa.M = s.M; pa.Mg = s.Mg; pa.cone = s.cone;
-    pa.has_peak = s.has_peak; pa.max_rows = pol_max; pa.blk_doubles = pol_blk;
-    pa.max_sess = lng ? acnqp::polish_long_sess(s.N, p->k_sessions) : acnqp::polish_max_sess(s.N, p->k_sessions);
-    pa.G = d->Gabi; pa.limits = d->limabi;
-    pa.horizon = p->horizon; pa.lb = p->lb; pa.ub = p->ub; pa.q = p->q; pa.pdiag = p->pdiag;
-    pa.s_off = p->s_off; pa.s_len = p->s_len; pa.s_cap = p->s_cap; pa.s_eq = p->s_eq; pa.peak = s.has_peak ? p->peak : nullptr;
-    pa.x = r->x; pa.y = ybuf; pa.status = r->status; pa.iters = r->iters; pa.pri = r->pri_res; pa.dua = r->dua_res; pa.obj = r->obj;
-    pa.list = list; pa.count = ctr + 2; pa.queue = ctr + 0; pa.stats = h->pol_stats; pa.reg_rel = o->reg_rel;
-    // (expected: the problems the FIRST launch serves -- its queue_length is the batch, count_dev being null there; only the
-    //  resume launch runs over a shorter list.  A first launch over fewer problems would leave the launch alongside polling
-    //  until its bound)
-    pa.alongside = 0; pa.expected = p->batch; pa.retired = ctr + 3; pa.max_polls = along_polls; pa.taken = h->pol_stats + 16;
+    acnqp::PolishArgs pa = polish_args(h, pl, pb, p, o, r);
+    pa.retired = pb.ctr + acnqp::kPolCtrRetired; pa.max_polls = along_polls; pa.taken = h->pol_stats + 16;
     if (alongside) {
       // no host synchronisation; nothing the launch alongside waits for is queued behind it: the solver counts its own
       // finished problems, and every poll is bounded
@@ -680,17 +678,15 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
       HIP_TRY(hipEventRecord(wk->join, h->aux));
       HIP_TRY(hipStreamWaitEvent(st, wk->join, 0));
     }
-    // (pipelined chunks hand a handful of problems over: few workgroups, so that the launch does not queue for 256 slots
-    //  behind the neighbouring streams' solver launches)
-    if (*e == hipSuccess) *e = acnqp::launch_polish(pa, pol_grid, st, slab);
+    if (*e == hipSuccess) *e = lng ? acnqp::launch_polish_long(pa, pb.slab, pb.grid, st) : acnqp::launch_polish(pa, pb.grid, st);
   }
   if (*e == hipSuccess) {
     acnqp::TiledArgs a3 = a;
-    a3.resume = 1; a3.order = list; a3.count_dev = ctr + 2; a3.queue = ctr + 1;
+    a3.resume = 1; a3.order = list; a3.count_dev = count; a3.queue = pb.ctr + acnqp::kPolCtrResumeQueue;
     // ... from where the first launch left them: its schedule and site-row multipliers are the warm start of pass 0 (the
     // retry passes that may follow start cold, as always).  Measured on jpl52 x 24 x 4,096, where two problems have more
     // tight rows than the polish holds: from scratch the launch took 93 ms against 61 ms without a polish.
-    a3.warm_x = r->x; a3.warm_y = ybuf;
+    a3.warm_x = r->x; a3.warm_y = pb.y;
     a3.x_host = nullptr;   // (the listed problems' schedules go to the host below, whoever had the last word on them)
     a3.lb_host = nullptr; a3.ub_host = nullptr; a3.q_host = nullptr;   // (the first launch has completed the device copy)
     a3.ws_by_slot = 1; a3.grid_cap = std::min(p->batch, a.grid_oversub > 1 ? 64 : 2 * h->cus);   // (<= the grid the workspace was sized for)
@@ -698,8 +694,8 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
     *e = launch_solver(h, rt, a3, ws, st);
   }
   if (*e == hipSuccess && a.x_host != nullptr) {   // (not a launch of acnqp_launch_count: it belongs to this one)
-    hipLaunchKernelGGL(pol_x_to_host_kernel, dim3((unsigned)std::min(p->batch, 64)), dim3(256), 0, st, list, ctr + 2, p->batch,
-                       s.N * p->t_max, r->x, a.x_host);
+    hipLaunchKernelGGL(pol_x_to_host_kernel, dim3((unsigned)std::min(p->batch, 64)), dim3(256), 0, st, list, count, p->batch,
+                       h->shape.N * p->t_max, r->x, a.x_host);
     *e = hipGetLastError();
   }
   return ACNQP_OK;
@@ -713,43 +709,18 @@ int launch_with_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Rou
 // and switch, never by batch size.  It runs BEHIND the last pass, not from polish_iters on: a wide site's working set
 // changes by one constraint per round, and only the ADMM's final iterate is within the 96 rounds.
 int launch_wide_polish(acnqp_handle* h, acnqp_handle::Work* wk, const acnqp::Route& rt, const acnqp::TiledArgs& a, const Workspace& ws,
-                       const acnqp_problems* p, const acnqp_options* o, const acnqp_results* r, hipStream_t st, hipError_t* e) {
-  const acnqp::SiteShape& s = h->shape;
-  const acnqp::SiteDev* d = &h->site;
-  const int nrow_site = s.M + s.has_peak;
-  // [0] queue of the polish kernel, [2] list length; list[B]; saved status [B]; multipliers [B][Mg][Tm] unless the caller
-  // wants them anyway; then the slabs, one per workgroup
-  const int grid = acnqp::polish_wide_grid(p->batch);
-  const size_t sbytes = (size_t)acnqp::polish_wide_slab_bytes(s.N, p->t_max, p->k_sessions, s.Mg, nrow_site, grid);
-  const size_t lbytes = ((size_t)p->batch * sizeof(int32_t) + 255) & ~(size_t)255;
-  const size_t ybytes = r->y ? 0 : (((size_t)p->batch * s.Mg * p->t_max * sizeof(double) + 255) & ~(size_t)255);
-  HIP_TRY(reserve_behind(st, {{&wk->pol, 256 + 2 * lbytes + ybytes + sbytes}}));
-  char* base = static_cast<char*>(wk->pol.p);
-  int32_t* ctr = reinterpret_cast<int32_t*>(base);
-  int32_t* list = reinterpret_cast<int32_t*>(base + 256);
-  int32_t* saved = reinterpret_cast<int32_t*>(base + 256 + lbytes);
-  double* ybuf = r->y ? r->y : reinterpret_cast<double*>(base + 256 + 2 * lbytes);
-  double* slab = reinterpret_cast<double*>(base + 256 + 2 * lbytes + ybytes);
-  HIP_TRY(hipMemsetAsync(ctr, 0, 256, st));
+                       const acnqp::PolishPlan& pl, const acnqp_problems* p, const acnqp_options* o, const acnqp_results* r, hipStream_t st,
+                       hipError_t* e) {
+  PolishBuffers pb;
+  const int rc = reserve_polish(h, wk, pl, a, p, r, st, &pb);
+  if (rc != ACNQP_OK) return rc;
+  int32_t* const count = pb.ctr + acnqp::kPolCtrListLength;
   acnqp::TiledArgs a1 = a;
-  a1.y_out = ybuf;
+  a1.y_out = pb.y;
   *e = launch_solver(h, rt, a1, ws, st);
-  if (*e == hipSuccess) *e = acnqp::launch_polish_wide_list(r->status, saved, list, ctr + 2, p->batch, st);
-  if (*e == hipSuccess) {
-    acnqp::PolishArgs pa;
-    pa.B = p->batch; pa.N = s.N; pa.Tm = p->t_max; pa.K = p->k_sessions; pa.M = s.M; pa.Mg = s.Mg; pa.cone = s.cone;
-    pa.has_peak = s.has_peak; pa.max_rows = acnqp::polish_long_rows(s.Mg, p->t_max);
-    pa.blk_doubles = acnqp::polish_wide_block_doubles(p->t_max, s.Mg);
-    pa.max_sess = acnqp::polish_long_sess(s.N, p->k_sessions);
-    pa.G = d->Gabi; pa.limits = d->limabi;
-    pa.horizon = p->horizon; pa.lb = p->lb; pa.ub = p->ub; pa.q = p->q; pa.pdiag = p->pdiag;
-    pa.s_off = p->s_off; pa.s_len = p->s_len; pa.s_cap = p->s_cap; pa.s_eq = p->s_eq; pa.peak = s.has_peak ? p->peak : nullptr;
-    pa.x = r->x; pa.y = ybuf; pa.status = r->status; pa.iters = r->iters; pa.pri = r->pri_res; pa.dua = r->dua_res; pa.obj = r->obj;
-    pa.list = list; pa.count = ctr + 2; pa.queue = ctr + 0; pa.stats = h->pol_stats; pa.reg_rel = o->reg_rel;
-    pa.alongside = 0; pa.expected = p->batch; pa.retired = nullptr; pa.max_polls = 0; pa.taken = nullptr;
-    *e = acnqp::launch_polish_wide(pa, slab, grid, st);
-  }
-  if (*e == hipSuccess) *e = acnqp::launch_polish_wide_restore(r->status, saved, list, ctr + 2, p->batch, st);
+  if (*e == hipSuccess) *e = acnqp::launch_polish_wide_list(r->status, pb.saved, pb.list, count, p->batch, st);
+  if (*e == hipSuccess) *e = acnqp::launch_polish_wide(polish_args(h, pl, pb, p, o, r), pb.slab, pb.grid, st);
+  if (*e == hipSuccess) *e = acnqp::launch_polish_wide_restore(r->status, pb.saved, pb.list, count, p->batch, st);
   return ACNQP_OK;
 }
 
@@ -776,15 +747,20 @@ int solve_batch_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_opt
   if ((rc = schedule_launch(h, wk, rt, p, st, &a)) != ACNQP_OK) return rc;
   Workspace ws;
   if ((rc = reserve_workspace(wk, rt, st, &a, &ws)) != ACNQP_OK) return rc;
-  // the polish: the shape's part of the decision is the route's and the polish unit's, the options' part is here
-  const int pol_blk = (o->polish_iters > 0 && o->polish_iters < o->max_iter && !a.warm_x) ? polish_block_doubles(h, rt) : -1;
+  // the polish: shape, switches and options decide in ONE place (acn_qp_polplan.hpp)
+  const acnqp::PolishPlan pl = polish_plan_of(h, rt, o->polish_iters, o->max_iter, a.warm_x != nullptr);
   hipError_t e = hipSuccess;
-  if (pol_blk >= 0) {
-    if ((rc = launch_with_polish(h, wk, rt, a, ws, pol_blk, p, o, r, st, nothing_follows, &e)) != ACNQP_OK) return rc;
-  } else if (o->polish_iters > 0 && wide_polish_route(h, rt)) {   // (cold or warm-started: it starts from the launch's last iterate)
-    if ((rc = launch_wide_polish(h, wk, rt, a, ws, p, o, r, st, &e)) != ACNQP_OK) return rc;
-  } else {
-    e = launch_solver(h, rt, a, ws, st);
+  switch (pl.kind) {
+    case acnqp::PolishKind::on_chip:
+    case acnqp::PolishKind::long_horizon:
+      if ((rc = launch_with_polish(h, wk, rt, a, ws, pl, p, o, r, st, nothing_follows, &e)) != ACNQP_OK) return rc;
+      break;
+    case acnqp::PolishKind::wide:   // (cold or warm-started: it starts from the launch's last iterate)
+      if ((rc = launch_wide_polish(h, wk, rt, a, ws, pl, p, o, r, st, &e)) != ACNQP_OK) return rc;
+      break;
+    case acnqp::PolishKind::none:
+      e = launch_solver(h, rt, a, ws, st);
+      break;
   }
   if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   HIP_TRY(hipEventRecord(h->ev_stop[evk], st));

@@ -19,8 +19,7 @@
 
 namespace acnqp {
 
-// LDS one workgroup may use: the whole CU when alone, half of it when two share the CU
-constexpr int kLdsPerCu = 160 * 1024;
+// (kLdsPerCu, the LDS one workgroup may use: acn_qp_pollds.hpp)
 constexpr int kAccelMax1 = 5, kAccelMax2 = 5;   // Anderson columns compiled into the OCC = 1 / OCC = 2 variants
 
 // Anderson columns that fit next to the solver's own LDS for this kernel shape with `occ` workgroups per CU
@@ -112,26 +111,17 @@ hipError_t launch_stream(const StreamArgs& sa, hipStream_t st);
 // long-horizon kernel (acn_qp_long.hpp); lds_resident: its LDS-resident variant for two column tiles x two row tiles
 int long_tiles(int t_max);
 hipError_t launch_long(const StreamArgs& sa, hipStream_t st, bool lds_resident);
-// polish kernel (acn_qp_polish.hpp): rows of the Schur system its LDS holds for a shape (0: does not fit); launch over
-// the list the solver kernel left
-int polish_blocks_that_fit(int N, int Tm, int Mg, int nrow, int max_sess, int lds_bytes);   // LDS doubles for the per-period blocks (<= the worst case)
-int polish_max_sess(int N, int K);                                            // session columns the capacitance matrix holds
-int polish_max_rows(int nrow, int Tm);                                        // rows the row tables hold
-// (a horizon beyond 32 goes to the long-horizon kernel with `long_slab`, its workgroups' slabs; null there: an error)
-hipError_t launch_polish(const PolishArgs& pa, int max_grid, hipStream_t st, double* long_slab = nullptr);
+// polish kernel (acn_qp_polish.hpp): launch over the list the solver kernel left.  (The sizes of the three polish kernels'
+// tables, their grids and their slabs are inline functions beside the layouts: acn_qp_pollds.hpp, acn_qp_polslab.hpp,
+// acn_qp_polwide.hpp; which kernel a launch runs is the polish plan's, acn_qp_polplan.hpp.)
+hipError_t launch_polish(const PolishArgs& pa, int max_grid, hipStream_t st);
 // long-horizon polish kernel (acn_qp_polish_long.hpp): horizons 33 ... 288, N <= 64; the state in a slab of global memory per
 // workgroup, tables for the worst case of the shape
-int polish_long_grid(int batch);                                              // workgroups (slabs) of a launch
-long long polish_long_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid);   // bytes of the slabs of `grid` workgroups
-int polish_long_block_doubles(int Tm, int Mg);                                // doubles of the packed per-period blocks (PolishArgs.blk_doubles)
 hipError_t launch_polish_long(const PolishArgs& pa, double* slab, int grid, hipStream_t st);
 // wide-site polish kernel (acn_qp_polish_wide.hpp): 64 < N <= 1,024, horizons <= 48, behind the large-site kernel's launch;
 // the state in a slab of global memory per workgroup (acn_qp_polwide.hpp), tables for the worst case of the shape.  The list
 // kernel saves the status of every problem that ended MAX_ITER or SOLVED_INACCURATE in saved[B], marks it and lists it; the
 // restore kernel gives the saved status back to what the polish did not solve.
-int polish_wide_grid(int batch);                                              // workgroups (slabs) of a launch
-long long polish_wide_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid);   // bytes of the slabs of `grid` workgroups
-int polish_wide_block_doubles(int Tm, int Mg);                                // doubles of the packed per-period blocks (PolishArgs.blk_doubles)
 hipError_t launch_polish_wide_list(int32_t* status, int32_t* saved, int32_t* list, int32_t* count, int B, hipStream_t st);
 hipError_t launch_polish_wide(const PolishArgs& pa, double* slab, int grid, hipStream_t st);
 hipError_t launch_polish_wide_restore(int32_t* status, const int32_t* saved, const int32_t* list, const int32_t* count, int B, hipStream_t st);

@@ -18,7 +18,7 @@
 // The kernel below reads top to bottom as step 1 ... step 10 of the specification.  What a thread does on its own
 // variables and sessions -- register arrays and bit masks, fully unrolled -- is written out here; every step on the LDS
 // tables is a call into acn_qp_polish_steps.hpp (PolishArgs and the kPol* constants live there too), with the tight rows
-// as PolTightMask and the blocking-constraint codes as PolCode8.
+// as PolTightMask and the blocking-constraint codes as PolCode8.  The LDS carve-up, PolishLds, is acn_qp_pollds.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,45 +28,6 @@
 #include "acn_qp_polish_steps.hpp"
 
 namespace acnqp {
-
-// LDS carve-up in doubles (host: size; device: offsets)
-struct PolishLds {
-  int xs, ds, gs, u, du, nu, invn, rc0, rc1, rca, rdg, lam, blk, cap, zb, zv, sisq, red, ints, total;
-  int mt_max;   // rows of one period's block at most: two per site row
-  __host__ __device__ PolishLds(int N, int Tm, int Mg, int nrow, int max_rows, int blk_doubles, int max_sess) {
-    int o = 0;
-    mt_max = 2 * nrow;
-    xs = o; o += N * Tm;
-    ds = o; o += N * Tm;
-    gs = o; o += Mg * N;
-    u = o; o += Mg * Tm;
-    du = o; o += Mg * Tm;
-    nu = o; o += nrow * Tm;
-    invn = o; o += N * 4;
-    rc0 = o; o += max_rows;
-    rc1 = o; o += max_rows;
-    rca = o; o += max_rows;
-    rdg = o; o += max_rows;
-    lam = o; o += max_rows;
-    blk = o; o += blk_doubles;                               // the per-period blocks of B, packed lower, one after the other
-    cap = o; o += max_sess * (max_sess + 1) / 2;             // C = I - V' B^-1 V, packed lower
-    zb = o; o += mt_max * max_sess;                          // L_t^-1 V_t of the block in work
-    zv = o; o += max_sess;                                   // V' y, then w
-    sisq = o; o += max_sess;                                 // 1 / sqrt(n_s) of the session columns
-    red = o; o += 16;
-    ints = o;   // ints from here: rj, rr, rt [max_rows], tstart[Tm + 1], boff[Tm + 1], ract[nrow], misc[8], si / sks [max_sess]; then cs[N * Tm] bytes
-    const int nint = 3 * max_rows + 2 * (Tm + 1) + nrow + 8 + 2 * max_sess;
-    o += (nint + 1) / 2 + (N * Tm + 7) / 8;
-    total = o;
-  }
-  // doubles for the blocks that fit `bytes` of LDS, at most what the worst case needs (every site row tight in every period)
-  __host__ static int blocks_that_fit(int N, int Tm, int Mg, int nrow, int max_rows, int max_sess, int bytes) {
-    const int worst = Tm * (2 * nrow) * (2 * nrow + 1) / 2;
-    const long long fixed = (long long)PolishLds(N, Tm, Mg, nrow, max_rows, 0, max_sess).total * 8;
-    const long long room = ((long long)bytes - fixed) / 8;
-    return (int)(room < 0 ? 0 : (room < worst ? room : worst));
-  }
-};
 
 // kPolTQ: periods per thread, 4 (horizons <= 16) or 8 (<= 32).  Two workgroups per CU: a polish workgroup then takes ONE of
 // the two slots the register-resident solver kernel's workgroups take (256 registers, <= 76 KB of LDS on its shapes) and

@@ -1,16 +1,8 @@
-// Long-horizon polish kernel (acn_qp_polish_long.hpp): instantiation, slab sizing and launcher.
+// Long-horizon polish kernel (acn_qp_polish_long.hpp): instantiation and launcher.
 #include "acn_qp_launch.hpp"
 #include "acn_qp_polish_long.hpp"
 
 namespace acnqp {
-
-long long polish_long_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid) {
-  return PolishLongLayout(N, Tm, K, Mg, nrow).slab_bytes() * std::max(1, std::min(grid, kPolLongGrid));
-}
-
-int polish_long_grid(int batch) { return std::max(1, std::min(batch, kPolLongGrid)); }
-
-int polish_long_block_doubles(int Tm, int Mg) { return Tm * (Mg * (Mg + 1) / 2); }
 
 hipError_t launch_polish_long(const PolishArgs& pa, double* slab, int grid, hipStream_t st) {
   const int nrow = pa.M + (pa.has_peak ? 1 : 0);

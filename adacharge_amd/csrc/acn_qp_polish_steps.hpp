@@ -22,6 +22,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "acn_qp_pollds.hpp"
 #include "acn_qp_polslab.hpp"
 
 #if defined(__HIPCC__)
@@ -32,10 +33,7 @@
 
 namespace acnqp {
 
-constexpr int kPolThreads = 256;
-constexpr int kPolMaxRounds = 96;
-constexpr int kPolMaxRows = 256;      // rows of the Schur system at most (row tables; one thread per row in the triangular solves)
-constexpr int kPolMaxSess = 128;      // tight sessions with free variables (columns of V) at most (PolishArgs.max_sess <= this)
+constexpr int kPolMaxRounds = 96;        // (kPolThreads, kPolMaxRows, kPolMaxSess: acn_qp_pollds.hpp)
 constexpr double kPolTolBound = 1e-7;    // |x - bound| below which the ADMM iterate counts as "on the bound"
 constexpr double kPolTolRow = 1e-9;      // relative size of a site-row multiplier that counts as non-zero
 constexpr double kPolTolStep = 1e-7;     // convergence of a round: |dx|_inf <= tol max(1, |x|_inf) (1e-9 sat below the noise the

@@ -1,16 +1,8 @@
-// Wide-site polish kernel (acn_qp_polish_wide.hpp): instantiation, slab sizing and launchers.
+// Wide-site polish kernel (acn_qp_polish_wide.hpp): instantiation and launchers.
 #include "acn_qp_launch.hpp"
 #include "acn_qp_polish_wide.hpp"
 
 namespace acnqp {
-
-int polish_wide_grid(int batch) { return std::max(1, std::min(batch, kPolWideGrid)); }
-
-long long polish_wide_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid) {
-  return PolishWideLayout(N, Tm, K, Mg, nrow).slab_bytes() * polish_wide_grid(grid);
-}
-
-int polish_wide_block_doubles(int Tm, int Mg) { return Tm * (Mg * (Mg + 1) / 2); }
 
 hipError_t launch_polish_wide_list(int32_t* status, int32_t* saved, int32_t* list, int32_t* count, int B, hipStream_t st) {
   hipLaunchKernelGGL(polish_wide_list_kernel, dim3(1), dim3(kPolThreads), 0, st, status, saved, list, count, B);

@@ -7,6 +7,8 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+
 #if defined(__HIPCC__)
 #define ACNQP_SLAB_FN __host__ __device__ inline
 #else
@@ -109,5 +111,12 @@ ACNQP_SLAB_FN bool polish_long_holds(int N, int Tm, int K, int Mg, int nrow) {
   return N >= 1 && N <= kPolLongMaxN && Tm >= kPolLongMinT && Tm <= kPolLongMaxT && K >= 1 && N * K <= kPolLongMaxSess &&
          nrow >= 1 && Mg >= nrow && Mg <= 48;
 }
+// host: workgroups (slabs) of a launch, bytes of the slabs of `grid` workgroups, doubles of the packed per-period blocks
+// (PolishArgs.blk_doubles)
+inline int polish_long_grid(int batch) { return std::max(1, std::min(batch, kPolLongGrid)); }
+inline long long polish_long_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid) {
+  return PolishLongLayout(N, Tm, K, Mg, nrow).slab_bytes() * std::max(1, std::min(grid, kPolLongGrid));
+}
+inline int polish_long_block_doubles(int Tm, int Mg) { return Tm * (Mg * (Mg + 1) / 2); }
 
 }  // namespace acnqp

@@ -102,5 +102,12 @@ ACNQP_SLAB_FN bool polish_wide_holds(int N, int Tm, int K, int Mg, int nrow) {
   return N >= kPolWideMinN && N <= kPolWideMaxN && Tm >= 1 && Tm <= kPolWideMaxT && K >= 1 && K <= kPolWideMaxK &&
          polish_long_sess(N, K) <= kPolWideMaxSess && nrow >= 1 && Mg >= nrow && Mg <= kPolWideMaxMg;
 }
+// host: workgroups (slabs) of a launch, bytes of the slabs of `grid` workgroups, doubles of the packed per-period blocks
+// (PolishArgs.blk_doubles)
+inline int polish_wide_grid(int batch) { return std::max(1, std::min(batch, kPolWideGrid)); }
+inline long long polish_wide_slab_bytes(int N, int Tm, int K, int Mg, int nrow, int grid) {
+  return PolishWideLayout(N, Tm, K, Mg, nrow).slab_bytes() * polish_wide_grid(grid);
+}
+inline int polish_wide_block_doubles(int Tm, int Mg) { return Tm * (Mg * (Mg + 1) / 2); }
 
 }  // namespace acnqp

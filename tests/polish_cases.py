@@ -244,9 +244,11 @@ def declined_rows(batch, b, y, t_max):
 
 def polish_tables(site, t_max, k, tiled):
     """(rows, session columns, doubles for the packed per-period blocks) the polish kernel's LDS holds at a padded shape --
-    polish_max_rows, polish_max_sess and PolishLds of acn_qp_polish.hpp / .hip with polish_block_doubles of acn_qp_api.hip,
-    restated; blocks -1: not even one full block fits and the library runs no polish at this shape.  ``tiled``: the route is
-    one of the register-resident families (two workgroups per CU at t_max <= 16, one row tile, one session slot)."""
+    polish_max_rows, polish_max_sess and PolishLds of acn_qp_pollds.hpp with the LDS budget of polish_plan
+    (acn_qp_polplan.hpp), restated; blocks -1: not even one full block fits and the library runs no polish at this shape.
+    ``tiled``: the route is one of the register-resident families (two workgroups per CU at t_max <= 16, one row tile, one
+    session slot).  tests/test_polish_plan.py compiles the two headers for the host and holds this restatement to them on
+    the CPU, shape by shape; tests/test_polish_gpu.py holds it to what the library runs."""
     N, M, Mg, soc, pk = int(site.N), int(site.M), int(site.Mg), int(site.cone) == 1, int(bool(site.has_peak))
     nrow = M + pk
     rows = min(256, ((2 * nrow * t_max + 7) // 8) * 8)

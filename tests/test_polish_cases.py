@@ -150,8 +150,8 @@ def test_cases_cover_what_the_polish_serves():
 
 
 def test_restated_lds_tables_of_the_polish_kernel():
-    """polish_cases.polish_tables (PolishLds and polish_block_doubles, restated; tests/test_polish_gpu.py holds it to
-    acnqp_route on every shape it runs): no block fits for SOC rows at N = 64 and t_max = 32, so the library runs no polish
+    """polish_cases.polish_tables (PolishLds and polish_plan's LDS budget, restated; tests/test_polish_plan.py holds it to
+    the headers, tests/test_polish_gpu.py to acnqp_route on every shape it runs): no block fits for SOC rows at N = 64 and t_max = 32, so the library runs no polish
     there and polish_kernel<8> over 32 periods is held on N = 52; the LINEAR N = 64 site fits at 32; four session slots leave
     jpl52 at t_max = 32 less room for blocks than two -- and problems of the rows case outgrow it"""
     soc64 = PC.site_pool((64, 4, 0.4), "SOC", (32,), 1, 1).site

@@ -226,6 +226,81 @@ def test_same_bits_alone_and_in_a_batch_three_times_the_size():
             assert np.array_equal(three[key][part * pool.B:(part + 1) * pool.B], alone[key]), (key, part)
 
 
+KEYS = ("x", "y", "status", "iters", "pri_res", "dua_res", "obj")
+
+
+def _launch(h, batch, options, want_y=True):
+    """H.launch_poisoned with or without the caller's multiplier array (without: the launch keeps them in its own scratch)"""
+    import torch
+
+    from adacharge_amd.backend import DeviceBatch
+
+    if want_y:
+        return H.launch_poisoned(h, batch, options)
+    dev = DeviceBatch(batch, "cuda:0", want_y=False)
+    for a in (dev.x, dev.pri_res, dev.dua_res, dev.obj):
+        a.fill_(float("nan"))
+    dev.iters.fill_(-1)
+    dev.status.fill_(-1)
+    h.solve_device(dev, options, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return {k: getattr(dev, k).cpu().numpy() for k in KEYS if k != "y"}
+
+
+def _in_turn_on_one_handle_and_each_on_a_fresh_one(site, launches, **switch):
+    """[(batch, options, want_y)] launched in turn on ONE handle and one stream -- the stream's scratch buffer
+    (acn_qp_polplan.hpp: PolishScratch) is carved anew for each -- against the same launch on a handle of its own: the bits"""
+    from adacharge_amd.backend import SiteHandle
+
+    h = SiteHandle(site, 0, **switch)
+    for n, (batch, o, want_y) in enumerate(launches):
+        s0 = h.polish_stats()
+        got = _launch(h, batch, o, want_y)
+        rose = h.polish_stats()["attempted"] - s0["attempted"]
+        fresh = SiteHandle(site, 0, **switch)
+        ref = _launch(fresh, batch, o, want_y)
+        fresh.close()
+        print(f"[polish-plan] launch {n}: {batch.B} x {batch.N} x {batch.Tm} (K {batch.K}), multipliers {'wanted' if want_y else 'not wanted'}: "
+              f"{rose} handed to the polish, status {got['status'].tolist()}")
+        assert rose > 0, (n, rose)   # (the condition that this launch tests anything)
+        assert set(got) == set(KEYS) - (set() if want_y else {"y"})
+        for key in got:
+            assert np.array_equal(got[key], ref[key]), (n, key)
+    h.close()
+
+
+@pytest.mark.gpu
+def test_one_scratch_buffer_serves_the_on_chip_and_the_long_kind_in_turn():
+    from adacharge_amd.backend import SiteHandle, default_options
+
+    short_name, short_P = "ct54_soc_two", 40          # caltech54 SOC at horizon 12, K = 2: the on-chip polish
+    at = PC.twin(short_name, short_P)                  # (the CPU twin at P, as polish_cases.cpu_case asks it)
+    still_open = [int(b) for b in np.flatnonzero(at["status"] != 1)][:8]
+    assert still_open, at["status"]
+    short = PC.pool(short_name).subset(still_open)
+    long_name, long_P = LC.CASES["ct54_t48@40"][:2]    # the same site at horizon 48: the long-horizon polish
+    lng = LC.pool(long_name)
+    assert short.B <= 8 and lng.B <= 8 and short.Tm == 12
+    h = SiteHandle(lng.site, 0, polish_long=True)
+    fams = [h.route(b.Tm, b.K, b.B) for b in (short, lng)]
+    h.close()
+    assert fams[0][1] == 1 and fams[0][0] not in LONG_FAMILIES and fams[1][1] == 1 and fams[1][0] in LONG_FAMILIES, fams
+    a = (short, default_options(polish_iters=short_P, retry_passes=0), True)
+    b = (lng, default_options(polish_iters=long_P, retry_passes=0), True)
+    _in_turn_on_one_handle_and_each_on_a_fresh_one(lng.site, [a, b, a, b], polish_long=True)
+
+
+@pytest.mark.gpu
+def test_one_scratch_buffer_serves_the_wide_kind_with_and_without_the_callers_multipliers():
+    from adacharge_amd.backend import default_options
+    from tests import polish_wide_cases as WC
+
+    case = "n65_soc"   # the smallest site of tests/polish_wide_cases.py, six problems
+    pool = WC.pool(WC.CASES[case][0])
+    o = default_options(**WC.start_options(case))
+    _in_turn_on_one_handle_and_each_on_a_fresh_one(pool.site, [(pool, o, True), (pool, o, False), (pool, o, True)], polish_wide=True)
+
+
 @pytest.mark.gpu
 def test_the_switch_is_off_by_default_and_leaves_short_horizons_alone():
     from adacharge_amd.backend import SiteHandle, default_options
