@@ -36,3 +36,13 @@ from .utils import infrastructure_constraints_feasible  # noqa: F401
 from .acn import SimpleRampdown  # noqa: F401  (the estimator estimate_max_rate=True reads; acnportal is not a dependency)
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    """``solve_qp`` (adacharge_amd/diff.py: the batched QP as a differentiable torch operation) on first use: torch is
+    plumbing here and is not imported with the package."""
+    if name == "solve_qp":
+        from .diff import solve_qp
+
+        return solve_qp
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

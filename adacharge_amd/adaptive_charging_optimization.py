@@ -406,6 +406,7 @@ class AdaptiveChargingOptimization:
         if not bool(opts.pop("retry_stalled", True)):   # shorthand kept from round 2: the passes live in the library now
             opts["retry_passes"] = 0
         self._last_plan, self._last_batch = plan, None
+        self._last_table, self._last_infrastructure = table, infrastructure
         self._last_handle, self._last_options, self._last_duals = handle, backend.default_options(**opts), None
         if warm_start is not None and any(w is not None for w in warm_start):
             # per problem (x0, y0) or None; a problem without one starts from its own cold start's point only if all
@@ -491,6 +492,54 @@ class AdaptiveChargingOptimization:
             out[f"infrastructure_constraints.{infrastructure.constraint_ids[j]}"] = val
         if site.has_peak and np.isfinite(batch.peak[b][:T]).any():
             out["peak_constraint"] = y[site.Mg - 1].copy()
+        return out
+
+    def schedule_gradients(self, grad_rates, b: int = 0):
+        """How a scalar ``L`` of the optimal schedule of problem ``b`` of the last solve moves with the problem's data:
+        ``grad_rates`` (N, T) is ``dL/d(rates)``; one adjoint solve on the GPU (``SiteHandle.vjp``, include/acn_qp.h) gives, in
+        the reference's units (rates in A, energy in kWh) and with ``f`` the MINIMISED objective as in ``dual_values``:
+
+          * ``"q"``: (N, T) ``dL/dq``, q the linear cost of ``f`` per ampere (objective weights and tariffs enter through it);
+          * ``"energy_demands"``: {session_id: ``dL/d(remaining demand)`` per kWh} (0 for a session whose row is slack);
+          * ``"infrastructure_limits"``: {constraint id: ``dL/d(limit)``, summed over the periods the limit binds in};
+          * ``"peak_limit"``: (T,) ``dL/d(peak limit of period t)`` (only when the solve had a peak limit);
+          * ``"rate_bounds"``: {"lb": (N, T), "ub": (N, T)}, non-zero where the rate sits on that bound;
+          * ``"info"``: dict(verdict, rows, weak, free, solve_residual, stationarity) of ``backend.VjpResult``.  ``weak``
+            counts constraints that are active with a zero multiplier: there the schedule has a kink and the gradient is
+            that of the active set as found.  A verdict other than 0 comes with zero gradients.
+
+        Raises ``ValueError`` with the reason for a problem the adjoint kernel does not serve (more than 64 EVSEs, horizons
+        beyond 32, more than four sessions per EVSE, load-flattening or demand-charge terms)."""
+        res, batch = self.last_result, self.last_batch
+        if res is None or getattr(self, "_last_handle", None) is None:
+            raise RuntimeError("schedule_gradients: no solve yet")
+        from . import backend
+
+        if int(res.status[b]) not in backend.ACCEPTED_STATUSES:
+            raise InfeasibilityException(f"problem {b} ended with status {backend.STATUS_NAMES.get(int(res.status[b]), res.status[b])}: no gradients")
+        table, infrastructure, site = self._last_table, self._last_infrastructure, batch.site
+        T, M = int(batch.T[b]), site.M
+        g = np.asarray(grad_rates, float)
+        if g.ndim != 2 or g.shape[0] != batch.N or g.shape[1] < T:
+            raise ValueError(f"grad_rates must have shape ({batch.N}, {T})")
+        gx = np.zeros((1, batch.N, batch.Tm))
+        gx[0, :, :T] = g[:, :T]
+        one = slice(b, b + 1)
+        point = backend.BatchResult(res.x[one], res.status[one], res.iters[one], res.pri_res[one], res.dua_res[one], res.obj[one], y=res.y[one])
+        v = self._last_handle.vjp(batch.subset(one), point, gx, options=self._last_options)
+        out = {"q": v.q[0][:, :T].copy(), "energy_demands": {}, "infrastructure_limits": {},
+               "rate_bounds": {"lb": v.lb[0][:, :T].copy(), "ub": v.ub[0][:, :T].copy()}}
+        for k in np.flatnonzero(table.prob == b):
+            i, sid = int(table.evse[k]), table.session_ids[k] if table.session_ids is not None else int(k)
+            slot = np.flatnonzero((batch.s_len[b, :, i] > 0) & (batch.s_off[b, :, i] == table.off[k]))
+            k_i = infrastructure.voltages[i] * self.interface.period / 1e3 / 60
+            out["energy_demands"][sid] = float(v.cap[0, slot[0], i]) / k_i if table.rem[k] > 0 and slot.size else 0.0
+        for j in range(M):
+            out["infrastructure_limits"][infrastructure.constraint_ids[j]] = float(v.rows[0, j].sum())
+        if site.has_peak and np.isfinite(batch.peak[b][:T]).any():
+            out["peak_limit"] = v.rows[0, M][:T].copy()
+        out["info"] = dict(verdict=int(v.info[0, 0]), rows=int(v.info[0, 1]), weak=int(v.info[0, 2]), free=int(v.info[0, 3]),
+                           solve_residual=float(v.res[0, 0]), stationarity=float(v.res[0, 1]))
         return out
 
     @property

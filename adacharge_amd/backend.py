@@ -194,6 +194,8 @@ def _abi():
         ("acnqp_select", [h, P(_Problems), i32, i32, i32, ptr, P(_Next), ptr, ptr]),
         # cur, n_evse, n_rows, m, pos, dense, held_x, held_y, prev_status, out, solved, flags
         ("acnqp_hold", [h, P(_Problems), i32, i32, i32, ptr, P(_Results), ptr, ptr, ptr, P(_Results), ptr, ptr]),
+        # problems, options, x, y, status, gx, gq, gcap, grow, glb, gub, info, res
+        ("acnqp_vjp", [h, P(_Problems), P(Options)] + [ptr] * 11),
     ):
         rows += [(stem + "_host", rc, args), (stem + "_device", rc, args + [stream])]
     introspection = [
@@ -393,6 +395,19 @@ class DualResult:
     energy: np.ndarray   # (B,) worst energy-row violation / max(1, |cap|)
     site: np.ndarray     # (B,) worst site-row violation / max(1, limit)
     comp: np.ndarray     # (B,) worst multiplier x slack over the site rows (oracle-free KKT check, scaled as documented)
+
+
+@dataclass
+class VjpResult:
+    """The gradients through the solve of a batch of answers (acnqp_vjp_host / acnqp_vjp_device, include/acn_qp.h), for a
+    scalar L of the schedules with dL/dx given, in the units of the C ABI (minimisation form, energy rows in A-periods)."""
+    q: np.ndarray                # (B, N, Tm) dL/dq; exact 0 on fixed variables and dead periods
+    cap: np.ndarray              # (B, K, N) dL/d(s_cap): layout of s_cap; 0 for a slack row or an empty slot
+    rows: np.ndarray             # (B, M + has_peak, Tm) dL/d(limit of a site row at a period); row M: the peak's periods
+    lb: Optional[np.ndarray]     # (B, N, Tm) dL/dlb, non-zero where the variable sits on lb (None: not asked for)
+    ub: Optional[np.ndarray]     # (B, N, Tm) dL/dub
+    info: np.ndarray             # (B, 4) int32: verdict (0 done), rows of the Schur system, weak members, free variables
+    res: np.ndarray              # (B, 2): residual of the adjoint solve; the primal point's stationarity on free variables
 
 
 class _PlanArrays:
@@ -799,6 +814,55 @@ class SiteHandle:
             self._lib.acnqp_duals_device(self._h, C.byref(p), C.byref(o), _dptr(dev.x), _dptr(dev.y),
                                          _dptr(dev.status) if use_status else None, C.byref(d), C.c_void_p(stream)),
             "acnqp_duals_device",
+        )
+
+    # -- gradients through the solve (acn_qp_vjp.hpp) -----------------------------------------------------------------
+    def vjp(self, batch: ProblemBatch, result: "BatchResult", grad_x, want_bounds: bool = True,
+            options: Optional[Options] = None) -> VjpResult:
+        """acnqp_vjp_host: for the answers ``result`` (a BatchResult with ``y``) to ``batch`` and ``grad_x`` (B, N, Tm) =
+        dL/dx of a scalar L of the schedules, the gradients of L with respect to q, s_cap, the site rows' limits and -- with
+        ``want_bounds`` -- lb and ub, by one adjoint solve per problem on the GPU.  ``options``: those of the solve
+        (``reg_rel`` is read).  Served: N <= 64, horizons <= 32, K <= 4, no load-flattening or demand-charge row; anything
+        else raises ValueError with the reason."""
+        self._check_site(batch)
+        B, N, Tm, K = batch.B, batch.N, batch.Tm, batch.K
+        if self.site.Mg > 0 and result.y is None:
+            raise ValueError("gradients need the site-row multipliers: solve with want_y=True")
+        o = options if options is not None else default_options()
+        p, _, _, keep = self._marshal(batch, False)
+        x, y, st, gx = _f8(result.x), _f8(result.y), _i4(result.status), _f8(grad_x)
+        if x.shape != (B, N, Tm) or st.shape != (B,) or gx.shape != (B, N, Tm) or (y is not None and y.shape != (B, self.site.Mg, Tm)):
+            raise ValueError("result arrays and grad_x do not match the batch")
+        nrow = self.site.M + (1 if self.site.has_peak else 0)
+        out = VjpResult(np.zeros((B, N, Tm)), np.zeros((B, K, N)), np.zeros((B, nrow, Tm)), np.zeros((B, N, Tm)) if want_bounds else None,
+                        np.zeros((B, N, Tm)) if want_bounds else None, np.zeros((B, 4), np.int32), np.zeros((B, 2)))
+        _check(self._lib.acnqp_vjp_host(self._h, C.byref(p), C.byref(o), _ptr(x), _ptr(y), _ptr(st), _ptr(gx), _ptr(out.q), _ptr(out.cap),
+                                        _ptr(out.rows) if nrow else None, _ptr(out.lb), _ptr(out.ub), _ptr(out.info), _ptr(out.res)),
+               "acnqp_vjp_host")
+        del keep
+        return out
+
+    def vjp_device(self, dev: "DeviceBatch", grad_x, gq, gcap, grow, info, res, glb=None, gub=None, options: Optional[Options] = None,
+                   stream: int = 0, use_status: bool = True) -> None:
+        """acnqp_vjp_device: the same for a ``DeviceBatch`` after ``solve_device`` (``want_y=True`` on a site with rows).
+        ``grad_x``, ``gq`` (B, N, Tm), ``gcap`` (B, K, N), ``grow`` (B, M + has_peak, Tm), ``res`` (B, 2) and the optional
+        ``glb``, ``gub`` (B, N, Tm) are float64 device tensors, ``info`` (B, 4) int32.  Asynchronous on ``stream``."""
+        o = options if options is not None else default_options()
+        if self.site.Mg > 0 and dev.y is None:
+            raise ValueError("gradients need the site-row multipliers: DeviceBatch(..., want_y=True)")
+        B, N, Tm, K = dev.B, dev.N, dev.Tm, dev.K
+        nrow = self.site.M + (1 if self.site.has_peak else 0)
+        d = dev.x.device
+        for t, name, dt, shape in ((grad_x, "grad_x", _F8, (B, N, Tm)), (gq, "gq", _F8, (B, N, Tm)), (gcap, "gcap", _F8, (B, K, N)),
+                                   (grow, "grow", _F8, (B, nrow, Tm)), (glb, "glb", _F8, (B, N, Tm)), (gub, "gub", _F8, (B, N, Tm)),
+                                   (info, "info", _I4, (B, 4)), (res, "res", _F8, (B, 2))):
+            _want(t, name, dt, shape, d)
+        p = _device_problems(dev)
+        _check(
+            self._lib.acnqp_vjp_device(self._h, C.byref(p), C.byref(o), _dptr(dev.x), _dptr(dev.y), _dptr(dev.status) if use_status else None,
+                                       _dptr(grad_x), _dptr(gq), _dptr(gcap), _dptr(grow) if nrow else None, _dptr(glb), _dptr(gub),
+                                       _dptr(info), _dptr(res), C.c_void_p(stream)),
+            "acnqp_vjp_device",
         )
 
     # -- pilot signals (acn_qp_pilots.hpp) ----------------------------------------------------------------------------

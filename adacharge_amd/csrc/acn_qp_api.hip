@@ -24,6 +24,7 @@
 #include "acn_qp_plant.hpp"
 #include "acn_qp_estimate.hpp"
 #include "acn_qp_hold.hpp"
+#include "acn_qp_vjp.hpp"
 #include "acn_qp_site.hpp"
 
 namespace {

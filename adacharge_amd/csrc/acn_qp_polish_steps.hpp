@@ -15,7 +15,8 @@
 // What is NOT here, on purpose: the per-thread phases (own variables and sessions, steps 1, 4, the first half of 7, the
 // variable and session halves of 8 and 10, the move, the stationarity loop of the KKT check, writing x) -- register arrays
 // and bit masks, fully unrolled, in the short kernel, loops over the slab in the long one --, and steps 6a / 6b staging, 6c
-// and 6e, where the long kernel's arithmetic differs.
+// and 6e, where the long kernel's arithmetic differs.  (pol_step6_lds states 6a ... 6e on LDS tables for
+// the adjoint kernel, acn_qp_vjp.hpp, which runs ONE such round: DESIGN.md 3.6i.)
 //
 // The first part (constants, PolishArgs, codes, the triangle index) compiles on the host: tests/host/polish_steps.cpp.
 #pragma once
@@ -492,6 +493,90 @@ __device__ __forceinline__ bool pol_step6d(double* CAP, double* ZV, double* DI, 
     __syncthreads();
     if (tid < k) acc -= CAP[k * (k + 1) / 2 + tid] * dme * ZV[k];
   }
+  __syncthreads();
+  return true;
+}
+
+// (6a) ... (6e) on LDS tables, phase for phase as polish_kernel<4 | 8> writes them out between its phase clocks, for a kernel
+// that has none (vjp_kernel, acn_qp_vjp.hpp): the blocks' L D L' (a wave per block), y = B^-1 rhs, the capacitance matrix
+// block by block, C w = V' y, lam = y + B^-1 V w.  In: LAM = rhs, BLK / CAP as pol_step5 left them.  Out: LAM = lam, RDG =
+// 1 / D of the blocks; RCA, ZB and ZV are scratch.  `bad`: an int of LDS the caller has zeroed.  False: a pivot is not
+// positive (block-uniform).  Ends behind a barrier.
+__device__ __forceinline__ bool pol_step6_lds(const PolRows& R, const double* Gs, const signed char* CS, const int* TSTART, const int* BOFF,
+                                              double* BLK, double* CAP, double* ZB, double* ZV, const double* SISQ, const int* SI, const int* SKS,
+                                              int* bad, int N, int Tm, int M, int m, int nsa, int MS, int tid) {
+  const int wave_ = tid >> 6, lane_ = tid & 63;
+  // (6a)
+  for (int t = wave_; t < Tm; t += 4) {
+    const int mt = TSTART[t + 1] - TSTART[t], a0 = TSTART[t];
+    double* blk = BLK + BOFF[t];
+    if (!pol_block_factor(blk, mt, lane_)) { if (lane_ == 0) *bad = 1; continue; }
+    for (int k = lane_; k < mt; k += 64) R.RDG[a0 + k] = 1.0 / blk[k * (k + 1) / 2 + k];
+  }
+  __syncthreads();
+  if (*bad) return false;
+  // (6b)
+  for (int t = wave_; t < Tm; t += 4) {
+    const int mt = TSTART[t + 1] - TSTART[t], a0 = TSTART[t];
+    if (mt > 0) pol_block_solve(BLK + BOFF[t], R.RDG + a0, R.LAM + a0, mt, lane_);
+  }
+  __syncthreads();
+  // (6c)
+  for (int c = tid; c < nsa; c += kPolThreads) {
+    const int ic = SI[c], ks = SKS[c];
+    double z = 0;
+    for (int t = 0; t < Tm; ++t)
+      if (CS[ic * Tm + t] == ks)
+        for (int a = TSTART[t]; a < TSTART[t + 1]; ++a) z += R.at(Gs, N, M, a, ic) * R.LAM[a];
+    ZV[c] = z * SISQ[c];
+  }
+  for (int t = 0; t < Tm; ++t) {
+    const int mt = TSTART[t + 1] - TSTART[t], a0 = TSTART[t];
+    if (mt == 0) continue;   // (block-uniform)
+    const double* blk = BLK + BOFF[t];
+    for (int idx = tid; idx < mt * nsa; idx += kPolThreads) {
+      const int k = idx / nsa, c = idx - k * nsa;
+      const int ic = SI[c];
+      ZB[k * MS + c] = CS[ic * Tm + t] == SKS[c] ? R.at(Gs, N, M, a0 + k, ic) * SISQ[c] : 0.0;
+    }
+    __syncthreads();
+    for (int c = tid; c < nsa; c += kPolThreads) {
+      if (CS[SI[c] * Tm + t] != SKS[c]) continue;
+      for (int k = 0; k < mt; ++k) {
+        const double zk = ZB[k * MS + c] * R.RDG[a0 + k];
+        for (int r = k + 1; r < mt; ++r) ZB[r * MS + c] -= blk[r * (r + 1) / 2 + k] * zk;
+      }
+    }
+    __syncthreads();
+    for (int p = tid; p < nsa * (nsa + 1) / 2; p += kPolThreads) {
+      const int c = pol_tri_row(p);
+      const int c2 = p - c * (c + 1) / 2;
+      if (CS[SI[c] * Tm + t] != SKS[c] || CS[SI[c2] * Tm + t] != SKS[c2]) continue;
+      double sacc = 0;
+      for (int k = 0; k < mt; ++k) sacc += ZB[k * MS + c] * R.RDG[a0 + k] * ZB[k * MS + c2];
+      CAP[p] -= sacc;
+    }
+    __syncthreads();
+  }
+  // (6d) (1 / D of C goes into the Z buffer, free now)
+  if (!pol_step6d(CAP, ZV, ZB, nsa, tid)) return false;
+  // (6e)
+  for (int a = tid; a < m; a += kPolThreads) {
+    const int ta = R.RT[a];
+    double sacc = 0;
+    for (int c = 0; c < nsa; ++c) {
+      const int ic = SI[c];
+      if (CS[ic * Tm + ta] == SKS[c]) sacc += R.at(Gs, N, M, a, ic) * SISQ[c] * ZV[c];
+    }
+    R.RCA[a] = sacc;
+  }
+  __syncthreads();
+  for (int t = wave_; t < Tm; t += 4) {
+    const int mt = TSTART[t + 1] - TSTART[t], a0 = TSTART[t];
+    if (mt > 0) pol_block_solve(BLK + BOFF[t], R.RDG + a0, R.RCA + a0, mt, lane_);
+  }
+  __syncthreads();
+  for (int a = tid; a < m; a += kPolThreads) R.LAM[a] += R.RCA[a];
   __syncthreads();
   return true;
 }

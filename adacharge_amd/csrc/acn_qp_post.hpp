@@ -1,4 +1,4 @@
-// The post-solve entries (dual report, pilot signals, time passes, before the solve, the plant, the estimator, select and hold): argument checks, _device entries, _host entries.  A
+// The post-solve entries (dual report, pilot signals, time passes, before the solve, the plant, the estimator, select and hold, gradients): argument checks, _device entries, _host entries.  A
 // host entry is a TABLE of the arrays it stages and a body that rebuilds the argument structs on staging addresses and
 // calls the _device entry; ONE planner lays the table out and ONE loop (run_staged) moves it.
 // Part 1 (table row, planner, overlap predicate) is plain host code: tests/test_post_stage.py compiles it with the host
@@ -840,6 +840,101 @@ int acnqp_hold_host(acnqp_handle* h, const acnqp_problems* c, int32_t n_evse, in
     rc2.x = dev(RX); rc2.y = dev(RY); rc2.status = dev(RST); rc2.iters = dev(RIT);
     oc.x = dev(OX); oc.y = dev(OY); oc.status = dev(OST); oc.iters = dev(OIT);
     return hold_device(h, &cc, n_evse, n_rows, m, dev(POS), &rc2, dev(HX), dev(HY), dev(PST), &oc, dev(OSV), dev(OFLG), h->slot[0].st, true);
+  });
+}
+
+// ---- gradients through the solve (acn_qp_vjp.hpp) -----------------------------------------------------------------------
+static int check_vjp_args(const acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y,
+                          const int32_t* status, const double* gx, const double* gq, const double* gcap, const double* grow, const double* glb,
+                          const double* gub, const int32_t* info, const double* res, acnqp::VjpTables* tb, const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!p || !o) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  const acnqp::SiteShape& s = h->shape;
+  if (s.has_flat || s.has_max)
+    return fail(ACNQP_ERR_INVALID, w + ": a site with a load-flattening or demand-charge row is not served (its objective is not the header's diagonal form)");
+  if (s.N > 64) return fail(ACNQP_ERR_INVALID, w + ": the site has " + std::to_string(s.N) + " EVSEs, at most 64 are served");
+  if (p->t_max < 1 || p->t_max > 32) return fail(ACNQP_ERR_INVALID, w + ": t_max is " + std::to_string(p->t_max) + ", horizons 1 ... 32 are served");
+  if (p->k_sessions < 1 || p->k_sessions > acnqp::kMaxK)
+    return fail(ACNQP_ERR_INVALID, w + ": k_sessions is " + std::to_string(p->k_sessions) + ", 1 ... 4 session slots are served");
+  const int nrow = s.M + s.has_peak;
+  if (!acnqp::vjp_tables(s.N, p->t_max, p->k_sessions, s.Mg, nrow, tb))
+    return fail(ACNQP_ERR_INVALID, w + ": " + std::to_string(nrow) + " site rows: one period's block of the working set does not fit the LDS");
+  if (p->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (p->batch == 0) return ACNQP_OK;
+  if (!p->horizon || !p->lb || !p->ub || !p->q || !p->pdiag || !p->s_off || !p->s_len || !p->s_cap || !p->s_eq)
+    return fail(ACNQP_ERR_INVALID, w + ": null problem array");
+  if (s.has_peak && !p->peak) return fail(ACNQP_ERR_INVALID, w + ": site has a peak row but peak is null");
+  if (!x || (s.Mg > 0 && !y) || !gx) return fail(ACNQP_ERR_INVALID, w + ": null x, y or gx");
+  if (!gq || !gcap || (nrow > 0 && !grow) || !info || !res) return fail(ACNQP_ERR_INVALID, w + ": null gq, gcap, grow, info or res");
+  if (!(o->reg_rel >= 0)) return fail(ACNQP_ERR_INVALID, w + ": invalid option value (reg_rel)");
+  struct Span { const void* p; size_t n; const char* name; };
+  const size_t B = (size_t)p->batch, N = (size_t)s.N, Tm = (size_t)p->t_max, K = (size_t)p->k_sessions, Mg = (size_t)s.Mg;
+  const size_t nb = B * N * Tm * 8, ns4 = B * K * N * 4, ns8 = B * K * N * 8;
+  const Span in[] = {{p->horizon, B * 4, "horizon"}, {p->lb, nb, "lb"}, {p->ub, nb, "ub"}, {p->q, nb, "q"}, {p->pdiag, B * 8, "pdiag"},
+                     {p->s_off, ns4, "s_off"}, {p->s_len, ns4, "s_len"}, {p->s_cap, ns8, "s_cap"}, {p->s_eq, B, "s_eq"},
+                     {s.has_peak ? p->peak : nullptr, B * Tm * 8, "peak"}, {x, nb, "x"}, {Mg > 0 ? y : nullptr, B * Mg * Tm * 8, "y"},
+                     {status, B * 4, "status"}, {gx, nb, "gx"}};
+  const Span out[] = {{gq, nb, "gq"}, {gcap, ns8, "gcap"}, {grow, B * (size_t)nrow * Tm * 8, "grow"}, {glb, nb, "glb"}, {gub, nb, "gub"},
+                      {info, B * 16, "info"}, {res, B * 16, "res"}};
+  const size_t n_out = sizeof(out) / sizeof(out[0]);
+  for (size_t a = 0; a < n_out; ++a) {
+    for (const Span& sp : in)
+      if (acnqp::spans_meet(out[a].p, out[a].n, sp.p, sp.n))
+        return fail(ACNQP_ERR_INVALID, w + ": an output aliases an input (" + out[a].name + " overlaps " + sp.name + ")");
+    for (size_t b2 = a + 1; b2 < n_out; ++b2)
+      if (acnqp::spans_meet(out[a].p, out[a].n, out[b2].p, out[b2].n))
+        return fail(ACNQP_ERR_INVALID, w + ": two outputs overlap (" + out[a].name + " and " + out[b2].name + ")");
+  }
+  return ACNQP_OK;
+}
+
+int acnqp_vjp_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y, const int32_t* status,
+                     const double* gx, double* gq, double* gcap, double* grow, double* glb, double* gub, int32_t* info, double* res,
+                     void* hip_stream) {
+  acnqp::VjpTables tb;
+  const int rc = check_vjp_args(h, p, o, x, y, status, gx, gq, gcap, grow, glb, gub, info, res, &tb, "acnqp_vjp_device");
+  if (rc != ACNQP_OK || p->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const acnqp::SiteDev* d = &h->site;
+  acnqp::VjpArgs a;
+  a.B = p->batch; a.N = h->shape.N; a.Tm = p->t_max; a.K = p->k_sessions; a.M = h->shape.M; a.Mg = h->shape.Mg; a.cone = h->shape.cone;
+  a.has_peak = h->shape.has_peak;
+  a.max_rows = tb.max_rows; a.blk_doubles = tb.blk_doubles; a.max_sess = tb.max_sess;
+  a.G = d->Gabi; a.limits = d->limabi;
+  a.horizon = p->horizon; a.lb = p->lb; a.ub = p->ub; a.q = p->q; a.pdiag = p->pdiag;
+  a.s_off = p->s_off; a.s_len = p->s_len; a.s_cap = p->s_cap; a.s_eq = p->s_eq;
+  a.peak = h->shape.has_peak ? p->peak : nullptr;
+  a.x = x; a.y = y; a.status = status; a.gx = gx;
+  a.gq = gq; a.gcap = gcap; a.grow = grow; a.glb = glb; a.gub = gub; a.info = info; a.res = res;
+  a.reg_rel = o->reg_rel;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_vjp(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("vjp kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_vjp_host(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y, const int32_t* status,
+                   const double* gx, double* gq, double* gcap, double* grow, double* glb, double* gub, int32_t* info, double* res) {
+  acnqp::VjpTables tb;
+  const int rc = check_vjp_args(h, p, o, x, y, status, gx, gq, gcap, grow, glb, gub, info, res, &tb, "acnqp_vjp_host");
+  if (rc != ACNQP_OK || p->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t N = (size_t)h->shape.N, Tm = (size_t)p->t_max, K = (size_t)p->k_sessions, Mg = (size_t)h->shape.Mg, nv = N * Tm * 8, ns = K * N;
+  const size_t nrow = (size_t)(h->shape.M + h->shape.has_peak);
+  enum { LB, UB, Q, X, Y, GX, SOFF, SLEN, SCAP, PEAK, HOR, PD, SEQ, STAT, GQ, GCAP, GROW, GLB, GUB, INFO, RES, NARR };
+  const S arr[NARR] = {S::in(p->lb, nv), S::in(p->ub, nv), S::in(p->q, nv), S::in(x, nv), S::in(y, Mg * Tm * 8), S::in(gx, nv), S::in(p->s_off, ns * 4),
+                       S::in(p->s_len, ns * 4), S::in(p->s_cap, ns * 8), S::in(p->peak, h->shape.has_peak ? Tm * 8 : 0), S::in(p->horizon, 4),
+                       S::in(p->pdiag, 8), S::in(p->s_eq, 1), S::in(status, status ? 4 : 0), S::out(gq, nv), S::out(gcap, ns * 8),
+                       S::out(grow, nrow * Tm * 8), S::out(glb, glb ? nv : 0), S::out(gub, gub ? nv : 0), S::out(info, 16), S::out(res, 16)};
+  return run_staged(h, arr, NARR, (size_t)p->batch, [&](size_t, size_t nb, auto dev) {
+    acnqp_problems pc = *p;
+    pc.batch = (int32_t)nb;
+    pc.lb = dev(LB); pc.ub = dev(UB); pc.q = dev(Q); pc.s_off = dev(SOFF); pc.s_len = dev(SLEN); pc.s_cap = dev(SCAP);
+    pc.peak = dev(PEAK); pc.horizon = dev(HOR); pc.pdiag = dev(PD); pc.s_eq = dev(SEQ);
+    pc.warm_x = pc.warm_y = nullptr;
+    return acnqp_vjp_device(h, &pc, o, dev(X), dev(Y), dev(STAT), dev(GX), dev(GQ), dev(GCAP), dev(GROW), dev(GLB), dev(GUB), dev(INFO), dev(RES),
+                            h->slot[0].st);
   });
 }
 

@@ -841,6 +841,52 @@ int acnqp_hold_host(acnqp_handle* h, const acnqp_problems* cur, int32_t n_evse, 
                     const int32_t* pos, const acnqp_results* dense, const double* held_x, const double* held_y,
                     const int32_t* prev_status, acnqp_results* out, uint8_t* solved, int32_t* flags);
 
+/* ---- gradients through the solve (additive to ABI v10: new symbols only) ---------------------------------------------
+ * For an answer (x, y) of the library and gx = dL/dx of a scalar L of the schedule: the gradients of L with respect to the
+ * problem's data, by one adjoint solve with the KKT matrix of the optimal working set, in the minimisation form and the
+ * units of this header.  With pd_eff as in the dual report, the working set is taken at (x, y) as the Newton polish takes
+ * its first guess: a variable within 1e-7 of a bound is fixed; an energy row is tight when s_eq holds or its sum reaches
+ * cap - 1e-7 max(1, |cap|); a site row or peak period is tight when its multiplier in y (a SOC pair: its length) exceeds
+ * 1e-9 max(1, |q|_inf).  A tight SOC pair enters by its outward normal at G x and, with a multiplier above
+ * 1e-7 max(1, |q|_inf), by its curvature.  With H = pd_eff I + the curvature and C the tight rows on the free variables,
+ *
+ *     H a + C'm = gx_free,   C a = 0        (dual regularisation as in the polish: dependent rows get the least-norm m)
+ *
+ *   gq    [B*N*Tm]       dL/dq = -a on free variables; exact 0 on fixed ones, at t >= horizon[b] and outside every window
+ *   gcap  [B*K*N]        layout of s_cap: dL/dcap = m of the session's row; 0 for a slack row and an empty slot
+ *   grow  [B*nrow*Tm]    nrow = n_infra + has_peak: dL/d(limit of row r at period t) = m of that row; 0 where it is not
+ *                        tight.  limits[r] is shared by all periods: its gradient is the sum over t.  Row n_infra is the
+ *                        peak row: the gradient of peak[t] is its own entry.  May be NULL when nrow is 0
+ *   glb, gub  [B*N*Tm]   either may be NULL: for a variable fixed at that bound (lb wins where both hold) gx minus the
+ *                        variable's column of (H, C) applied to (a, m); 0 elsewhere
+ *   info  [B*4] int32    [0] verdict: 0 done, 1 status neither SOLVED nor SOLVED_INACCURATE, 2 the working set outgrows
+ *                        the kernel's tables (the polish's limits), 3 a pivot of the factorisation is not positive;
+ *                        [1] rows of the Schur system; [2] weak members: fixed variables with lb < ub and tight
+ *                        inequality energy rows whose own multiplier at (x, y), from stationarity, is below
+ *                        1e-9 max(1, |q|_inf) in magnitude -- there the solution map has a kink and the gradient is that
+ *                        of the working set as taken; [3] free variables
+ *   res   [B*2]          [0] |H a + C'm - gx|_inf on the free variables / max(1, |gx|_inf), of the solve as performed;
+ *                        [1] |pd_eff x + q + G'y + mu|_inf on the free variables / max(1, |q|_inf), mu the least-squares
+ *                        multipliers of the tight energy rows: how far from a KKT point the gradient was taken
+ * A verdict other than 0 writes exact zeros to that problem's gradients, counts and residuals.  No floating-point
+ * atomics, fixed summation order: the same problem gives the same bits in any batch, at any position.
+ *
+ * acnqp_vjp_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns without
+ * synchronising.  p: the problems (warm_x / warm_y ignored); o: read for reg_rel only; x, y (may be NULL for a site
+ * without rows) and status (NULL: every problem counts as solved) as a solve wrote them.  Served: n_evse <= 64,
+ * t_max <= 32, k_sessions <= 4, no flat and no max row.  Refused with ACNQP_ERR_INVALID and acnqp_last_error set,
+ * outputs untouched: a null handle or argument, a shape not served, a null required array, an output that overlaps an
+ * input or another output.  batch == 0 returns ACNQP_OK.                                                               */
+int acnqp_vjp_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y,
+                     const int32_t* status, const double* gx, double* gq, double* gcap, double* grow, double* glb,
+                     double* gub, int32_t* info, double* res, void* hip_stream);
+
+/* acnqp_vjp_host -- the same with host pointers, synchronous; a large batch is processed in chunks.  Same bits as the
+ * device entry.                                                                                                       */
+int acnqp_vjp_host(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y,
+                   const int32_t* status, const double* gx, double* gq, double* gcap, double* grow, double* glb,
+                   double* gub, int32_t* info, double* res);
+
 #ifdef __cplusplus
 }
 #endif
