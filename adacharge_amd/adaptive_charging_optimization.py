@@ -156,11 +156,13 @@ _HANDLE_CACHE = {}          # insertion-ordered: least recently used first
 _HANDLE_CACHE_MAX = 64
 
 
-def _site_handle(infrastructure, constraint_type, with_peak, device, with_flat=False, with_max=False, polish_long=False, polish_wide=False):
-    """One uploaded site per (infrastructure content, cone, peak, GPU, long-horizon and wide-site polish switches).  The
+def _site_handle(infrastructure, constraint_type, with_peak, device, with_flat=False, with_max=False, polish_long=False, polish_wide=False,
+                 vjp_long=False):
+    """One uploaded site per (infrastructure content, cone, peak, GPU, long-horizon and wide-site polish switches, long-horizon
+    gradient switch).  The
     reference rebuilds every atom on every call (adacharge.py:152-158); here the
     site matrix is uploaded once and reused by all later MPC steps.  The switch is part of the key: it is a property
-    of the handle (``acnqp_set_long_polish``, ``acnqp_set_wide_polish``), and two optimizers must never flip each other's."""
+    of the handle (``acnqp_set_long_polish``, ``acnqp_set_wide_polish``, ``acnqp_set_long_vjp``), and two optimizers must never flip each other's."""
     from . import backend
     from .builder import make_site
 
@@ -171,11 +173,12 @@ def _site_handle(infrastructure, constraint_type, with_peak, device, with_flat=F
         None if infrastructure.phases is None else np.asarray(infrastructure.phases).tobytes(),
         np.asarray(infrastructure.voltages).tobytes(),
         constraint_type, bool(with_peak), int(device), bool(with_flat), bool(with_max), bool(polish_long), bool(polish_wide),
+        bool(vjp_long),
     )
     ent = _HANDLE_CACHE.pop(key, None)
     if ent is None:
         site = make_site(infrastructure, constraint_type, with_peak=with_peak, with_flat=with_flat, with_max=with_max)
-        ent = (site, backend.SiteHandle(site, device, polish_long=bool(polish_long), polish_wide=bool(polish_wide)))
+        ent = (site, backend.SiteHandle(site, device, polish_long=bool(polish_long), polish_wide=bool(polish_wide), vjp_long=bool(vjp_long)))
         while len(_HANDLE_CACHE) >= _HANDLE_CACHE_MAX:   # least recently used out; a caller that still holds the pair
             _HANDLE_CACHE.pop(next(iter(_HANDLE_CACHE)))  # keeps its handle alive (SiteHandle frees the device side in __del__)
     _HANDLE_CACHE[key] = ent                             # (re-)inserted last = most recently used
@@ -225,7 +228,10 @@ class AdaptiveChargingOptimization:
             ``acnqp_options`` field); and ``polish_wide`` (default False):
             on sites of 65 ... 1,024 EVSEs the Newton polish runs behind
             the solve on what it left MAX_ITER or SOLVED_INACCURATE
-            (``acnqp_set_wide_polish``; a switch of the site handle too).
+            (``acnqp_set_wide_polish``; a switch of the site handle too);
+            and ``vjp_long`` (default False): ``schedule_gradients`` also
+            serves horizons 33 ... 288 on sites of up to 64 EVSEs
+            (``acnqp_set_long_vjp``; a switch of the site handle too).
         device (int): HIP device ordinal.
     """
 
@@ -394,6 +400,7 @@ class AdaptiveChargingOptimization:
             with_max=_objective_needs_max(self.objective_configuration),
             polish_long=bool(self.solver_options.get("polish_long", False)),
             polish_wide=bool(self.solver_options.get("polish_wide", False)),
+            vjp_long=bool(self.solver_options.get("vjp_long", False)),
         )
         plan = plan_from_table(
             table, infrastructure, self.interface, self.objective_configuration, self.constraint_type,
@@ -403,6 +410,7 @@ class AdaptiveChargingOptimization:
         opts.update(self.solver_options)
         opts.pop("polish_long", None)   # (consumed above: the handle's switches)
         opts.pop("polish_wide", None)
+        opts.pop("vjp_long", None)
         if not bool(opts.pop("retry_stalled", True)):   # shorthand kept from round 2: the passes live in the library now
             opts["retry_passes"] = 0
         self._last_plan, self._last_batch = plan, None
@@ -508,8 +516,9 @@ class AdaptiveChargingOptimization:
             counts constraints that are active with a zero multiplier: there the schedule has a kink and the gradient is
             that of the active set as found.  A verdict other than 0 comes with zero gradients.
 
-        Raises ``ValueError`` with the reason for a problem the adjoint kernel does not serve (more than 64 EVSEs, horizons
-        beyond 32, more than four sessions per EVSE, load-flattening or demand-charge terms)."""
+        Raises ``ValueError`` with the reason for a problem the adjoint kernels do not serve (more than 64 EVSEs, horizons
+        beyond 32 -- beyond 288 with ``solver_options={"vjp_long": True}``, which also asks for a site with at least one
+        constraint --, more than four sessions per EVSE, load-flattening or demand-charge terms)."""
         res, batch = self.last_result, self.last_batch
         if res is None or getattr(self, "_last_handle", None) is None:
             raise RuntimeError("schedule_gradients: no solve yet")

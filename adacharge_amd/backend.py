@@ -178,6 +178,7 @@ def _abi():
         ("acnqp_route", i32, [h, i32, i32, i32, P(i32)]),
         ("acnqp_set_long_polish", rc, [h, i32]),
         ("acnqp_set_wide_polish", rc, [h, i32]),
+        ("acnqp_set_long_vjp", rc, [h, i32]),
     ]
     # acnqp_X_host takes these arguments, acnqp_X_device the same and the stream behind them
     for stem, args in (
@@ -616,16 +617,19 @@ def pinned_empty(shape, dtype=np.float64) -> np.ndarray:
 class SiteHandle:
     """One ``acnqp_handle``: a site uploaded to one GPU."""
 
-    def __init__(self, site: SiteData, device: int = 0, polish_long: bool = False, polish_wide: bool = False):
+    def __init__(self, site: SiteData, device: int = 0, polish_long: bool = False, polish_wide: bool = False, vjp_long: bool = False):
         """``polish_long``: the Newton polish also takes over at horizons 33 ... 288 (N <= 64; ``acnqp_set_long_polish``).
         ``polish_wide``: on sites of 65 ... 1,024 EVSEs (horizons <= 48) the Newton polish runs behind the solver launch on
         what it ended MAX_ITER or SOLVED_INACCURATE (``acnqp_set_wide_polish``).
-        Both off by default: launches then do exactly what they did before there was such a polish."""
+        Both off by default: launches then do exactly what they did before there was such a polish.
+        ``vjp_long``: ``vjp`` / ``vjp_device`` also serve horizons 33 ... 288 (N <= 64, a site with rows; ``acnqp_set_long_vjp``).
+        Off by default: longer horizons are then refused as before; at horizons <= 32 the switch changes nothing."""
         self._lib = load_library()
         self.site = site
         self.device = int(device)
         self.polish_long = bool(polish_long)
         self.polish_wide = bool(polish_wide)
+        self.vjp_long = bool(vjp_long)
         G = np.ascontiguousarray(site.G, dtype=np.float64)
         lim = np.ascontiguousarray(site.limits, dtype=np.float64)
         desc = _Site(
@@ -641,6 +645,8 @@ class SiteHandle:
             _check(self._lib.acnqp_set_long_polish(self._h, 1), "acnqp_set_long_polish")
         if self.polish_wide:
             _check(self._lib.acnqp_set_wide_polish(self._h, 1), "acnqp_set_wide_polish")
+        if self.vjp_long:
+            _check(self._lib.acnqp_set_long_vjp(self._h, 1), "acnqp_set_long_vjp")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -822,8 +828,8 @@ class SiteHandle:
         """acnqp_vjp_host: for the answers ``result`` (a BatchResult with ``y``) to ``batch`` and ``grad_x`` (B, N, Tm) =
         dL/dx of a scalar L of the schedules, the gradients of L with respect to q, s_cap, the site rows' limits and -- with
         ``want_bounds`` -- lb and ub, by one adjoint solve per problem on the GPU.  ``options``: those of the solve
-        (``reg_rel`` is read).  Served: N <= 64, horizons <= 32, K <= 4, no load-flattening or demand-charge row; anything
-        else raises ValueError with the reason."""
+        (``reg_rel`` is read).  Served: N <= 64, horizons <= 32 (to 288 on a ``vjp_long=True`` handle whose site has a
+        row), K <= 4, no load-flattening or demand-charge row; anything else raises ValueError with the reason."""
         self._check_site(batch)
         B, N, Tm, K = batch.B, batch.N, batch.Tm, batch.K
         if self.site.Mg > 0 and result.y is None:

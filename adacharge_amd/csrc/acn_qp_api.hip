@@ -105,12 +105,13 @@ struct acnqp_handle {
   struct Work {
     hipStream_t st; DevBuf buf; DevBuf ord; DevBuf pol; long long used; hipEvent_t last; DevBuf dua;   // pol: the polish's list and multiplier buffer; dua: g of a dual report without z
     hipEvent_t fork = nullptr, join = nullptr;   // the polish alongside a solver launch: where it may start, where it has ended (created on first use)
+    DevBuf vjp;                                  // the slabs of a long-horizon backward (acn_qp_vjp_long.hpp)
     void release() {
       if (last) (void)hipEventDestroy(last);
       if (fork) (void)hipEventDestroy(fork);
       if (join) (void)hipEventDestroy(join);
       last = fork = join = nullptr;
-      for (DevBuf* b : {&buf, &ord, &pol, &dua}) b->release();
+      for (DevBuf* b : {&buf, &ord, &pol, &dua, &vjp}) b->release();
     }
   };
   std::vector<Work> work;
@@ -159,6 +160,7 @@ struct acnqp_handle {
   hipStream_t aux = nullptr;      // the polish launches that run alongside a solver launch (launch_with_polish)
   bool long_polish = false;       // acnqp_set_long_polish: polish_long_shape routes run the long-horizon polish
   bool wide_polish = false;       // acnqp_set_wide_polish: polish_wide_shape routes run the wide-site polish behind the solver launch
+  bool long_vjp = false;          // acnqp_set_long_vjp: the vjp entries serve horizons 33 ... 288 too (acn_qp_vjp_long.hpp)
   // the post-solve host entries' device staging (acn_qp_post.hpp: the whole-call arrays and one chunk).  ONE buffer for
   // the three: each runs on slot[0].st, synchronises it before reserve() and returns synchronised
   DevBuf post_stage;
@@ -796,6 +798,12 @@ static float event_pair_ms(acnqp_handle* h, long long launch) {
 int acnqp_set_long_polish(acnqp_handle* h, int32_t on) {
   if (!h) return fail(ACNQP_ERR_INVALID, "acnqp_set_long_polish: null handle");
   h->long_polish = on != 0;
+  return ACNQP_OK;
+}
+
+int acnqp_set_long_vjp(acnqp_handle* h, int32_t on) {
+  if (!h) return fail(ACNQP_ERR_INVALID, "acnqp_set_long_vjp: null handle");
+  h->long_vjp = on != 0;
   return ACNQP_OK;
 }
 

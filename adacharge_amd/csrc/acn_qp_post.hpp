@@ -854,11 +854,23 @@ static int check_vjp_args(const acnqp_handle* h, const acnqp_problems* p, const 
   if (s.has_flat || s.has_max)
     return fail(ACNQP_ERR_INVALID, w + ": a site with a load-flattening or demand-charge row is not served (its objective is not the header's diagonal form)");
   if (s.N > 64) return fail(ACNQP_ERR_INVALID, w + ": the site has " + std::to_string(s.N) + " EVSEs, at most 64 are served");
-  if (p->t_max < 1 || p->t_max > 32) return fail(ACNQP_ERR_INVALID, w + ": t_max is " + std::to_string(p->t_max) + ", horizons 1 ... 32 are served");
+  const int t_served = h->long_vjp ? acnqp::kPolLongMaxT : 32;   // (acnqp_set_long_vjp: acn_qp_vjp_long.hpp beyond 32)
+  if (p->t_max < 1 || p->t_max > t_served)
+    return fail(ACNQP_ERR_INVALID, w + ": t_max is " + std::to_string(p->t_max) + ", horizons 1 ... " + std::to_string(t_served) + " are served");
   if (p->k_sessions < 1 || p->k_sessions > acnqp::kMaxK)
     return fail(ACNQP_ERR_INVALID, w + ": k_sessions is " + std::to_string(p->k_sessions) + ", 1 ... 4 session slots are served");
   const int nrow = s.M + s.has_peak;
-  if (!acnqp::vjp_tables(s.N, p->t_max, p->k_sessions, s.Mg, nrow, tb))
+  if (p->t_max > 32) {   // the long-horizon kernel: the shapes its layout holds (polish_long_holds), each refusal with its reason
+    const std::string at = w + ": t_max is " + std::to_string(p->t_max) + " and ";
+    if (nrow < 1) return fail(ACNQP_ERR_INVALID, at + "the site has no row: beyond horizon 32 a site with at least one row is served");
+    if (s.Mg > 48) return fail(ACNQP_ERR_INVALID, at + "the site has " + std::to_string(s.Mg) + " rows: beyond horizon 32 at most 48 are served");
+    if (s.N * p->k_sessions > acnqp::kPolLongMaxSess)
+      return fail(ACNQP_ERR_INVALID, at + "N * k_sessions is " + std::to_string(s.N * p->k_sessions) + ": beyond horizon 32 at most 256 are served");
+    if (!acnqp::polish_long_holds(s.N, p->t_max, p->k_sessions, s.Mg, nrow)) return fail(ACNQP_ERR_INVALID, at + "the long-horizon tables do not hold the shape");
+    tb->max_rows = acnqp::polish_long_rows(s.Mg, p->t_max);
+    tb->max_sess = acnqp::polish_long_sess(s.N, p->k_sessions);
+    tb->blk_doubles = acnqp::polish_long_block_doubles(p->t_max, s.Mg);
+  } else if (!acnqp::vjp_tables(s.N, p->t_max, p->k_sessions, s.Mg, nrow, tb))
     return fail(ACNQP_ERR_INVALID, w + ": " + std::to_string(nrow) + " site rows: one period's block of the working set does not fit the LDS");
   if (p->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
   if (p->batch == 0) return ACNQP_OK;
@@ -909,7 +921,20 @@ int acnqp_vjp_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_optio
   a.gq = gq; a.gcap = gcap; a.grow = grow; a.glb = glb; a.gub = gub; a.info = info; a.res = res;
   a.reg_rel = o->reg_rel;
   (void)hipGetLastError();
-  const hipError_t e = acnqp::launch_vjp(a, reinterpret_cast<hipStream_t>(hip_stream));
+  const hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  hipError_t e;
+  if (a.Tm > 32) {
+    // the long-horizon kernel (check_vjp_args has asked for the switch): its slabs in this stream's buffer, reserved behind the
+    // stream's earlier launches -- no synchronisation unless the buffer grows
+    const int nrow = a.M + a.has_peak;
+    const int grid = acnqp::vjp_long_grid(a.N, a.Tm, a.K, a.Mg, nrow, a.B, h->cus);
+    acnqp_handle::Work* wk = h->work_for(st);
+    HIP_TRY(reserve_behind(st, {{&wk->vjp, (size_t)acnqp::PolishLongLayout(a.N, a.Tm, a.K, a.Mg, nrow).slab_bytes() * (size_t)grid}}));
+    e = acnqp::launch_vjp_long(a, static_cast<double*>(wk->vjp.p), grid, st);
+    if (e == hipSuccess && wk->last) HIP_TRY(hipEventRecord(wk->last, st));   // what an eviction of this stream's buffers waits for
+  } else {
+    e = acnqp::launch_vjp(a, st);
+  }
   if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("vjp kernel launch: ") + hipGetErrorString(e));
   return ACNQP_OK;
 }

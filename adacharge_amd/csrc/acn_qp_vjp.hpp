@@ -324,5 +324,11 @@ __global__ __launch_bounds__(kPolThreads, kPolTQ == 4 ? 2 : 1) void vjp_kernel(c
 struct VjpTables { int max_rows, max_sess, blk_doubles; };
 bool vjp_tables(int N, int Tm, int K, int Mg, int nrow, VjpTables* t);
 hipError_t launch_vjp(const VjpArgs& a, hipStream_t st);
+// the long-horizon kernel (acn_qp_vjp_long.hpp: horizons 33 ... 288, the state in a slab of global memory per workgroup):
+// workgroups (slabs) of a launch -- one per problem up to the device's compute units, fewer where the slabs would pass
+// kVjpLongScratchBytes -- and the launcher (slab: that many slabs of PolishLongLayout::slab_bytes(); max_rows, max_sess,
+// blk_doubles of `a`: the layout's worst case)
+int vjp_long_grid(int N, int Tm, int K, int Mg, int nrow, int batch, int cus);
+hipError_t launch_vjp_long(const VjpArgs& a, double* slab, int grid, hipStream_t st);
 
 }  // namespace acnqp

@@ -1,5 +1,5 @@
 """The batched QP as a differentiable torch operation: ``solve_qp`` solves on the GPU (``SiteHandle.solve_device``) and its
-backward is ONE adjoint launch (``SiteHandle.vjp_device``, adacharge_amd/csrc/acn_qp_vjp.hpp) -- for learning objective
+backward is ONE adjoint launch (``SiteHandle.vjp_device``, adacharge_amd/csrc/acn_qp_vjp.hpp, acn_qp_vjp_long.hpp) -- for learning objective
 weights and tariffs against an outcome of the schedule, bilevel pricing, sensitivity studies over scenario batches.
 
     x = solve_qp(handle, template, q, s_cap, lb, ub)      # (B, N, Tm) float64 on the handle's GPU
@@ -8,8 +8,9 @@ weights and tariffs against an outcome of the schedule, bilevel pricing, sensiti
 Everything stays on the current stream; neither direction synchronises with the host.  The gradients are those of the
 active set at the solver's answer (include/acn_qp.h says how it is taken): accurate where the answer is -- solve with tight
 ``eps_abs`` / ``eps_rel`` -- and one-sided at a kink.  The limits of the site's rows belong to the handle, not to the
-problem: their gradients come from ``SiteHandle.vjp_device`` directly.  Served shapes: N <= 64, horizons <= 32, K <= 4, no
-load-flattening or demand-charge row; another shape raises ValueError in backward.
+problem: their gradients come from ``SiteHandle.vjp_device`` directly.  Served shapes: N <= 64, K <= 4, no load-flattening
+or demand-charge row, and horizons <= 32 on any handle; horizons 33 ... 288 on a ``SiteHandle(site, device, vjp_long=True)``
+whose site has at least one row (and at most 48 rows of G).  Another shape raises ValueError in backward, with the reason.
 """
 from __future__ import annotations
 
@@ -55,8 +56,13 @@ class _SolveQP(torch.autograd.Function):
         gq, glb, gub = (torch.empty((B, N, Tm), **f8) for _ in range(3))
         gcap, grow, res = torch.empty((B, K, N), **f8), torch.empty((B, nrow, Tm), **f8), torch.empty((B, 2), **f8)
         info = torch.empty((B, 4), dtype=torch.int32, device=dev.x.device)
-        handle.vjp_device(dev, grad_x.contiguous(), gq, gcap, grow, info, res, glb=glb, gub=gub, options=ctx.options,
-                          stream=torch.cuda.current_stream(dev.x.device).cuda_stream)
+        try:
+            handle.vjp_device(dev, grad_x.contiguous(), gq, gcap, grow, info, res, glb=glb, gub=gub, options=ctx.options,
+                              stream=torch.cuda.current_stream(dev.x.device).cuda_stream)
+        except ValueError as e:
+            if 32 < Tm <= 288 and not handle.vjp_long:
+                raise ValueError(f"{e}; horizons 33 ... 288 are served on a SiteHandle(site, device, vjp_long=True)") from e
+            raise
         _last_info = info
         gpeak = grow[:, M, :].contiguous() if ctx.has_peak and handle.site.has_peak else None
         return None, None, None, gq, gcap, glb, gub, gpeak

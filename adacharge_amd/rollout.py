@@ -422,7 +422,8 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             host_idx = np.asarray(rplan.sel_idx)
     opts = dict(alg.solver_options or {})
     site, handle = _site_handle(infra, alg.constraint_type, table.has_peak, alg.device, with_flat=table.need_flat, with_max=table.need_max,
-                                polish_long=bool(opts.pop("polish_long", False)), polish_wide=bool(opts.pop("polish_wide", False)))
+                                polish_long=bool(opts.pop("polish_long", False)), polish_wide=bool(opts.pop("polish_wide", False)),
+                                vjp_long=bool(opts.pop("vjp_long", False)))
     if not bool(opts.pop("retry_stalled", True)):
         opts["retry_passes"] = 0
     options = backend.default_options(**opts)

@@ -874,7 +874,7 @@ int acnqp_hold_host(acnqp_handle* h, const acnqp_problems* cur, int32_t n_evse, 
  * acnqp_vjp_device -- every pointer is a device pointer on the handle's GPU; enqueued on `hip_stream`, returns without
  * synchronising.  p: the problems (warm_x / warm_y ignored); o: read for reg_rel only; x, y (may be NULL for a site
  * without rows) and status (NULL: every problem counts as solved) as a solve wrote them.  Served: n_evse <= 64,
- * t_max <= 32, k_sessions <= 4, no flat and no max row.  Refused with ACNQP_ERR_INVALID and acnqp_last_error set,
+ * t_max <= 32 (to 288 behind acnqp_set_long_vjp, below), k_sessions <= 4, no flat and no max row.  Refused with ACNQP_ERR_INVALID and acnqp_last_error set,
  * outputs untouched: a null handle or argument, a shape not served, a null required array, an output that overlaps an
  * input or another output.  batch == 0 returns ACNQP_OK.                                                               */
 int acnqp_vjp_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y,
@@ -886,6 +886,19 @@ int acnqp_vjp_device(acnqp_handle* h, const acnqp_problems* p, const acnqp_optio
 int acnqp_vjp_host(acnqp_handle* h, const acnqp_problems* p, const acnqp_options* o, const double* x, const double* y,
                    const int32_t* status, const double* gx, double* gq, double* gcap, double* grow, double* glb,
                    double* gub, int32_t* info, double* res);
+
+/* Additive to ABI v10 (a new symbol; no structure changes): gradients through the solve at horizons 33 ... 288.  A property
+ * of the handle, OFF after acnqp_create: with it off acnqp_vjp_device / acnqp_vjp_host are what they were, and t_max > 32 is
+ * refused with "horizons 1 ... 32 are served".  on != 0: the two entries also serve 33 <= t_max <= 288 on a site with
+ * n_evse <= 64, k_sessions <= 4, at least one row (n_infra + has_peak >= 1), at most 48 rows of acnqp_site.G and no flat or
+ * max row, by a second kernel that keeps its state in a slab of global memory per workgroup (min(batch, compute units)
+ * workgroups, fewer where the slabs would pass 512 MiB; the slabs are the handle's, per stream, and the device entry
+ * synchronises the stream only when they must grow).  Outputs, masks, info and res as above; its tables hold the worst case
+ * of the shape, so verdict 2 does not occur there; same bits in any batch, at any position, from either entry.  For
+ * t_max <= 32 the switch changes nothing: the same kernel, the same bits.  New refusals with it on (ACNQP_ERR_INVALID,
+ * outputs untouched, the reason in acnqp_last_error): t_max > 288 ("horizons 1 ... 288 are served"); and at t_max > 32 a
+ * site without rows, or with more than 48 rows of G.  Returns ACNQP_OK, ACNQP_ERR_INVALID for a null handle.            */
+int acnqp_set_long_vjp(acnqp_handle* h, int32_t on);
 
 #ifdef __cplusplus
 }

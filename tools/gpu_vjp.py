@@ -2,6 +2,10 @@
 16,384 x 54 x 12, against the solve launch of the same batch, in one process.
 
     python tools/gpu_vjp.py [--batch 16384] [--horizon 12] [--out profiles/vjp_timing.json]
+    python tools/gpu_vjp.py --long [--out profiles/vjp_long_timing.json]
+
+``--long``: the long-horizon kernel (adacharge_amd/csrc/acn_qp_vjp_long.hpp, ``solver_options={"vjp_long": True}``) at
+256 x 54 x 144 and at 16 x 54 x 288, each beside its batch's solve launch, into one file.
 
 The kernel time is the median of 5 launches between HIP events (one warm-up launch first); the solve time is the sum of
 the HIP-event durations of the call's launches (``BatchResult.kernel_ms``).  Nothing is asserted about any time.  The
@@ -18,13 +22,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=16384)
-    ap.add_argument("--horizon", type=int, default=12)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vjp_timing.json"))
-    args = ap.parse_args()
+LONG_SHAPES = ((256, 144), (16, 288))   # (batch, horizon) of --long
 
+
+def measure(batch_size, horizon, solver_options=None):
+    """one shape: the solve, then the timed adjoint launches at its answer"""
     import torch
 
     from adacharge_amd import AdaptiveChargingOptimization, ObjectiveComponent, equal_share, quick_charge, sites
@@ -34,8 +36,9 @@ def main():
 
     infra = sites.caltech54()
     iface = Interface({"infrastructure_info": infra, "period": 5})
-    table = st.enforce_pilot_limit(sites.snapshot_table(infra, args.horizon, args.batch), infra)
-    opt = AdaptiveChargingOptimization([ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-12)], iface, "SOC")
+    table = st.enforce_pilot_limit(sites.snapshot_table(infra, horizon, batch_size), infra)
+    opt = AdaptiveChargingOptimization([ObjectiveComponent(quick_charge), ObjectiveComponent(equal_share, 1e-12)], iface, "SOC",
+                                       solver_options=solver_options)
     res, _ = opt.solve_table(table, infra)
     handle, batch = res.handle, opt.last_batch
     dev = DeviceBatch(batch, torch.device("cuda", handle.device), want_y=True)
@@ -64,7 +67,7 @@ def main():
     lean = [launch(False) for _ in range(5)]
     inf, rr = info.cpu().numpy(), r.cpu().numpy()
     done = inf[:, 0] == 0
-    out = {
+    return {
         "shape": [int(B), int(N), int(Tm)],
         "device": torch.cuda.get_device_name(dev.x.device),
         "vjp_launch_ms": {"median": statistics.median(full), "runs": full},
@@ -78,6 +81,22 @@ def main():
         "solve_residual_max": float(rr[done, 0].max()),
         "stationarity": {"median": float(np.median(rr[done, 1])), "max": float(rr[done, 1].max())},
     }
+
+
+def main():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16384)
+    ap.add_argument("--horizon", type=int, default=12)
+    ap.add_argument("--long", action="store_true", help="the long-horizon kernel at 256 x 54 x 144 and 16 x 54 x 288")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.long:
+        args.out = args.out or os.path.join(root, "profiles", "vjp_long_timing.json")
+        out = {"solver_options": {"vjp_long": True}, "launches": [measure(b, t, {"vjp_long": True}) for b, t in LONG_SHAPES]}
+    else:
+        args.out = args.out or os.path.join(root, "profiles", "vjp_timing.json")
+        out = measure(args.batch, args.horizon)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
