@@ -45,4 +45,8 @@ def __getattr__(name):
         from .diff import solve_qp
 
         return solve_qp
+    if name == "simulate_prices":   # the closed-loop rollout as a differentiable operation of the tariff, likewise
+        from .diff import simulate_prices
+
+        return simulate_prices
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -261,7 +261,7 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         return out
 
     def simulate_batch(self, fleets, steps, start_time=0, warm_start=False, return_schedules=False, observer=None, session_order=None,
-                       prices=None, resolve="every_step"):
+                       prices=None, resolve="every_step", keep_tape=False):
         """Closed-loop extension: ``steps`` control periods of B scenarios of this site (``fleets``: one list of EV records
         per scenario, or a ``rollout.FleetTable``) with the whole state resident in HBM.  On one stream, per period:
         ``solve_device -> pilots_device (first period) -> advance_device``, with no host synchronisation inside the loop; an
@@ -307,10 +307,16 @@ class AdaptiveSchedulingAlgorithm(BaseAlgorithm):
         ``iters`` of a held step is 0.  ``quantize`` sets ``max_recompute = 1``: then, as with ``max_recompute=1`` itself, every
         step is solved and the run is the ``"every_step"`` run.  Whenever some step is not solved, ``estimate_max_rate`` and
         ``uninterrupted_charging`` raise ``ValueError``: both are per solve in the reference and have no rule under a held
-        schedule here."""
+        schedule here.
+        ``keep_tape=True`` keeps every step's state on the device in ``RolloutResult.tape`` so that
+        ``rollout.rollout_gradients(result, grad_pilots)`` can run the backward sweep through the whole loop -- gradients of a
+        scalar of the applied pilots with respect to the tariff, the requested energies and the site limits
+        (``rollout.simulate`` says what it holds and what it serves: continuous pilots, every step solved, no battery,
+        estimator or ``session_order``, a site the vjp kernels serve; anything else raises ``ValueError``).  Off, nothing
+        changes."""
         from .rollout import simulate
 
-        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer, session_order, prices, resolve)
+        return simulate(self, fleets, steps, start_time, warm_start, return_schedules, observer, session_order, prices, resolve, keep_tape)
 
 
 class AdaptiveChargingAlgorithmOffline(BaseAlgorithm):

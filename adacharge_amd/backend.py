@@ -197,6 +197,9 @@ def _abi():
         ("acnqp_hold", [h, P(_Problems), i32, i32, i32, ptr, P(_Results), ptr, ptr, ptr, P(_Results), ptr, ptr]),
         # problems, options, x, y, status, gx, gq, gcap, grow, glb, gub, info, res
         ("acnqp_vjp", [h, P(_Problems), P(Options)] + [ptr] * 11),
+        # cur, applied, status, x, plan, cost, max_pilot, gdir, gq_next, gcap_vjp_next, gcap_carry_next, horizon_next, flags_next,
+        # gx, gcap_carry, garr, gprice
+        ("acnqp_advance_vjp", [h, P(_Problems), ptr, ptr, ptr, P(_AdvancePlan), P(ClockCost)] + [ptr] * 11),
     ):
         rows += [(stem + "_host", rc, args), (stem + "_device", rc, args + [stream])]
     introspection = [
@@ -975,6 +978,82 @@ class SiteHandle:
         else:
             _check(self._lib.acnqp_advance_priced_device(*head, C.byref(cost), C.byref(nx), _dptr(flags), C.c_void_p(stream)),
                    "acnqp_advance_priced_device")
+
+    # -- the adjoint of time passes (acn_qp_advance_vjp.hpp) -----------------------------------------------------------------
+    def _advance_vjp_plan(self, plan: AdvancePlan, step: int, seg_row, keep=None):
+        """(the plan's struct for the call of step ``step``, its clock cost or None); ``seg_row`` None: no arrival"""
+        pl = plan._struct(self.site.N, self.site.Mg, step, 0 if seg_row is None else seg_row, keep)
+        if seg_row is None:
+            pl.a_seg = None
+        return pl, plan._cost_struct(self.site.N, keep)
+
+    def advance_vjp(self, cur: dict, plan: AdvancePlan, step: int, applied=None, status=None, x=None, max_pilot=None, gdir=None,
+                    gq_next=None, gcap_vjp_next=None, gcap_carry_next=None, horizon_next=None, flags_next=None, garr=None, gprice=None,
+                    seg_row=0) -> dict:
+        """acnqp_advance_vjp_host: one call of the backward sweep through the closed loop (include/acn_qp.h, "the adjoint of
+        time passes") for the state ``cur`` of step ``step`` -- a dict with ``s_off, s_len, s_cap`` (B, K, N) -- under ``plan``
+        (numpy arrays).  ``applied``, ``gdir`` (B, N), ``status`` (B,), ``x`` (B, N, Tm), ``max_pilot`` (N,): what the step's
+        advance saw and dL/d applied; the ``*_next`` arrays are the adjoints of the next state, None counting as zeros.
+        ``garr`` (A,) and ``gprice`` (B, P) are accumulated across calls: pass the arrays of the previous call, or None to start
+        from zeros (``gprice`` only with a clock cost).  ``seg_row`` None: no arrival in this step.  Returns a dict with
+        ``gcap_carry`` (B, K, N), ``garr``, and, where they apply, ``gx`` (B, N, Tm; not at step -1) and ``gprice``."""
+        off, ln, cap = _i4(cur["s_off"]), _i4(cur["s_len"]), _f8(cur["s_cap"])
+        if off.ndim != 3 or off.shape[2] != self.site.N or off.shape != ln.shape or off.shape != cap.shape:
+            raise ValueError("cur needs s_off, s_len, s_cap of shape (B, K, N) for the handle's site")
+        B, K, N = off.shape
+        xs = _f8(x)
+        if xs is not None and (xs.ndim != 3 or xs.shape[:2] != (B, N)):
+            raise ValueError("x must have shape (B, N, Tm)")
+        Tm =xs.shape[2] if xs is not None else (np.shape(gq_next)[2] if gq_next is not None else int(plan.q_table.shape[2]))
+        keep = []
+        pl, cost = self._advance_vjp_plan(plan, step, seg_row, keep)
+        out = dict(gx=np.zeros((B, N, Tm)) if step >= 0 else None, gcap_carry=np.zeros((B, K, N)),
+                   garr=np.zeros(plan._len("a_evse")) if garr is None else np.ascontiguousarray(garr, np.float64),
+                   gprice=(np.zeros((B, plan.c_series.shape[1])) if gprice is None else np.ascontiguousarray(gprice, np.float64))
+                   if cost is not None else gprice)
+        p = _Problems(B, Tm, K, s_off=_ptr(off), s_len=_ptr(ln), s_cap=_ptr(cap))
+        ins = [_f8(applied), _i4(status), xs]
+        adj = [_f8(max_pilot), _f8(gdir), _f8(gq_next), _f8(gcap_vjp_next), _f8(gcap_carry_next), _i4(horizon_next), _i4(flags_next)]
+        _check(self._lib.acnqp_advance_vjp_host(self._h, C.byref(p), *[_ptr(a) for a in ins], C.byref(pl),
+                                                None if cost is None else C.byref(cost), *[_ptr(a) for a in adj], _ptr(out["gx"]),
+                                                _ptr(out["gcap_carry"]), _ptr(out["garr"]) if out["garr"].size else None,
+                                                _ptr(_f8(out["gprice"]))),
+               "acnqp_advance_vjp_host")
+        del keep
+        return {k: v for k, v in out.items() if v is not None}
+
+    def advance_vjp_device(self, cur: "DeviceBatch", plan: AdvancePlan, step: int, gcap_carry, applied=None, max_pilot=None, gdir=None,
+                           gx=None, gq_next=None, gcap_vjp_next=None, gcap_carry_next=None, horizon_next=None, flags_next=None,
+                           garr=None, gprice=None, use_status: bool = True, stream: int = 0, seg_row=0) -> None:
+        """acnqp_advance_vjp_device: the same on device memory, for the ``DeviceBatch`` ``cur`` of step ``step`` after its solve
+        (``cur.x``, ``cur.status`` are read at step >= 0) and ``plan`` from ``AdvancePlan.to_device``.  Float64 device tensors:
+        ``applied``, ``gdir`` (B, N), ``max_pilot`` (N,), ``gq_next`` (B, N, Tm), ``gcap_vjp_next``, ``gcap_carry_next`` and the
+        output ``gcap_carry`` (B, K, N), the outputs ``gx`` (B, N, Tm), ``garr`` (A,) and ``gprice`` (B, P); int32:
+        ``horizon_next``, ``flags_next`` (B,).  ``garr`` and ``gprice`` are accumulated over a sweep: zero them once.
+        Asynchronous on ``stream``."""
+        B, N, Tm, K = cur.B, cur.N, cur.Tm, cur.K
+        d = cur.s_cap.device
+        P = None if plan.c_series is None else int(plan.c_series.shape[1])
+        for t, name, dt, shape in ((applied, "applied", _F8, (B, N)), (max_pilot, "max_pilot", _F8, (N,)), (gdir, "gdir", _F8, (B, N)),
+                                   (gx, "gx", _F8, (B, N, Tm)), (gq_next, "gq_next", _F8, (B, N, Tm)),
+                                   (gcap_vjp_next, "gcap_vjp_next", _F8, (B, K, N)), (gcap_carry_next, "gcap_carry_next", _F8, (B, K, N)),
+                                   (horizon_next, "horizon_next", _I4, (B,)), (flags_next, "flags_next", _I4, (B,)),
+                                   (gcap_carry, "gcap_carry", _F8, (B, K, N)), (garr, "garr", _F8, (plan._len("a_evse"),)),
+                                   (gprice, "gprice", _F8, None if P is None else (B, P))):
+            _want(t, name, dt, shape, d)
+        if gcap_carry is None:
+            raise ValueError("gcap_carry must be given")
+        pl, cost = self._advance_vjp_plan(plan, step, seg_row)
+        p = _device_problems(cur)
+        at = step >= 0
+        _check(
+            self._lib.acnqp_advance_vjp_device(self._h, C.byref(p), _dptr(applied), _dptr(cur.status) if use_status and at else None,
+                                               _dptr(cur.x) if at else None, C.byref(pl), None if cost is None else C.byref(cost),
+                                               _dptr(max_pilot), _dptr(gdir), _dptr(gq_next), _dptr(gcap_vjp_next), _dptr(gcap_carry_next),
+                                               _dptr(horizon_next), _dptr(flags_next), _dptr(gx), _dptr(gcap_carry),
+                                               _dptr(garr) if garr is not None and garr.numel() else None, _dptr(gprice), C.c_void_p(stream)),
+            "acnqp_advance_vjp_device",
+        )
 
     # -- before the solve (acn_qp_prepare.hpp) ---------------------------------------------------------------------------
     def prepare_host(self, cur: dict, plan: PreparePlan, want_view: bool = True, min_rates: bool = True, key_row=None) -> dict:

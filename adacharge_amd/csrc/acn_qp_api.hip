@@ -20,6 +20,7 @@
 #include "acn_qp_duals.hpp"
 #include "acn_qp_pilots.hpp"
 #include "acn_qp_advance.hpp"
+#include "acn_qp_advance_vjp.hpp"
 #include "acn_qp_prepare.hpp"
 #include "acn_qp_plant.hpp"
 #include "acn_qp_estimate.hpp"

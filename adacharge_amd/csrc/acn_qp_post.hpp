@@ -20,6 +20,7 @@ struct Staged {
   static Staged in(const void* s, size_t b) { return {s, nullptr, b, false}; }
   static Staged out(void* d, size_t b) { return {nullptr, d, b, false}; }
   static Staged inout(void* p, size_t b) { return {p, p, b, false}; }   // uploaded, changed in place, downloaded
+  static Staged plan_inout(void* p, size_t b) { return {p, p, b, true}; }   // a whole-call array the chunks write into: downloaded once, at the end
 };
 
 struct StageAddr { void* p; template <class T> operator T*() const { return static_cast<T*>(p); } };   // a staging address, as its field's pointer type
@@ -81,8 +82,11 @@ int run_staged(acnqp_handle* h, const acnqp::Staged* a, int n, size_t batch, Bod
     const int rc = body(lo, nb, dev);
     if (rc != ACNQP_OK) return rc;
     for (int k = 0; k < n; ++k)
-      if (a[k].bytes && a[k].dst)
+      if (!a[k].whole && a[k].bytes && a[k].dst)
         HIP_TRY(hipMemcpyAsync(static_cast<char*>(a[k].dst) + a[k].bytes * lo, dev(k), a[k].bytes * nb, hipMemcpyDeviceToHost, st));
+    if (lo + nb >= batch)
+      for (int k = 0; k < n; ++k)
+        if (a[k].whole && a[k].bytes && a[k].dst) HIP_TRY(hipMemcpyAsync(a[k].dst, dev(k), a[k].bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   return ACNQP_OK;
@@ -392,6 +396,133 @@ int acnqp_advance_priced_host(acnqp_handle* h, const acnqp_problems* c, const do
 int acnqp_advance_host(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
                        const double* y, const acnqp_advance_plan* pl, acnqp_next* nx, int32_t* flags) {
   return acnqp_advance_priced_host(h, c, applied, status, x, y, pl, nullptr, nx, flags);
+}
+
+// ---- the adjoint of time passes (acn_qp_advance_vjp.hpp) ----------------------------------------------------------------
+static int check_advance_vjp_args(const acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
+                                  const acnqp_advance_plan* pl, const acnqp_clock_cost* cost, const double* max_pilot, const double* gdir,
+                                  const double* gq_next, const double* gcap_vjp_next, const double* gcap_carry_next, const int32_t* horizon_next,
+                                  const int32_t* flags_next, const double* gx, const double* gcap_carry, const double* garr, const double* gprice,
+                                  const char* who) {
+  const std::string w(who);
+  if (!h) return fail(ACNQP_ERR_INVALID, w + ": null handle");
+  if (!c || !pl) return fail(ACNQP_ERR_INVALID, w + ": null argument");
+  const acnqp::SiteShape& s = h->shape;
+  if (s.has_flat || s.has_max)
+    return fail(ACNQP_ERR_INVALID, w + ": a site with a load-flattening or demand-charge row is not served (the demand-charge floor and the "
+                                       "flat row's signal get no adjoint)");
+  if (pl->n_evse != s.N || pl->n_rows != s.Mg)
+    return fail(ACNQP_ERR_INVALID, w + ": the plan is for " + std::to_string(pl->n_evse) + " EVSEs and " + std::to_string(pl->n_rows) +
+                                       " site rows, the handle's site has " + std::to_string(s.N) + " and " + std::to_string(s.Mg));
+  if (gprice && !cost) return fail(ACNQP_ERR_INVALID, w + ": gprice is given without a clock cost: there is no price to differentiate");
+  if (cost) {
+    if (cost->n_evse != s.N)
+      return fail(ACNQP_ERR_INVALID, w + ": the clock cost is for " + std::to_string(cost->n_evse) + " EVSEs, the handle's site has " + std::to_string(s.N));
+    if (!cost->weight) return fail(ACNQP_ERR_INVALID, w + ": null weight of the clock cost");
+    uint64_t u;   // by its bits: this file is compiled with -fno-honor-nans
+    std::memcpy(&u, &cost->coef, sizeof u);
+    if ((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull) return fail(ACNQP_ERR_INVALID, w + ": the clock cost's coef is not finite");
+  }
+  if (c->batch < 0) return fail(ACNQP_ERR_INVALID, w + ": negative batch");
+  if (c->batch == 0) return ACNQP_OK;
+  if (c->t_max < 1 || c->t_max > 4096) return fail(ACNQP_ERR_INVALID, w + ": t_max must be in [1, 4096]");
+  if (c->k_sessions < 1 || c->k_sessions > acnqp::kAdvVjpMaxK)
+    return fail(ACNQP_ERR_INVALID, w + ": k_sessions is " + std::to_string(c->k_sessions) + ", 1 ... 4 session slots are served");
+  const size_t B = (size_t)c->batch, N = (size_t)s.N, Tm = (size_t)c->t_max, K = (size_t)c->k_sessions;
+  if (B * K * N > ((size_t)1 << 31) || B * N * Tm > ((size_t)1 << 40)) return fail(ACNQP_ERR_INVALID, w + ": batch too large");
+  if (!c->s_off || !c->s_len || !c->s_cap || !gcap_carry) return fail(ACNQP_ERR_INVALID, w + ": null s_off, s_len, s_cap or gcap_carry");
+  if (pl->step < -1) return fail(ACNQP_ERR_INVALID, w + ": step must be >= -1");
+  if (pl->step >= 0) {
+    if (!x) return fail(ACNQP_ERR_INVALID, w + ": x is null at step " + std::to_string(pl->step) + ": the clip of the pilot rule reads the step's schedule (only step -1 has none)");
+    if (!applied || !gdir || !gx || !max_pilot) return fail(ACNQP_ERR_INVALID, w + ": null applied, gdir, gx or max_pilot at step >= 0");
+  }
+  if (pl->n_arrivals < 0 || pl->n_rates < 0) return fail(ACNQP_ERR_INVALID, w + ": negative n_arrivals or n_rates");
+  if (pl->n_arrivals > 0 && pl->a_seg && (!pl->a_evse || !pl->a_slot || !pl->a_len || !pl->a_rate_seg || !garr))
+    return fail(ACNQP_ERR_INVALID, w + ": null arrival array or garr");
+  const bool prices = gprice && gq_next;
+  if (prices && !horizon_next) return fail(ACNQP_ERR_INVALID, w + ": gprice and gq_next are given but horizon_next is null");
+  if (cost && gprice && (long long)cost->series_len < (long long)pl->step + 1 + c->t_max)
+    return fail(ACNQP_ERR_INVALID, w + ": series_len is " + std::to_string(cost->series_len) + ", the prices of step + 1 + t_max = " +
+                                       std::to_string((long long)pl->step + 1 + c->t_max) + " periods are written");
+  struct Span { const void* p; size_t n; const char* name; };
+  const size_t nb = B * N * Tm * 8, ns4 = B * K * N * 4, ns8 = B * K * N * 8, A = pl->a_seg ? (size_t)pl->n_arrivals : 0;
+  const bool at = pl->step >= 0;
+  const Span in[] = {{c->s_off, ns4, "s_off"}, {c->s_len, ns4, "s_len"}, {c->s_cap, ns8, "s_cap"}, {at ? applied : nullptr, B * N * 8, "applied"},
+                     {at ? status : nullptr, B * 4, "status"}, {at ? x : nullptr, nb, "x"}, {at ? max_pilot : nullptr, N * 8, "max_pilot"},
+                     {at ? gdir : nullptr, B * N * 8, "gdir"}, {gq_next, nb, "gq_next"}, {gcap_vjp_next, ns8, "gcap_vjp_next"},
+                     {gcap_carry_next, ns8, "gcap_carry_next"}, {horizon_next, B * 4, "horizon_next"}, {flags_next, B * 4, "flags_next"},
+                     {cost ? cost->weight : nullptr, N * 8, "cost->weight"}};
+  const Span out[] = {{at ? gx : nullptr, nb, "gx"}, {gcap_carry, ns8, "gcap_carry"}, {garr, A * 8, "garr"},
+                      {gprice, cost ? B * (size_t)cost->series_len * 8 : 0, "gprice"}};
+  const size_t n_out = sizeof(out) / sizeof(out[0]);
+  for (size_t a = 0; a < n_out; ++a) {
+    for (const Span& sp : in)
+      if (acnqp::spans_meet(out[a].p, out[a].n, sp.p, sp.n))
+        return fail(ACNQP_ERR_INVALID, w + ": an output aliases an input (" + out[a].name + " overlaps " + sp.name + ")");
+    for (size_t b2 = a + 1; b2 < n_out; ++b2)
+      if (acnqp::spans_meet(out[a].p, out[a].n, out[b2].p, out[b2].n))
+        return fail(ACNQP_ERR_INVALID, w + ": two outputs overlap (" + out[a].name + " and " + out[b2].name + ")");
+  }
+  return ACNQP_OK;
+}
+
+int acnqp_advance_vjp_device(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
+                             const acnqp_advance_plan* pl, const acnqp_clock_cost* cost, const double* max_pilot, const double* gdir,
+                             const double* gq_next, const double* gcap_vjp_next, const double* gcap_carry_next, const int32_t* horizon_next,
+                             const int32_t* flags_next, double* gx, double* gcap_carry, double* garr, double* gprice, void* hip_stream) {
+  const int rc = check_advance_vjp_args(h, c, applied, status, x, pl, cost, max_pilot, gdir, gq_next, gcap_vjp_next, gcap_carry_next, horizon_next,
+                                        flags_next, gx, gcap_carry, garr, gprice, "acnqp_advance_vjp_device");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  acnqp::AdvanceVjpArgs a;
+  a.B = c->batch; a.N = h->shape.N; a.Tm = c->t_max; a.K = c->k_sessions;
+  a.s_off = c->s_off; a.s_len = c->s_len; a.s_cap = c->s_cap;
+  a.applied = applied; a.status = status; a.x = x; a.max_pilot = max_pilot; a.gdir = gdir;
+  a.step = pl->step; a.A = pl->n_arrivals; a.R = pl->n_rates; a.done_tol = pl->done_tol;
+  a.a_seg = pl->n_arrivals > 0 ? pl->a_seg : nullptr;
+  a.a_evse = pl->a_evse; a.a_slot = pl->a_slot; a.a_len = pl->a_len; a.a_rate_seg = pl->a_rate_seg;
+  if (cost) { a.c_P = cost->series_len; a.c_coef = cost->coef; a.c_weight = cost->weight; }
+  a.gq_next = gq_next; a.gcap_vjp_next = gcap_vjp_next; a.gcap_carry_next = gcap_carry_next;
+  a.horizon_next = horizon_next; a.flags_next = flags_next;
+  a.gx = gx; a.gcap_carry = gcap_carry; a.garr = garr; a.gprice = cost ? gprice : nullptr;
+  (void)hipGetLastError();
+  const hipError_t e = acnqp::launch_advance_vjp(a, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(ACNQP_ERR_HIP, std::string("advance vjp kernel launch: ") + hipGetErrorString(e));
+  return ACNQP_OK;
+}
+
+int acnqp_advance_vjp_host(acnqp_handle* h, const acnqp_problems* c, const double* applied, const int32_t* status, const double* x,
+                           const acnqp_advance_plan* pl, const acnqp_clock_cost* cost, const double* max_pilot, const double* gdir,
+                           const double* gq_next, const double* gcap_vjp_next, const double* gcap_carry_next, const int32_t* horizon_next,
+                           const int32_t* flags_next, double* gx, double* gcap_carry, double* garr, double* gprice) {
+  const int rc = check_advance_vjp_args(h, c, applied, status, x, pl, cost, max_pilot, gdir, gq_next, gcap_vjp_next, gcap_carry_next, horizon_next,
+                                        flags_next, gx, gcap_carry, garr, gprice, "acnqp_advance_vjp_host");
+  if (rc != ACNQP_OK || c->batch == 0) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t B = (size_t)c->batch, N = (size_t)h->shape.N, Tm = (size_t)c->t_max, K = (size_t)c->k_sessions, nv = N * Tm * 8, ns = K * N;
+  const bool at = pl->step >= 0;
+  const size_t A = pl->a_seg ? (size_t)pl->n_arrivals : 0, CP = cost && gprice ? (size_t)cost->series_len : 0;
+  enum { SEG, AEV, ASL, ALN, ARS, CW, MAXP, GARR, SOFF, SLEN, SCAP, APP, STAT, X, GDIR, GQN, GVN, GCN, HZN, FLN, GX, GCAR, GPR, NARR };
+  const S arr[NARR] = {
+      S::plan(pl->a_seg, A ? (B + 1) * 4 : 0), S::plan(pl->a_evse, A * 4), S::plan(pl->a_slot, A * 4), S::plan(pl->a_len, A * 4),
+      S::plan(pl->a_rate_seg, A ? (A + 1) * 4 : 0), S::plan(cost ? cost->weight : nullptr, cost ? N * 8 : 0), S::plan(max_pilot, at ? N * 8 : 0),
+      S::plan_inout(garr, A * 8),   // (only the records of this call's segments are written: the caller's other entries go up and come back)
+      S::in(c->s_off, ns * 4), S::in(c->s_len, ns * 4), S::in(c->s_cap, ns * 8), S::in(applied, at ? N * 8 : 0), S::in(status, at && status ? 4 : 0),
+      S::in(x, at ? nv : 0), S::in(gdir, at ? N * 8 : 0), S::in(gq_next, gq_next ? nv : 0), S::in(gcap_vjp_next, gcap_vjp_next ? ns * 8 : 0),
+      S::in(gcap_carry_next, gcap_carry_next ? ns * 8 : 0), S::in(horizon_next, horizon_next ? 4 : 0), S::in(flags_next, flags_next ? 4 : 0),
+      S::out(gx, at ? nv : 0), S::out(gcap_carry, ns * 8), S::inout(gprice, CP * 8)};
+  return run_staged(h, arr, NARR, B, [&](size_t lo, size_t nb, auto dev) {
+    acnqp_problems cc = *c;
+    cc.batch = (int32_t)nb;
+    cc.s_off = dev(SOFF); cc.s_len = dev(SLEN); cc.s_cap = dev(SCAP);
+    acnqp_advance_plan pc = *pl;
+    pc.a_seg = A ? (const int32_t*)dev(SEG) + lo : nullptr;   // (absolute record indices: the arrival arrays stay whole)
+    pc.a_evse = dev(AEV); pc.a_slot = dev(ASL); pc.a_len = dev(ALN); pc.a_rate_seg = dev(ARS);
+    acnqp_clock_cost kc{};
+    if (cost) { kc = *cost; kc.weight = dev(CW); kc.series = nullptr; }
+    return acnqp_advance_vjp_device(h, &cc, dev(APP), dev(STAT), dev(X), &pc, cost ? &kc : nullptr, dev(MAXP), dev(GDIR), dev(GQN), dev(GVN),
+                                    dev(GCN), dev(HZN), dev(FLN), dev(GX), dev(GCAR), dev(GARR), dev(GPR), h->slot[0].st);
+  });
 }
 
 // ---- before the solve (acn_qp_prepare.hpp) ------------------------------------------------------------------------------

@@ -11,15 +11,22 @@ active set at the solver's answer (include/acn_qp.h says how it is taken): accur
 problem: their gradients come from ``SiteHandle.vjp_device`` directly.  Served shapes: N <= 64, K <= 4, no load-flattening
 or demand-charge row, and horizons <= 32 on any handle; horizons 33 ... 288 on a ``SiteHandle(site, device, vjp_long=True)``
 whose site has at least one row (and at most 48 rows of G).  Another shape raises ValueError in backward, with the reason.
+
+``simulate_prices`` is the same for the CLOSED LOOP: a whole ``simulate_batch`` rollout as one differentiable operation of the
+tariff, its backward the sweep of ``rollout.rollout_gradients``.
+
+    pilots = simulate_prices(alg, table, prices)          # (steps, B, N) float64 on the GPU, what went to the chargers
+    (w * pilots).sum().backward()                          # prices.grad (B, P)
 """
 from __future__ import annotations
 
 import warnings
 from typing import Optional
 
+import numpy as np
 import torch
 
-from .backend import _PROBLEM_ARRAYS, DeviceBatch, Options, SiteHandle, default_options
+from .backend import ACCEPTED_STATUSES, _PROBLEM_ARRAYS, DeviceBatch, Options, SiteHandle, default_options
 
 _last_info = None      # info (B, 4) int32 of the most recent backward, still on the device
 _warned = False
@@ -75,8 +82,48 @@ def solve_qp(handle: SiteHandle, template: DeviceBatch, q, s_cap, lb, ub, peak=N
     return _SolveQP.apply(handle, template, options if options is not None else default_options(), q, s_cap, lb, ub, peak)
 
 
+class _SimulatePrices(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, alg, table, prices):
+        from .rollout import simulate
+
+        if table.c_series is None:
+            raise ValueError("simulate_prices needs a FleetTable whose objective has a tou_energy_cost component")
+        B, need = table.c_series.shape
+        if prices.dim() != 2 or prices.shape[0] != B or prices.shape[1] < need or prices.dtype != torch.float64:
+            raise ValueError(f"prices must be a float64 tensor of shape ({B}, P) with P >= steps + t_max = {need}")
+        table.c_series[...] = prices.detach()[:, :need].cpu().numpy()   # (the plan reads this array: the table now carries these prices)
+        result = simulate(alg, table, table.steps, table.start, keep_tape=True)
+        ctx.result, ctx.shape, ctx.where = result, tuple(prices.shape), prices.device
+        tape = result.tape
+        served = torch.from_numpy(np.isin(result.status, ACCEPTED_STATUSES)).to(tape.pilots.device)[..., None]
+        # what the advance saw: a step whose solve was not accepted delivered nothing (RolloutResult.pilots says the same)
+        return torch.where(served, tape.pilots, torch.zeros((), dtype=torch.float64, device=tape.pilots.device))
+
+    @staticmethod
+    def backward(ctx, grad_pilots):
+        global _last_info
+        from .rollout import rollout_gradients
+
+        g = rollout_gradients(ctx.result, grad_pilots.contiguous())
+        _last_info = g.info.reshape(-1, 4)
+        out = torch.zeros(ctx.shape, dtype=torch.float64, device=g.prices.device)
+        out[:, : g.prices.shape[1]] = g.prices
+        return None, None, out.to(ctx.where)
+
+
+def simulate_prices(alg, table, prices):
+    """The pilots (steps, B, N) of the closed-loop rollout ``alg.simulate_batch(table, table.steps, table.start,
+    keep_tape=True)`` under the tariff ``prices`` -- a float64 tensor (B, P), entry 0 the price of the run's first period,
+    P >= steps + t_max -- as a float64 tensor on the rollout's GPU, differentiable in ``prices``.  ``table`` is a
+    ``rollout.FleetTable`` whose objective holds ``tou_energy_cost``; the prices are written into its series, so the table
+    carries them afterwards.  The gradient is the one THROUGH the loop (``rollout.rollout_gradients`` says what a loss
+    that also reads the prices directly adds).  What ``keep_tape=True`` does not serve raises ValueError in forward."""
+    return _SimulatePrices.apply(alg, table, prices)
+
+
 def check_last_backward() -> int:
-    """How many problems of the most recent backward got no gradient (a verdict other than 0 in ``info``: not solved, or an
+    """How many problems of the most recent backward (of ``simulate_prices``: over all its steps) got no gradient (a verdict other than 0 in ``info``: not solved, or an
     active set beyond the kernel's tables -- their gradients are exact zeros).  Reads ``info``, so it waits for the device:
     call it when convenient, not in the training step's hot path.  Warns the first time the count is not zero."""
     global _warned

@@ -10,6 +10,11 @@ With ``resolve="events"`` the loop is the one around the reference's ``schedule(
 ``FleetTable.resolve_rows(max_recompute)`` says so -- step 0, plug-in and unplug events, every ``max_recompute`` periods --
 and keeps the schedule it holds in between: ``acnqp_select_device -> solve -> acnqp_hold_device`` in place of the solve.
 
+``simulate(..., keep_tape=True)`` keeps every step's state on the device and ``rollout_gradients`` runs the backward sweep
+through the whole loop: per step ``acnqp_advance_vjp_device`` (the adjoint of "time passes") and ``acnqp_vjp_device`` (the
+adjoint of the solve), for the gradients of a scalar of the applied pilots with respect to the tariff, the requested
+energies and the site rows' limits.
+
 ``FleetTable`` is everything the loop needs that does not depend on what the solver answers, computed once for the whole
 run: the arrival records of every step (the layout of ``acnqp_advance_plan``), the linear cost and the scalars of every
 horizon 1 .. Tm (``builder.objective_terms``), and the peak-limit series.  This is online MPC as in the reference's closed
@@ -19,7 +24,7 @@ from __future__ import annotations
 
 import copy
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import Any, List, Optional, Sequence
 
 import numpy as np
 
@@ -51,6 +56,46 @@ class RolloutResult:
                                                  # False, ``status`` is that of the solve the step's pilots came from and ``iters`` is 0
     resolve_flags: Optional[np.ndarray] = None   # (steps, B) int32: per scenario, the flags of acnqp_hold_device OR-ed with those of
                                                  # acnqp_select_device for its row of the step's dense batch (resolve="events")
+    tape: Optional["RolloutTape"] = None         # what ``rollout_gradients`` reads (keep_tape=True)
+
+
+@dataclass
+class RolloutTape:
+    """What the backward sweep of a rollout reads, all of it on the device and none of it copied: the forward loop wrote
+    these tensors and the tape only keeps them alive."""
+    handle: Any
+    table: "FleetTable"
+    plan: Any            # the AdvancePlan on the device, as the forward advances took it
+    max_pilot: Any       # (N,) of the continuous pilot rule
+    options: Any
+    states: list         # steps DeviceBatches: problem, x, y and status of every step
+    start: Any           # the empty DeviceBatch the run started from (step -1)
+    pilots: Any          # (steps, B, N) as the pilot kernel wrote them
+    flags: Any           # (steps, B) int32 of the advance that built each step's problems
+
+
+@dataclass
+class RolloutGradients:
+    """``rollout_gradients``: float64 tensors on the rollout's device unless stated."""
+    prices: Any          # (B, P) dL/d(price series) through the problems' linear cost; None without a clock cost
+    limits: Any          # (B, M) dL/d(limit of a site row), summed over steps and periods
+    info: Any            # (steps, B, 4) int32 of every step's acnqp_vjp_device (verdict 0: done)
+    res: Any             # (steps, B, 2)
+    garr: Any            # (A,) dL/d(a_cap) of the plan's arrival records, in A-periods
+    table: Any = None
+
+    @property
+    def requested(self) -> List[np.ndarray]:
+        """per scenario, dL/d(requested kWh) of every record of its fleet in the fleet's order; 0 for a record the table
+        never admitted.  Reads ``garr``, so it waits for the device."""
+        t = self.table
+        g = self.garr.cpu().numpy()
+        out = [np.zeros(len(f)) for f in t.fleets]
+        order = sorted(range(len(t._stays)), key=lambda j: (t._stays[j][2], t._stays[j][0]))   # the plan's record order (stable)
+        for r, j in enumerate(order):
+            b, i, _, _, n, _ = t._stays[j]
+            out[b][n] = g[r] / t.kwh_per_amp_period[i]
+        return out
 
 
 class FleetTable:
@@ -365,8 +410,19 @@ class FleetTable:
 
 
 def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = False, return_schedules: bool = False,
-             observer=None, session_order: Optional[str] = None, prices=None, resolve: str = "every_step") -> RolloutResult:
-    """``AdaptiveSchedulingAlgorithm.simulate_batch``: see there."""
+             observer=None, session_order: Optional[str] = None, prices=None, resolve: str = "every_step",
+             keep_tape: bool = False) -> RolloutResult:
+    """``AdaptiveSchedulingAlgorithm.simulate_batch``: see there.
+    ``keep_tape=True`` keeps what ``rollout_gradients`` needs in ``RolloutResult.tape``: instead of ping-ponging two
+    ``DeviceBatch``es the loop writes every step's problems into a batch of their own (with the site-row multipliers y),
+    and the tape holds these ``steps`` batches and the empty one the run starts from, the handle, the plan, the options and
+    ``flags``.  Nothing is copied and nothing is launched beyond what the forward launches.  The tape holds
+    ``(steps + 1) * B * (32 N Tm + 8 Mg Tm + 16 K N + 8 Tm [peak row] + 69)`` bytes of states (lb, ub, q, x; y; the slot
+    tables; peak; the scalars and result fields) beside the ``steps * B * (8 N + 12)`` of pilots, status and flags every
+    rollout holds.  Served with a tape: ``resolve="every_step"`` (or an events run that solves every step), continuous
+    pilots, no battery, no estimator, no ``session_order`` step, and a site the vjp kernels serve (N <= 64, no
+    load-flattening or demand-charge row, t_max <= 32, or <= 288 with ``solver_options={"vjp_long": True}``); anything else
+    raises ``ValueError`` before anything is launched."""
     if resolve not in RESOLVE_MODES:
         raise ValueError(f'resolve must be "every_step" or "events", not {resolve!r}')
     import torch
@@ -420,6 +476,8 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             counts = rplan.counts()
             table_seg = np.asarray(rplan.sel_seg)
             host_idx = np.asarray(rplan.sel_idx)
+    if keep_tape:
+        _refuse_tape(alg, table, session_order, rplan)
     opts = dict(alg.solver_options or {})
     site, handle = _site_handle(infra, alg.constraint_type, table.has_peak, alg.device, with_flat=table.need_flat, with_max=table.need_max,
                                 polish_long=bool(opts.pop("polish_long", False)), polish_wide=bool(opts.pop("polish_wide", False)),
@@ -465,7 +523,9 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
                 handle.prepare_device(state, prplan, pflags[row], *view, min_rates=min_rates, key_row=row, stream=stream)
         s_eq = 1 if alg.enforce_energy_equality else 0
         want_y = warm_start and site.Mg > 0
-        bufs = [backend.DeviceBatch.empty(site, B, Tm, K, dev, want_y=want_y, s_eq=s_eq, dfloor=table.dfloor0) for _ in range(2)]
+        # two states that ping-pong; with a tape, one per step and behind them the empty one the run starts from
+        bufs = [backend.DeviceBatch.empty(site, B, Tm, K, dev, want_y=want_y or keep_tape, s_eq=s_eq, dfloor=table.dfloor0)
+                for _ in range(steps + 1 if keep_tape else 2)]
         pilots = torch.zeros((steps, B, N), dtype=torch.float64, device=dev)
         status = torch.zeros((steps, B), dtype=torch.int32, device=dev)
         iters = torch.zeros((steps, B), dtype=torch.int32, device=dev)
@@ -516,11 +576,11 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
             view.own_ub, view.ub = state.ub, capped
             return view
         # the first period's problems: time "passes" on an empty state, its arrivals are admitted
-        handle.advance_device(bufs[1], bufs[0], nothing, plan, -1, flags[0], use_status=False, stream=stream, seg_row=0)
+        handle.advance_device(bufs[-1], bufs[0], nothing, plan, -1, flags[0], use_status=False, stream=stream, seg_row=0)
         solve_next = estimate(bufs[0], 0)
         prepare(solve_next, 0)
         for s in range(steps):
-            state, nxt = bufs[s % 2], bufs[(s + 1) % 2]
+            state, nxt = bufs[s % len(bufs)], bufs[(s + 1) % len(bufs)]
             cur = solve_next
             warm = want_y and s > 0   # (a site without rows has no multipliers to carry: it starts cold)
             if held and counts[s] < B:
@@ -573,4 +633,88 @@ def simulate(alg, fleets, steps: int, start_time: int = 0, warm_start: bool = Fa
                              None if xs is None else xs.cpu().numpy(), vis, None if pflags is None else pflags.cpu().numpy(),
                              table.energy_cost(drawn), None if actual is None else drawn, None if plflags is None else plflags.cpu().numpy(),
                              None if ests is None else ests.cpu().numpy(), None if eflags is None else eflags.cpu().numpy(),
-                             was_solved, rflags)
+                             was_solved, rflags,
+                             RolloutTape(handle, table, plan, pplan.max_pilot, options, bufs[:steps], bufs[-1], pilots, flags) if keep_tape else None)
+
+
+def _refuse_tape(alg, table: FleetTable, session_order, rplan) -> None:
+    """what ``keep_tape=True`` does not serve, each with its reason"""
+    why = None
+    if alg.quantize:
+        why = "quantize: a quantised pilot is piecewise constant in the schedule, there is no gradient to carry"
+    elif table.has_plant:
+        why = "a battery: the plant between the pilots and the advance has no adjoint"
+    elif alg.estimate_max_rate:
+        why = "estimate_max_rate: the estimator's state has no adjoint"
+    elif rplan is not None:
+        why = 'resolve="events" with a held step: a held schedule has no adjoint (max_recompute=1 solves every step)'
+    elif session_order is not None:
+        why = "a stated session_order: the prepare step between the advance and the solve has no adjoint"
+    elif table.need_flat or table.need_max:
+        why = "load_flattening / demand_charge: the gradients through the solve serve no site with a flat or max row"
+    elif table.N > 64:
+        why = f"a site of {table.N} EVSEs: the gradients through the solve serve at most 64"
+    else:
+        long = bool((alg.solver_options or {}).get("vjp_long", False))
+        if table.Tm > (288 if long else 32):
+            why = (f"t_max = {table.Tm}: the gradients through the solve serve horizons up to 32, and up to 288 with "
+                   'solver_options={"vjp_long": True}')
+    if why:
+        raise ValueError(f"simulate_batch(keep_tape=True) does not serve {why}")
+
+
+def rollout_gradients(result: RolloutResult, grad_pilots) -> RolloutGradients:
+    """The gradients of a scalar L of the applied pilots of a rollout run with ``keep_tape=True``: ``grad_pilots`` (steps, B, N)
+    = dL/d(pilots), a numpy array or a tensor on the rollout's device.  The backward sweep visits the steps from the last
+    to the first; per step ``acnqp_advance_vjp_device`` (the adjoint of the advance that followed the step, the clip of
+    the pilot rule included) and ``acnqp_vjp_device`` (the adjoint of the step's solve), then one last call of the former
+    for the advance that built the first problems -- ``2 steps + 1`` launches on the current stream and no host
+    synchronisation.  Returns ``RolloutGradients``: ``prices`` (B, P), ``requested`` (per scenario, one value per fleet record,
+    in L per kWh), ``limits`` (B, M), and every step's ``info`` and ``res``.
+    These are the gradients THROUGH the loop.  A loss that reads a parameter also directly keeps that term for the caller:
+    the energy cost of ``FleetTable.energy_cost`` is ``sum pilots * weight * price``, so with ``w = table.c_weight`` and
+    ``p = table.c_series[:, :steps]``
+
+        g = rollout_gradients(result, np.einsum("i,bs->sbi", w, p))          # d cost / d pilots
+        dcost_dprice = g.prices.cpu().numpy(); dcost_dprice[:, :steps] += np.einsum("sbi,i->bs", result.pilots, w)
+
+    Steps whose solve was not accepted, or whose working set is beyond the vjp kernel's tables, pass no gradient
+    (``info[s, b, 0] != 0``)."""
+    import torch
+
+    tape = result.tape
+    if tape is None:
+        raise ValueError("rollout_gradients needs a rollout run with keep_tape=True")
+    handle, table, plan = tape.handle, tape.table, tape.plan
+    steps, B, N = tape.pilots.shape
+    Tm, K = table.Tm, table.K
+    dev = tape.pilots.device
+    M = handle.site.M
+    nrow = M + (1 if handle.site.has_peak else 0)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        gd = torch.as_tensor(grad_pilots, dtype=torch.float64, device=dev).contiguous()
+        if tuple(gd.shape) != (steps, B, N):
+            raise ValueError(f"grad_pilots must have shape {(steps, B, N)}")
+        f8 = dict(dtype=torch.float64, device=dev)
+        gx, gq = torch.empty((B, N, Tm), **f8), torch.empty((B, N, Tm), **f8)
+        gcap, grow = torch.empty((B, K, N), **f8), torch.empty((B, nrow, Tm), **f8)
+        carry = [torch.empty((B, K, N), **f8) for _ in range(2)]
+        info, res = torch.zeros((steps, B, 4), dtype=torch.int32, device=dev), torch.zeros((steps, B, 2), **f8)
+        garr = torch.zeros(plan._len("a_evse"), **f8)
+        gprice = None if plan.c_series is None else torch.zeros(tuple(plan.c_series.shape), **f8)
+        limits = torch.zeros((B, M), **f8)
+        nxt = {}   # the adjoints of the state one step later: nothing behind the last step
+        for s in range(steps - 1, -2, -1):
+            cur = tape.states[s] if s >= 0 else tape.start
+            at = s >= 0
+            handle.advance_vjp_device(cur, plan, s, carry[s % 2], applied=tape.pilots[s] if at else None, max_pilot=tape.max_pilot if at else None,
+                                      gdir=gd[s] if at else None, gx=gx if at else None, garr=garr, gprice=gprice, stream=stream,
+                                      seg_row=s + 1 if s + 1 < steps else None, **nxt)
+            if not at:
+                break
+            handle.vjp_device(cur, gx, gq, gcap, grow, info[s], res[s], options=tape.options, stream=stream)
+            if M:
+                limits.add_(grow[:, :M].sum(dim=2))
+            nxt = dict(gq_next=gq, gcap_vjp_next=gcap, gcap_carry_next=carry[s % 2], horizon_next=cur.horizon, flags_next=tape.flags[s])
+    return RolloutGradients(gprice, limits, info, res, garr, table)

@@ -610,6 +610,49 @@ int acnqp_advance_priced_host(acnqp_handle* h, const acnqp_problems* cur, const 
                               const double* x, const double* y, const acnqp_advance_plan* plan,
                               const acnqp_clock_cost* cost, acnqp_next* next, int32_t* flags);
 
+/* The adjoint of time passes (additive to ABI v10: new symbols only, no new struct) -- one call of the backward sweep
+ * through a closed loop solve -> continuous pilots -> advance.  L is a scalar of the pilots `applied` of every step, as
+ * the advance saw them.  The call for step s (plan->step = s, plan->a_seg the row the forward advance after period s
+ * took) reads the state of step s in `cur` (s_off, s_len, s_cap), applied [B*N], status [B] or NULL, the step's
+ * schedules x [B*N*Tm], max_pilot [N] of the continuous pilot rule, gdir [B*N] = dL/d applied of step s, and the adjoints
+ * of the state of step s + 1: gq_next [B*N*Tm] and gcap_vjp_next [B*K*N] (gq and gcap of that step's acnqp_vjp_device),
+ * gcap_carry_next [B*K*N] (gcap_carry of the previous call of this entry), horizon_next [B] (that state's horizon) and
+ * flags_next [B] (the flags of the advance that built it).  Each of the five may be NULL and then counts as zeros: the
+ * last step of a run has no next state.  For every problem b:
+ *   A1  G[k][i] = gcap_vjp_next[k][i] + gcap_carry_next[k][i], one addition: dL/d(s_cap) of the next state.
+ *   A2  with a clock cost, gprice and gq_next, where flags_next has no bit 2: for t < horizon_next,
+ *       gprice[b][step + 1 + t] += coef * (sum over i, increasing, of weight[i] * gq_next[i][t]) -- rule 6b's adjoint.
+ *       gprice [B*series_len] is accumulated over the calls of a sweep: the caller zeroes it once.
+ *   A3  rules 1, 2 and 4 are replayed on `cur` with the forward's comparisons: which slots are kept, which of those
+ *       were served (s_off == 0), which arrival records were admitted and into which slot.
+ *   A4  gcap_carry[k][i] = G[k][i] for a kept slot, exact 0 for any other.
+ *   A5  ga[i] = gdir[i], then minus G[k][i] for k ascending over the kept, served slots; exact 0 for a problem whose
+ *       status rule 1 does not serve.
+ *   A6  gx[i][0] = ga[i] where 0 <= x[i][0] <= max_pilot[i] (the clip is inactive), exact 0 elsewhere and for t >= 1:
+ *       the gx of acnqp_vjp_device for step s.
+ *   A7  garr[r] = G[k][i] for a record r of b's segment admitted into slot (k, i), exact 0 for a refused one.  garr [A]
+ *       is indexed like a_cap; records outside the call's segments are not written.
+ * step = -1 (the advance that built the first period's problems) reads no applied, status, x, max_pilot or gdir and
+ * writes no gx.  plan->a_seg == NULL: no arrival in this step.  The peak series and the demand-charge floor (rules 7, 8)
+ * get no adjoint.  tests/advance_vjp_spec.py states the rules in plain loops and the library returns its bits; no atomics.
+ * Refused with ACNQP_ERR_INVALID and acnqp_last_error set, before any device work and with the outputs untouched: a null
+ * handle, cur or plan; a site with a load-flattening or demand-charge row; n_evse or n_rows other than the handle's;
+ * k_sessions above 4; x, applied, gdir, gx or max_pilot NULL at step >= 0; gprice without a clock cost; gprice and gq_next
+ * without horizon_next; series_len < step + 1 + t_max; an output that overlaps an input or another output.  The clock
+ * cost's series is not read.  _device: device pointers, enqueued on `hip_stream`, no synchronisation.  _host: host
+ * pointers, synchronous, chunked like the other host entries; same bits.                                              */
+int acnqp_advance_vjp_device(acnqp_handle* h, const acnqp_problems* cur, const double* applied, const int32_t* status,
+                             const double* x, const acnqp_advance_plan* plan, const acnqp_clock_cost* cost,
+                             const double* max_pilot, const double* gdir, const double* gq_next,
+                             const double* gcap_vjp_next, const double* gcap_carry_next, const int32_t* horizon_next,
+                             const int32_t* flags_next, double* gx, double* gcap_carry, double* garr, double* gprice,
+                             void* hip_stream);
+int acnqp_advance_vjp_host(acnqp_handle* h, const acnqp_problems* cur, const double* applied, const int32_t* status,
+                           const double* x, const acnqp_advance_plan* plan, const acnqp_clock_cost* cost,
+                           const double* max_pilot, const double* gdir, const double* gq_next,
+                           const double* gcap_vjp_next, const double* gcap_carry_next, const int32_t* horizon_next,
+                           const int32_t* flags_next, double* gx, double* gcap_carry, double* garr, double* gprice);
+
 /* ---- before the solve (additive to ABI v10: new symbols only) --------------------------------------------------------
  * The link between the slot state an advance writes and the two steps of the reference that read the SESSION LIST:
  * apply_minimum_charging_rate (ada.py:147-150), a greedy walk in arrival order, and diff_based_reallocation
