@@ -629,9 +629,11 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
           im |= ((v > lbv[t]) & (v < ubv[t])) ? (1u << t) : 0u;
         }
       } else {
+        unsigned sw = swm;   // (decoded HERE: the plain path above reads no window mask, and must not pay for its decode)
+        asm volatile("" : "+v"(sw));
 #pragma unroll
         for (int t = 0; t < TS; ++t) {
-          const bool inw = (swm >> t) & 1u;
+          const bool inw = (sw >> t) & 1u;
           const real v = zin[t] - (inw ? m : 0.0);
           const real z = fmin(fmax(v, lbv[t]), ubv[t]);
           z1[t] = z;
@@ -653,9 +655,11 @@ __global__ __launch_bounds__(kWaveNW * 64, 1) void admm_wave_kernel(const TiledA
       const bool open = need & (nl <= 0.f) & !((lo > -big_) & (hi < big_));
       if (__any(open)) {   // flat piece with an open bracket (rare): the true bracket ends, so that the fallback bisects
         real lo_l = big_, hi_l = -big_;
+        unsigned sw = swm;   // (as in the general-windows evaluation: decoded where it is read)
+        asm volatile("" : "+v"(sw));
 #pragma unroll
         for (int t = 0; t < TS; ++t) {
-          const bool inw = (swm >> t) & 1u;
+          const bool inw = (sw >> t) & 1u;
           lo_l = inw ? fmin(lo_l, zin[t] - ubv[t]) : lo_l;
           hi_l = inw ? fmax(hi_l, zin[t] - lbv[t]) : hi_l;
         }
